@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- frames/s of DCL_Net.forward on synthetic YCB-V-shaped crops (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps K --warmup W [--shape stress|ref]
+    python bench.py --gpus 1 --steps K --warmup W [--shape stress|ref] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A step = one Network.forward over one batch of b=32 crops whose `data` dict is already resident in HBM.
-One process per GPU; ranks own disjoint crops (weak scaling, no data-path collective); the only RCCL
-traffic is the ADD-S metric all-reduce after the timed region.  Rank 0 prints ONE JSON line.
+One process per GPU; ranks own disjoint crops (weak scaling, no data-path collective).  Rank 0 prints ONE JSON line.
+A plain run sets up, warms up, times the K steps (and writes the last step's outputs with --dump-outputs) and prints
+the headline; --full then adds everything else the line reports (rooflines, the other workloads, the CPU baseline,
+and the ADD-S metric all-reduce -- the only RCCL traffic -- after the timed region).
 
 Workloads: "stress" = BASELINE.json configs[1] (bs 32, N=12288 observed, M=2048 model points) -- the headline;
 "ref" = what configs/config_YCBV_bs32.yaml really defines (N=M=1024), reported alongside as `ref_shape`.
@@ -170,32 +172,60 @@ def to_device(data, dev):
     return out
 
 
-def run_forward_bench(dcl, net, data, steps, warmup, distributed):
-    """returns (seconds for `steps` forwards, max over ranks; per-launch attention kernel times in ms)"""
+def run_forward_bench(dcl, net, data, steps, warmup, distributed, events=True, keep=None):
+    """returns (seconds for `steps` forwards, max over ranks; per-launch attention kernel times in ms -- empty unless
+    `events`); keep = a dict: it receives what the last timed forward returned"""
     dev = torch.device("cuda", torch.cuda.current_device())
     with torch.no_grad():
         for _ in range(warmup):
             net(data)
-        dcl.ops.PROFILE_EVENTS = []
+        dcl.ops.PROFILE_EVENTS = [] if events else None
         torch.cuda.synchronize()
         if distributed:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             net(data)
+        pred = net(data)
         torch.cuda.synchronize()
         if distributed:
             dist.barrier()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-    ev, dcl.ops.PROFILE_EVENTS = dcl.ops.PROFILE_EVENTS, None
+    ev, dcl.ops.PROFILE_EVENTS = dcl.ops.PROFILE_EVENTS or [], None
     att_ms = [a.elapsed_time(b) for (name, a, b) in ev if name == "cross_attention"]
+    if keep is not None:
+        keep.update(pred)
     if distributed:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     return dt, att_ms
+
+
+DUMP_MAX_ELEMS = 1 << 20       # per array: 4 MiB as float32 (the stress step's F_Xo_p alone has 100 M elements)
+
+
+def dump_outputs(pred, out_dir):
+    """--dump-outputs: every tensor the last timed forward returned, as out_dir/<name>.npy -- float64 tensors as float64, all
+    others as float32 (integer and bool ones as float64: exact).  An array of more than DUMP_MAX_ELEMS elements is stored as
+    the fixed sample of DUMP_MAX_ELEMS of its flattened elements that numpy's default_rng(0) draws (ascending indices), so two
+    builds run with the same arguments can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in sorted(pred.items()):
+        if not torch.is_tensor(t):
+            continue
+        t = t.detach()
+        t = t.float() if t.is_floating_point() and t.dtype != torch.float64 else t.double()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= 64 << 20, "dumped outputs exceed 64 MB"
 
 
 def primitives_roofline(dcl, reps=5):
@@ -831,85 +861,16 @@ def dry_run(args, rank, local_rank, world, cpus):
         dist.destroy_process_group()
 
 
-def main():
-    _flush_c_stdio(unbuffer=True)
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--shape", choices=list(SHAPES), default="stress")
-    ap.add_argument("--batch", type=int, default=32)
-    ap.add_argument("--no-extras", action="store_true", help="skip ref-shape / primitives / cpu baseline legs")
-    ap.add_argument("--pipelined-calls", action="store_true",
-                    help="let back-to-back forward calls overlap on the GPU (Network(async_inputs=True))")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the in-run PMC passes behind roofline.traffic")
-    ap.add_argument("--pmc-child", action="store_true",
-                    help="(internal) one warm-up + one forward of the workload and exit: the body of the PMC passes")
-    ap.add_argument("--dry-run", action="store_true",
-                    help="no GPU: the launcher / rank / affinity / sharding / metric-reduction plumbing over gloo with an "
-                         "empty step; prints the same JSON line with \"dry_run\": true and no rate (CPU test of the N > 1 path)")
-    args = ap.parse_args()
-
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.pmc_child:
-        # called without a launcher: start one rank per GPU as a CHILD (nothing has touched the GPU yet; never exec) and
-        # hand its output and exit code on
-        import subprocess
-        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
-               "--master-addr", "127.0.0.1", "--master-port", os.environ.get("MASTER_PORT", "29517"),
-               os.path.abspath(__file__)] + sys.argv[1:]
-        sys.exit(subprocess.call(cmd))
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    distributed = world > 1 or os.environ.get("DCL_FORCE_DIST") == "1"     # the latter: exercise the RCCL path on 1 GPU
-    # one process per GPU: before anything touches the GPU, every rank moves onto the host cores of its GPU's NUMA node
-    # (KFD topology in sysfs; an even split of the allowed cores if that cannot be read) -- sharding.rank_cpu_set
-    local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
-    cpus = importlib.import_module("dcl-net_amd").sharding.pin_rank_to_gpu_numa(local_rank, local_world)
-    if args.dry_run:
-        return dry_run(args, rank, local_rank, world, cpus)
-    torch.cuda.set_device(local_rank)
-    dev = torch.device("cuda", local_rank)
-    if distributed:
-        if world == 1:                                         # DCL_FORCE_DIST=1 without a launcher: a one-rank RCCL group
-            os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-            os.environ.setdefault("MASTER_PORT", "29511")
-            os.environ.setdefault("RANK", "0")
-            os.environ.setdefault("WORLD_SIZE", "1")
-        dist.init_process_group("nccl", device_id=dev)         # RCCL over xGMI
-    dcl = importlib.import_module("dcl-net_amd")
+def full_report(args, dcl, net, sd, cfg, host_data, data, dev, dt, att_ms, graphed, rank, local_rank, world, distributed, cpus):
+    """--full: everything the bench line reports beyond its headline, measured after the timed steps -> dict of extra keys"""
     b = args.batch
     n_inp, n_tmp = SHAPES[args.shape]
-    cfg = dcl.synth.default_cfg(n_inp, n_tmp)
-    # headline: strictly serial forward calls (the attention roofline is then measured on an otherwise idle GPU);
-    # --pipelined-calls lets back-to-back calls overlap (async_inputs: sparse half of call k+1 under the dense half of
-    # call k) -- reported as an extra at N=1
-    net = dcl.DCL_Net.Network(cfg, mode="test", async_inputs=args.pipelined_calls,
-                              **({"graph_max_batch": 0} if args.pmc_child else {}))   # counter passes: separate launches
-    sd = dcl.synth.synth_state_dict(net, 1)
-    net.load_state_dict(sd)
-    net = net.to(dev).eval()
-    host_data = dcl.synth.make_batch(b, n_inp, n_tmp, first=rank * b)          # disjoint crops per rank
-    data = to_device(host_data, dev)
-    if args.pmc_child:
-        with torch.no_grad():
-            net(data)
-            torch.cuda.synchronize()
-            time.sleep(0.05)                              # the pause measure_kernel_shares cuts the trace at
-            net(data)
-        torch.cuda.synchronize()
-        return
-
-    dt, att_ms = run_forward_bench(dcl, net, data, args.steps, args.warmup, distributed)
-    graphed = bool(net.__dict__.get("_graphs"))          # calls this small in points replay a whole-forward hipGraph (default)
     net_l = net
     if graphed:                                          # per-kernel timings (attention events, conv hooks) need separate launches
         net_l = dcl.DCL_Net.Network(cfg, mode="test", async_inputs=args.pipelined_calls, graph_max_batch=0)
         net_l.load_state_dict(sd)
         net_l = net_l.to(dev).eval()
         _, att_ms = run_forward_bench(dcl, net_l, data, max(5, args.steps // 2), 2, False)
-    frames = world * b * args.steps
-    value = frames / dt
 
     # roofline of the dominant hand-written kernel: the correspondence attention (2 launches per forward)
     flop_dir = [2.0 * (64 + 320) * n_inp * n_tmp * b] * 2     # dir 1: nq=N,nk=M ; dir 2: nq=M,nk=N -- same product
@@ -982,25 +943,8 @@ def main():
     rccl = collective_report(distributed, rank, world, {"device": "cuda:%d" % local_rank,
                                                         "name": torch.cuda.get_device_name(dev), "cpus": cpus})
 
-    line = {"metric": "frames/sec DCL_Net.forward @ YCB-V bs32", "value": round(value, 2), "unit": "frames/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32 (exact 3xbf16-split products on the bf16 MFMA, f32 accumulate)",
-            "data": "synthetic",
-            "dtype_note": "fp32 tensors, fp32 accumulators everywhere.  Sparse convs: fp32 MFMA.  The big per-point linear layers (and, "
-                          "where noted under `roofline`, the attention) form each fp32 product from the EXACT three-way bf16 split of "
-                          "both operands -- six bf16 piece products of weight >= 2^-16 on the bf16 MFMA, dropped terms <= 2^-25 of the "
-                          "product -- with errors against float64 equal to an fp32 FMA chain's (tests/test_gpu_ops.py: split core "
-                          "beside the fp32 core; every golden at the reference tolerances 1e-4 / 1e-5)",
-            "config": {"workload": "YCB-V bs=32 (config_YCBV_bs32.yaml), N=%d observed / M=%d model points per crop, "
-                                   "64^3 x 6 mm voxels; shape=%s" % (n_inp, n_tmp, args.shape),
-                       "global_batch": world * b, "frames_per_step_per_gpu": b, "parallelism": "frames sharded x%d" % world,
-                       "weights": "seeded random (no checkpoints offline)",
-                       "calls": "pipelined (async_inputs)" if args.pipelined_calls else "serial",
-                       "path": "whole-forward hipGraph replay" if graphed else "launch by launch"},
-            "roofline": roofline,
-            "whole_forward": whole_forward_rate(n_inp, n_tmp, b, dt / args.steps),
-            "adds_auc_synthetic_weights": auc, "metric_frames_reduced": int(table.sums[:, 0].sum()), "rccl": rccl}
+    line = {"roofline": roofline, "adds_auc_synthetic_weights": auc,
+            "metric_frames_reduced": int(table.sums[:, 0].sum()), "rccl": rccl}
     rdata_for_pipe = None
     if rank == 0 and world == 1 and not args.no_extras:
         line["roofline_sparse_conv"] = {args.shape: sparse_conv_roofline(dcl, net_l, data, dev)}
@@ -1086,6 +1030,112 @@ def main():
                                  "unit": "frames/s", "value": round(world * 40 * 20 / dt40, 2), "n_gpus": world,
                                  "ms_per_step": round(dt40 / 20 * 1e3, 3), "scaling": "weak"}
         del net40, d40
+    return line
+
+
+def main():
+    _flush_c_stdio(unbuffer=True)
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--shape", choices=list(SHAPES), default="stress")
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure and check everything else: attention / GEMM / sparse-conv rooflines, "
+                         "the ADD-S metric reduction, the other shapes, batches and call modes, primitives, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed forward returned (rank 0) as DIR/<name>.npy, float32 / float64")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip ref-shape / primitives / cpu baseline legs")
+    ap.add_argument("--pipelined-calls", action="store_true",
+                    help="let back-to-back forward calls overlap on the GPU (Network(async_inputs=True))")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: skip the in-run PMC passes behind roofline.traffic")
+    ap.add_argument("--pmc-child", action="store_true",
+                    help="(internal) one warm-up + one forward of the workload and exit: the body of the PMC passes")
+    ap.add_argument("--dry-run", action="store_true",
+                    help="no GPU: the launcher / rank / affinity / sharding / metric-reduction plumbing over gloo with an "
+                         "empty step; prints the same JSON line with \"dry_run\": true and no rate (CPU test of the N > 1 path)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.pmc_child:
+        # called without a launcher: start one rank per GPU as a CHILD (nothing has touched the GPU yet; never exec) and
+        # hand its output and exit code on
+        import subprocess
+        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
+               "--master-addr", "127.0.0.1", "--master-port", os.environ.get("MASTER_PORT", "29517"),
+               os.path.abspath(__file__)] + sys.argv[1:]
+        sys.exit(subprocess.call(cmd))
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    distributed = world > 1 or os.environ.get("DCL_FORCE_DIST") == "1"     # the latter: exercise the RCCL path on 1 GPU
+    # one process per GPU: before anything touches the GPU, every rank moves onto the host cores of its GPU's NUMA node
+    # (KFD topology in sysfs; an even split of the allowed cores if that cannot be read) -- sharding.rank_cpu_set
+    local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
+    cpus = importlib.import_module("dcl-net_amd").sharding.pin_rank_to_gpu_numa(local_rank, local_world)
+    if args.dry_run:
+        return dry_run(args, rank, local_rank, world, cpus)
+    torch.cuda.set_device(local_rank)
+    dev = torch.device("cuda", local_rank)
+    if distributed:
+        if world == 1:                                         # DCL_FORCE_DIST=1 without a launcher: a one-rank RCCL group
+            os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+            os.environ.setdefault("MASTER_PORT", "29511")
+            os.environ.setdefault("RANK", "0")
+            os.environ.setdefault("WORLD_SIZE", "1")
+        dist.init_process_group("nccl", device_id=dev)         # RCCL over xGMI
+    dcl = importlib.import_module("dcl-net_amd")
+    b = args.batch
+    n_inp, n_tmp = SHAPES[args.shape]
+    cfg = dcl.synth.default_cfg(n_inp, n_tmp)
+    # headline: strictly serial forward calls (the attention roofline is then measured on an otherwise idle GPU);
+    # --pipelined-calls lets back-to-back calls overlap (async_inputs: sparse half of call k+1 under the dense half of
+    # call k) -- reported as an extra at N=1
+    net = dcl.DCL_Net.Network(cfg, mode="test", async_inputs=args.pipelined_calls,
+                              **({"graph_max_batch": 0} if args.pmc_child else {}))   # counter passes: separate launches
+    sd = dcl.synth.synth_state_dict(net, 1)
+    net.load_state_dict(sd)
+    net = net.to(dev).eval()
+    host_data = dcl.synth.make_batch(b, n_inp, n_tmp, first=rank * b)          # disjoint crops per rank
+    data = to_device(host_data, dev)
+    if args.pmc_child:
+        with torch.no_grad():
+            net(data)
+            torch.cuda.synchronize()
+            time.sleep(0.05)                              # the pause measure_kernel_shares cuts the trace at
+            net(data)
+        torch.cuda.synchronize()
+        return
+
+    pred = {}
+    dt, att_ms = run_forward_bench(dcl, net, data, args.steps, args.warmup, distributed, events=args.full, keep=pred)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(pred, args.dump_outputs)
+    del pred
+    graphed = bool(net.__dict__.get("_graphs"))          # calls this small in points replay a whole-forward hipGraph (default)
+    value = world * b * args.steps / dt
+    line = {"metric": "frames/sec DCL_Net.forward @ YCB-V bs32", "value": round(value, 2), "unit": "frames/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32 (exact 3xbf16-split products on the bf16 MFMA, f32 accumulate)",
+            "data": "synthetic",
+            "dtype_note": "fp32 tensors, fp32 accumulators everywhere.  Sparse convs: fp32 MFMA.  The big per-point linear layers (and, "
+                          "where noted under `roofline`, the attention) form each fp32 product from the EXACT three-way bf16 split of "
+                          "both operands -- six bf16 piece products of weight >= 2^-16 on the bf16 MFMA, dropped terms <= 2^-25 of the "
+                          "product -- with errors against float64 equal to an fp32 FMA chain's (tests/test_gpu_ops.py: split core "
+                          "beside the fp32 core; every golden at the reference tolerances 1e-4 / 1e-5)",
+            "config": {"workload": "YCB-V bs=32 (config_YCBV_bs32.yaml), N=%d observed / M=%d model points per crop, "
+                                   "64^3 x 6 mm voxels; shape=%s" % (n_inp, n_tmp, args.shape),
+                       "global_batch": world * b, "frames_per_step_per_gpu": b, "parallelism": "frames sharded x%d" % world,
+                       "weights": "seeded random (no checkpoints offline)",
+                       "calls": "pipelined (async_inputs)" if args.pipelined_calls else "serial",
+                       "path": "whole-forward hipGraph replay" if graphed else "launch by launch"},
+            "whole_forward": whole_forward_rate(n_inp, n_tmp, b, dt / args.steps)}
+    if args.full:
+        line.update(full_report(args, dcl, net, sd, cfg, host_data, data, dev, dt, att_ms, graphed, rank, local_rank, world,
+                                distributed, cpus))
     # the JSON line is the LAST thing on stdout: RCCL writes its banner ("RCCL version ...", "Librccl path ...") through C
     # stdio, which on a pipe is only flushed at exit -- i.e. behind a line printed here.  C stdout was made unbuffered in
     # main(); every rank flushes once more, and rank 0 prints after a barrier behind those flushes.

@@ -525,6 +525,35 @@ def test_tail_side_by_side_equals_serial_tail(dcl):
 
 
 
+def test_plain_bench_line_and_dumped_outputs(dcl, tmp_path):
+    """bench.py without --full: the headline line alone, `steps` timed steps (value x ms_per_step = frames per step), and
+    --dump-outputs writes what the last timed forward returned -- the same poses as a forward of the same seeded crops here"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    b, steps = 4, 3
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+           "--shape", "ref", "--batch", str(b), "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == steps and line["value"] > 0 and line["ms_per_step"] > 0
+    v, ms = line["value"], line["ms_per_step"]                           # rounded to 2 and 3 decimals
+    assert abs(v * ms - 1e3 * b) <= 0.0005 * v + 0.005 * ms + 1e-6
+    assert not {"roofline", "rccl", "ref_shape", "cpu_baseline"} & set(line), "a plain run measures the headline only"
+    got = {k: np.load(str(tmp_path / "out" / (k + ".npy"))) for k in ("rot_pred", "trans_pred", "conf", "F_Xo_p")}
+    assert all(v.dtype == np.float32 for v in got.values())
+    net, _, _ = _net(dcl, 1024, 1024, 1)
+    with torch.no_grad():
+        want = net(dcl.synth.make_batch(b, 1024, 1024))
+    _check({k: torch.from_numpy(got[k]) for k in ("rot_pred", "trans_pred", "conf")},
+           want["rot_pred"].reshape(got["rot_pred"].shape).cpu().numpy(), want["trans_pred"].cpu().numpy(),
+           want["conf"].cpu().numpy())
+
+
 def test_two_gpu_bench_over_rccl_when_the_box_has_two():
     """the first multi-GPU run must be boring.  On a lease with >= 2 GPUs this starts bench.py the way the
     driver does (torch.distributed.run, one rank per GPU, RCCL) for 3 steps and checks what the collective library saw: world 2,
@@ -541,8 +570,8 @@ def test_two_gpu_bench_over_rccl_when_the_box_has_two():
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-extras",
-           "--no-traffic"]
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
+           "--no-extras", "--no-traffic"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]

@@ -97,14 +97,12 @@ def test_yaml_config_loader(dcl, tmp_path):
     assert net.n_inp == 1024 and cfg.model.backbone.kernel_size == 3
 
 
-def test_yaml_loader_on_the_reference_configs(dcl):
-    """the reference's own yaml files (read here in the build container only; skipped where /root/reference is absent):
-    every model block builds a Network / Refiner with the shapes the configs promise"""
+def test_yaml_loader_on_the_reference_configs(dcl, golden_dir):
+    """the reference's own yaml files (configs/*.yaml, stored verbatim under tests/golden/configs/): every model block
+    builds a Network / Refiner with the shapes the configs promise"""
     import glob
-    import pytest
-    files = sorted(glob.glob("/root/reference/configs/*.yaml"))
-    if not files:
-        pytest.skip("reference configs not present on this box")
+    files = sorted(glob.glob(os.path.join(golden_dir, "configs", "*.yaml")))
+    assert [os.path.basename(f) for f in files] == ["config_LM.yaml", "config_YCBV_bs32.yaml", "config_YCBV_bs40.yaml"]
     for f in files:
         cfg = dcl.synth.load_yaml_cfg(f)
         m = cfg.model
@@ -360,6 +358,31 @@ def test_bench_two_rank_dry_run_line(tmp_path, world):
     for i in range(world):
         for j in range(i + 1, world):
             assert not (sets[i] & sets[j]), "ranks must be pinned to disjoint host cores"
+
+
+def test_bench_dump_outputs_writes_float_arrays_and_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs (dump_outputs): one DIR/<name>.npy per returned tensor, float32 (float64 for float64 and
+    integer tensors, exact), small arrays whole and in their shape, a large one as the same seeded sample every time"""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    cap = bench.DUMP_MAX_ELEMS
+    big = torch.arange(3 * cap, dtype=torch.float32).reshape(3, cap).t()          # a transposed view, as F_Xo_p is
+    pred = {"rot_pred": torch.randn(4, 9), "trans_pred": torch.randn(4, 3, dtype=torch.float64),
+            "flag": torch.tensor([7], dtype=torch.int32), "big": big, "meta": "not an array"}
+    for d in ("a", "b"):
+        bench.dump_outputs(pred, str(tmp_path / d))
+    a = {p.name[:-4]: np.load(str(p)) for p in (tmp_path / "a").iterdir()}
+    assert sorted(a) == ["big", "flag", "rot_pred", "trans_pred"]
+    assert a["rot_pred"].dtype == np.float32 and np.array_equal(a["rot_pred"], pred["rot_pred"].numpy())
+    assert a["trans_pred"].dtype == np.float64 and np.array_equal(a["trans_pred"], pred["trans_pred"].numpy())
+    assert a["flag"].dtype == np.float64 and a["flag"].tolist() == [7.0]
+    flat = big.reshape(-1).numpy()
+    assert a["big"].shape == (cap,) and a["big"].dtype == np.float32
+    assert np.isin(a["big"], flat).all() and len(np.unique(a["big"])) == cap
+    assert np.array_equal(a["big"], np.load(str(tmp_path / "b" / "big.npy")))
 
 
 def dcl_cpus(text):

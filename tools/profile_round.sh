@@ -12,8 +12,8 @@ O=gpurun_out
 stats() { rocprofv3 --kernel-trace --stats -d $O/${R}_$1 -o runc --output-format csv -- "${@:2}" > $O/${R}_$1.log 2>&1; }
 pmc()   { rocprofv3 --pmc $2 --kernel-trace -d $O/${R}_$1_$2 -o runc --output-format csv -- "${@:3}" > $O/${R}_$1_$2.log 2>&1; }
 mkdir -p $O
-stats stress python3 bench.py --steps 20 --warmup 3 --no-extras
-stats ref    python3 bench.py --shape ref --steps 40 --warmup 3 --no-extras
+stats stress python3 bench.py --full --steps 20 --warmup 3 --no-extras
+stats ref    python3 bench.py --full --shape ref --steps 40 --warmup 3 --no-extras
 stats prim   python3 tools/bench_primitives.py
 stats stream python3 tools/profile_stream.py 1
 stats crops  python3 tools/bench_crops.py
@@ -28,9 +28,9 @@ python3 tools/bench_linear_dma.py --check 2>&1 | grep -v amdgpu.ids > $O/${R}_ge
 { for a in "ref 32" "stress 32" "ref 6" "ref 1"; do python3 tools/conv_layers.py $a; done; } 2>&1 | grep -v amdgpu.ids > $O/${R}_conv_layers_runner.txt
 { for l in 0 1 2 3 4 5; do python3 tools/conv_stamps.py $l pair ref; done; } 2>&1 | grep -v "amdgpu.ids\|occupancy API" > $O/${R}_conv_stamps.txt
 { python3 tools/stream_b1.py 300 1; python3 tools/stream_b1.py 200 6; python3 tools/graph_timeline.py 1 6 32; } 2>&1 | grep -v amdgpu.ids > $O/${R}_small_calls.txt
-python3 bench.py > $O/${R}_bench_default.log 2>&1; tail -1 $O/${R}_bench_default.log > $O/${R}_bench_default.jsonl
+python3 bench.py --full > $O/${R}_bench_default.log 2>&1; tail -1 $O/${R}_bench_default.log > $O/${R}_bench_default.jsonl
 for c in FETCH_SIZE WRITE_SIZE SQ_VALU_MFMA_BUSY_CYCLES; do
-  pmc pmc $c python3 bench.py --steps 4 --warmup 2 --no-extras
+  pmc pmc $c python3 bench.py --full --steps 4 --warmup 2 --no-extras
 done
 for c in FETCH_SIZE WRITE_SIZE; do
   pmc pmcprim $c python3 tools/bench_primitives.py
