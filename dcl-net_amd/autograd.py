@@ -1,6 +1,7 @@
 """torch.autograd Functions of the ops on DCL-Net's path, mirroring the reference's Function classes
 (libs/spconv/spconv/functional.py:20-166, libs/pointnet_sp/pointnet2_utils.py:41-86,
-libs/pointgroup_ops/functions/pointgroup_ops.py:42-75): forward = the inference kernels, backward = csrc/backward.hip.
+libs/pointnet_lib/pointnet2_utils.py:40-76,144-238, libs/pointgroup_ops/functions/pointgroup_ops.py:42-75):
+forward = the inference kernels, backward = csrc/backward.hip.
 Used by the module mirrors (spconv/, libs/) so that `Network(cfg, mode='train')` is trainable on the GPU."""
 import torch
 from torch.autograd import Function
@@ -54,6 +55,55 @@ class ThreeInterpolateFn(Function):
     def backward(ctx, grad_out):
         idx, weight = ctx.saved_tensors
         return _ops.three_interpolate_grad_sp(grad_out, idx, weight, ctx.m), None, None
+
+
+class GroupPointsFn(Function):
+    """GroupingOperation of libs/pointnet_lib (pointnet2_utils.py:195-235): no gradient for idx."""
+
+    @staticmethod
+    def forward(ctx, features, idx):
+        idx = idx.contiguous().int()
+        ctx.save_for_backward(idx)
+        ctx.n = features.shape[2]
+        return _ops.group_points(features.contiguous(), idx)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (idx,) = ctx.saved_tensors
+        return _ops.group_points_grad(grad_out, idx, ctx.n), None
+
+
+class GatherPointsFn(Function):
+    """GatherOperation of libs/pointnet_lib (pointnet2_utils.py:40-76): no gradient for idx."""
+
+    @staticmethod
+    def forward(ctx, features, idx):
+        idx = idx.contiguous().int()
+        ctx.save_for_backward(idx)
+        ctx.n = features.shape[2]
+        return _ops.gather_points(features.contiguous(), idx)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (idx,) = ctx.saved_tensors
+        return _ops.gather_points_grad(grad_out, idx, ctx.n), None
+
+
+class ThreeInterpolateBatchedFn(Function):
+    """ThreeInterpolate of libs/pointnet_lib (pointnet2_utils.py:144-189): features (B,C,m); no gradient for idx or weight
+    (the reference gives none either)."""
+
+    @staticmethod
+    def forward(ctx, features, idx, weight):
+        idx, weight = idx.contiguous().int(), weight.contiguous()
+        ctx.save_for_backward(idx, weight)
+        ctx.m = features.shape[2]
+        return _ops.three_interpolate(features.contiguous(), idx, weight)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        idx, weight = ctx.saved_tensors
+        return _ops.three_interpolate_grad(grad_out, idx, weight, ctx.m), None, None
 
 
 class VoxelizationFn(Function):

@@ -1,7 +1,14 @@
-"""Mirror of libs/pointnet_lib/pointnet2_utils.py:10-271 (forward passes of the PointNet++ primitives)."""
+"""Mirror of libs/pointnet_lib/pointnet2_utils.py:10-386.  gather_operation, three_interpolate and grouping_operation are
+torch.autograd Functions, like the reference's (dcl.autograd: backward = the deterministic gathers of csrc/backward.hip);
+gradients flow to `features` only.  The index searches (FPS, knn, three_nn, ball_query) are not differentiable."""
 import torch
 
+from ... import autograd as _ag
 from ... import ops as _ops
+
+GatherOperation = _ag.GatherPointsFn
+ThreeInterpolate = _ag.ThreeInterpolateBatchedFn
+GroupingOperation = _ag.GroupPointsFn
 
 
 def furthest_point_sample(xyz, npoint):
@@ -11,7 +18,7 @@ def furthest_point_sample(xyz, npoint):
 
 def gather_operation(features, idx):
     """features (B,C,N), idx (B,npoint) -> (B,C,npoint)."""
-    return _ops.gather_points(features.contiguous(), idx.contiguous())
+    return GatherOperation.apply(features, idx)
 
 
 def knn(k, unknown, known):
@@ -27,12 +34,12 @@ def three_nn(unknown, known):
 
 def three_interpolate(features, idx, weight):
     """features (B,C,M), idx (B,n,3), weight (B,n,3) -> (B,C,n)."""
-    return _ops.three_interpolate(features.contiguous(), idx.contiguous(), weight.contiguous())
+    return ThreeInterpolate.apply(features, idx, weight)
 
 
 def grouping_operation(features, idx):
     """features (B,C,N), idx (B,npoint,nsample) -> (B,C,npoint,nsample)."""
-    return _ops.group_points(features.contiguous(), idx.contiguous().int())
+    return GroupingOperation.apply(features, idx)
 
 
 def ball_query(radius, nsample, xyz, new_xyz):
@@ -40,10 +47,16 @@ def ball_query(radius, nsample, xyz, new_xyz):
     return _ops.ball_query(radius, nsample, xyz.contiguous(), new_xyz.contiguous())
 
 
-# ---- grouping modules (libs/pointnet_lib/pointnet2_utils.py:274-386); forward passes only, like the ops above
+def _needs_grad(*ts):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
+
+
+# ---- grouping modules (libs/pointnet_lib/pointnet2_utils.py:274-386)
 class QueryAndGroup(torch.nn.Module):
     """Ball query around `new_xyz`, then the neighbours' centre-relative coordinates and/or features:
-    (B, 3 + C, npoint, nsample) with use_xyz, features first then xyz -- the reference's channel order (:292-307)."""
+    (B, 3 + C, npoint, nsample) with use_xyz, features first then xyz -- the reference's channel order (:292-307).
+    When features, xyz or new_xyz require grad, the reference's composition (grouping_operation, subtraction, cat) carries
+    the gradients; otherwise both blocks are gathered straight into the result.  The two paths give the same bits."""
 
     def __init__(self, radius, nsample, use_xyz=True):
         super().__init__()
@@ -55,6 +68,12 @@ class QueryAndGroup(torch.nn.Module):
             assert self.use_xyz, "Cannot have not features and not use xyz as a feature!"
         if features is not None and not self.use_xyz:
             return grouping_operation(features, idx)
+        if _needs_grad(xyz, new_xyz, features):
+            grouped_xyz = grouping_operation(xyz.transpose(1, 2).contiguous(), idx)
+            grouped_xyz = grouped_xyz - new_xyz.transpose(1, 2).unsqueeze(-1)
+            if features is None:
+                return grouped_xyz
+            return torch.cat([grouping_operation(features, idx), grouped_xyz], dim=1)
         # both blocks are gathered straight into the result (no torch.cat copy of the (B,C+3,npoint,nsample) tensor)
         B, npoint, ns = idx.shape
         c = 0 if features is None else features.shape[1]

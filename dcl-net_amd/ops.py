@@ -1368,6 +1368,63 @@ def three_interpolate_grad_sp(grad_out, idx, weight, m):
     return gp
 
 
+def _pn_grad_ws(query, sizes, dev, what):
+    nbytes = C.c_int64(0)
+    N.check(query(*sizes, C.byref(nbytes)), what + "_ws_bytes")
+    return torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev), nbytes.value
+
+
+def _pn_grad_points(grad_points, shape, dev):
+    if grad_points is None:
+        return torch.zeros(shape, dtype=torch.float32, device=dev)
+    assert tuple(grad_points.shape) == shape and grad_points.dtype == torch.float32 and grad_points.is_contiguous()
+    return grad_points
+
+
+def group_points_grad(grad_out, idx, n, grad_points=None):
+    """group_points_grad_wrapper of libs/pointnet_lib: grad_out (B,C,npoint,nsample), idx (B,npoint,nsample) i32 ->
+    grad_points (B,C,n).  Adds into `grad_points` when one is given (zeros otherwise); deterministic (include/dclnet_hip.h)."""
+    N.need_cuda(grad_out, idx, grad_points)
+    grad_out, idx = N.f32c(grad_out), N.i32c(idx)
+    B, c, npoint, ns = grad_out.shape
+    assert tuple(idx.shape) == (B, npoint, ns)
+    gp = _pn_grad_points(grad_points, (B, c, int(n)), grad_out.device)
+    ws, nb = _pn_grad_ws(N.lib().dcl_group_points_grad_ws_bytes, (B, c, int(n), npoint, ns), grad_out.device,
+                         "group_points_grad")
+    N.check(N.lib().dcl_group_points_grad(B, c, int(n), npoint, ns, N.ptr(grad_out), N.ptr(idx), N.ptr(gp), N.ptr(ws),
+                                          C.c_int64(nb), N.stream()), "group_points_grad")
+    return gp
+
+
+def gather_points_grad(grad_out, idx, n, grad_points=None):
+    """gather_points_grad_wrapper: grad_out (B,C,npoint), idx (B,npoint) i32 -> grad_points (B,C,n) (adds into it)."""
+    N.need_cuda(grad_out, idx, grad_points)
+    grad_out, idx = N.f32c(grad_out), N.i32c(idx)
+    B, c, npoint = grad_out.shape
+    assert tuple(idx.shape) == (B, npoint)
+    gp = _pn_grad_points(grad_points, (B, c, int(n)), grad_out.device)
+    ws, nb = _pn_grad_ws(N.lib().dcl_gather_points_grad_ws_bytes, (B, c, int(n), npoint), grad_out.device,
+                         "gather_points_grad")
+    N.check(N.lib().dcl_gather_points_grad(B, c, int(n), npoint, N.ptr(grad_out), N.ptr(idx), N.ptr(gp), N.ptr(ws),
+                                           C.c_int64(nb), N.stream()), "gather_points_grad")
+    return gp
+
+
+def three_interpolate_grad(grad_out, idx, weight, m, grad_points=None):
+    """three_interpolate_grad_wrapper of libs/pointnet_lib: grad_out (B,C,n), idx (B,n,3) i32, weight (B,n,3) ->
+    grad_points (B,C,m) (adds into it).  No weight gradient, as in the reference."""
+    N.need_cuda(grad_out, idx, weight, grad_points)
+    grad_out, idx, weight = N.f32c(grad_out), N.i32c(idx), N.f32c(weight)
+    B, c, n = grad_out.shape
+    assert tuple(idx.shape) == (B, n, 3) and tuple(weight.shape) == (B, n, 3)
+    gp = _pn_grad_points(grad_points, (B, c, int(m)), grad_out.device)
+    ws, nb = _pn_grad_ws(N.lib().dcl_three_interpolate_grad_ws_bytes, (B, c, n, int(m)), grad_out.device,
+                         "three_interpolate_grad")
+    N.check(N.lib().dcl_three_interpolate_grad(B, c, n, int(m), N.ptr(grad_out), N.ptr(idx), N.ptr(weight), N.ptr(gp),
+                                               N.ptr(ws), C.c_int64(nb), N.stream()), "three_interpolate_grad")
+    return gp
+
+
 def voxelize_bp(d_out, map_rule, n_points, mode=4):
     """PG_OP.voxelize_bp (pointgroup_ops.py:65-73) -> d_feats (N, C)."""
     N.need_cuda(d_out, map_rule)

@@ -336,7 +336,8 @@ int dcl_voxel_centres(const int32_t *indices, const int32_t *n_dev, int n_host, 
                       float *centres, dclStream_t stream);
 
 /* ---------------------------------------------------------- pointnet_lib ---
- * libs/pointnet_lib/src/pointnet2_api.cpp:10-25.  Same argument order.         */
+ * libs/pointnet_lib/src/pointnet2_api.cpp:10-25, all ten wrappers (the three
+ * *_grad ones below the forward ops).  Same argument order.                    */
 int dcl_ball_query(int b, int n, int m, float radius, int nsample, const float *new_xyz,
                    const float *xyz, int32_t *idx, dclStream_t stream);       /* idx fully written */
 int dcl_group_points(int b, int c, int n, int npoints, int nsample, const float *points,
@@ -356,6 +357,29 @@ int dcl_three_nn(int b, int n, int m, const float *unknown, const float *known, 
                  int32_t *idx, dclStream_t stream);
 int dcl_three_interpolate(int b, int c, int m, int n, const float *points, const int32_t *idx,
                           const float *weight, float *out, dclStream_t stream);
+
+/* The three gradient wrappers of the same file (pointnet2_api.cpp:14,17,24), the reference's arguments in its order, then
+ * a workspace: ws (16-byte aligned) of at least the *_ws_bytes of the same sizes.  Like the reference they ADD INTO
+ * grad_points, which the caller has zero-filled:
+ *   group_points_grad   grad_out (B,C,npoints,nsample), idx (B,npoints,nsample) -> grad_points (B,C,n)
+ *   gather_points_grad  grad_out (B,C,npoints),         idx (B,npoints)         -> grad_points (B,C,n)
+ *   three_interpolate_grad  grad_out (B,C,n), idx / weight (B,n,3)              -> grad_points (B,C,m)
+ * Deterministic (csrc/backward.hip: an inverse index of idx per call, then a gather): every element of grad_points gets
+ * the contributions that name it added one at a time, in ascending flat position order (p*nsample + s, p, i*3 + k;
+ * interpolation: the product grad_out*weight rounded to fp32 before the add) -- numpy.add.at on float32, bit for bit.
+ * Indices outside [0, n) (resp. [0, m)) contribute nothing and are never used as addresses.  Bad sizes (negative, more
+ * than 2^31 - 8192 positions per batch entry, b > 65535) and a short workspace return DCL_EINVAL before any GPU work;
+ * the size queries need no GPU.                                                                                         */
+int dcl_group_points_grad_ws_bytes(int b, int c, int n, int npoints, int nsample, int64_t *bytes_host);
+int dcl_group_points_grad(int b, int c, int n, int npoints, int nsample, const float *grad_out, const int32_t *idx,
+                          float *grad_points, void *ws, int64_t ws_bytes, dclStream_t stream);
+int dcl_gather_points_grad_ws_bytes(int b, int c, int n, int npoints, int64_t *bytes_host);
+int dcl_gather_points_grad(int b, int c, int n, int npoints, const float *grad_out, const int32_t *idx,
+                           float *grad_points, void *ws, int64_t ws_bytes, dclStream_t stream);
+int dcl_three_interpolate_grad_ws_bytes(int b, int c, int n, int m, int64_t *bytes_host);
+int dcl_three_interpolate_grad(int b, int c, int n, int m, const float *grad_out, const int32_t *idx,
+                               const float *weight, float *grad_points, void *ws, int64_t ws_bytes,
+                               dclStream_t stream);
 
 /* ------------------------------------------------------------ dense path ---
  * All dense operands are POINT-major: X[(b*n + p)*ld + c] (row = point, ld = row stride in
