@@ -1,7 +1,8 @@
 """torch.autograd Functions of the ops on DCL-Net's path, mirroring the reference's Function classes
 (libs/spconv/spconv/functional.py:20-166, libs/pointnet_sp/pointnet2_utils.py:41-86,
 libs/pointnet_lib/pointnet2_utils.py:40-76,144-238, libs/pointgroup_ops/functions/pointgroup_ops.py:42-75):
-forward = the inference kernels, backward = csrc/backward.hip.
+forward = the inference kernels, backward = csrc/backward.hip; and of the correspondence attention (CrossAttentionFn:
+forward = dcl_cross_attention, backward = csrc/attention_bwd.hip), which the reference forms from bmm and softmax.
 Used by the module mirrors (spconv/, libs/) so that `Network(cfg, mode='train')` is trainable on the GPU."""
 import torch
 from torch.autograd import Function
@@ -119,3 +120,37 @@ class VoxelizationFn(Function):
     def backward(ctx, d_out):
         (map_rule,) = ctx.saved_tensors
         return _ops.voxelize_bp(d_out, map_rule, ctx.n, ctx.mode), None, None
+
+
+class CrossAttentionFn(Function):
+    """One direction of the correspondence attention, Aligner.forward + the two following bmm (models/Modules.py:128-138,
+    models/DCL_Net.py:961-964), without the attention map in either pass: Q (b, nq, 64), K (b, nk, 64), V1 (b, nk, 256),
+    V2 (b, nk, 64) -> O1 (b, nq, 256), O2 (b, nq, 64) with O = softmax_keys(Q K^T) V.  Forward = ops.cross_attention (the
+    same bits as the op itself), backward = ops.cross_attention_backward (deterministic).  K and V2 may be one tensor: its
+    gradient is then dK + dV2."""
+
+    @staticmethod
+    def forward(ctx, Q, K, V1, V2):
+        b, nq, nk = Q.shape[0], Q.shape[1], K.shape[1]
+        Q2, K2 = _ops.N.f32c(Q).view(b * nq, -1), _ops.N.f32c(K).view(b * nk, -1)
+        V12 = _ops.N.f32c(V1).view(b * nk, -1)
+        V22 = K2 if V2 is K else _ops.N.f32c(V2).view(b * nk, -1)
+        O1 = torch.empty((b, nq, V12.shape[1]), dtype=torch.float32, device=Q.device)
+        O2 = torch.empty((b, nq, V22.shape[1]), dtype=torch.float32, device=Q.device)
+        _ops.cross_attention(b, Q2, K2, V12, O1.view(b * nq, -1), V22, O2.view(b * nq, -1))
+        ctx.save_for_backward(Q2, K2, V12, V22, O1, O2)
+        ctx.set_materialize_grads(False)                  # an unused output arrives as None, not as a tensor of zeros
+        ctx.b = b
+        ctx.shapes = (Q.shape, K.shape, V1.shape, V2.shape)
+        return O1, O2
+
+    @staticmethod
+    def backward(ctx, dO1, dO2):
+        Q2, K2, V12, V22, O1, O2 = ctx.saved_tensors
+        if (dO1 is None and dO2 is None) or not any(ctx.needs_input_grad):
+            return None, None, None, None
+        O1, O2 = O1.view(-1, O1.shape[2]), O2.view(-1, O2.shape[2])
+        g1 = torch.zeros_like(O1) if dO1 is None else _ops.N.f32c(dO1).view(O1.shape)
+        g2 = None if dO2 is None else _ops.N.f32c(dO2).view(O2.shape)
+        grads = _ops.cross_attention_backward(ctx.b, Q2, K2, V12, V22, O1, O2, g1, g2)
+        return tuple(g.view(s) if n else None for g, s, n in zip(grads, ctx.shapes, ctx.needs_input_grad))

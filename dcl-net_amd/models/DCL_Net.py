@@ -25,6 +25,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..autograd import CrossAttentionFn
 from .. import spconv
 from ..libs.pointgroup_ops.functions import pointgroup_ops
 from .losses import losses  # noqa: F401  (reference: models/DCL_Net.py::losses)
@@ -70,7 +71,8 @@ def _fuser():
 
 class Network(nn.Module):
     def __init__(self, cfg, mode="train", fused=True, graph_max_batch=8, async_inputs=False, graph_max_points=98304,
-                 single_stream=False, pipeline_chunks=1, capture_graph=True, pair_features=None):
+                 single_stream=False, pipeline_chunks=1, capture_graph=True, pair_features=None,
+                 train_attention="materialised"):
         """graph_max_batch > 0 (default 8): eval-mode calls with at most that many crops go through forward_graphed (one
         whole-forward hipGraph per batch size, captured on first use) -- the one-image-at-a-time eval loops of the
         reference (tools/test_LM.py:104-112: one object per call) are launch-bound otherwise: 0.53 instead of 1.1 ms
@@ -85,15 +87,23 @@ class Network(nn.Module):
         back-to-back calls pipeline: backbones of batch k+1 underneath the GEMMs / attention of batch k.
         single_stream=True: the whole call on the caller's stream (no side streams; what bench.py's per-kernel conv timing
         uses).  pipeline_chunks=K > 1: the sparse half in K passes over b/K crops (measured slower, kept runnable).
-        capture_graph=False: forward_graphed runs its capacity-mode body launch by launch (debugging aid).  These are
+        capture_graph=False: forward_graphed runs its capacity-mode body launch by launch (debugging aid).
         pair_features: True = the feature stage of both backbones as ONE launch sequence (every layer one launch over both
         sides' tiles, ops.backbone_features_pair: 8 conv + 4 pool launches per forward instead of 16 + 8), False = each side's
         own launches on its own stream, None (default) = automatic: paired when everything runs on one stream anyway
         (single_stream: measured 1.63 -> 1.53 ms of conv time per bs-32 forward), separate otherwise -- with two side streams
         the sides' stages overlap each other and the first dense GEMMs, which a common feature stage would serialise (measured
         at N = M = 1024: bs 32 4.28 vs 4.40 ms per step, one crop 0.61 vs 0.65 ms).
+        train_attention: how the differentiable module path (train() calls and fused=False instances; the fused eval pipeline
+        has no use for it) forms the correspondence attention.  "materialised" (default) = the mirrored Aligner, softmax(bmm)
+        as a (b, M, N) map that autograd keeps for the backward pass, followed by two more bmm with it; "fused" = one
+        autograd.CrossAttentionFn per direction (forward dcl_cross_attention, backward csrc/attention_bwd.hip), which stores
+        nothing of the map's size in either pass.
         These are constructor arguments on purpose: nothing on the call path reads the environment."""
         super().__init__()
+        if train_attention not in ("materialised", "fused"):
+            raise ValueError('train_attention must be "materialised" or "fused", got %r' % (train_attention,))
+        self.train_attention = train_attention
         self.single_stream = bool(single_stream)
         self._pair_features = pair_features              # both backbones' layers as ONE launch each; None = automatic (see property)
         self.pipeline_chunks = int(pipeline_chunks)
@@ -958,10 +968,19 @@ class Network(nn.Module):
             return getattr(self, name)(x).squeeze(-1).squeeze(-1)
         Xc = {t: dis("disengage_Xc_" + t, F_Xc) for t in ("p1", "m1", "p2", "m2")}
         Yo = {t: dis("disengage_Yo_" + t, F_Yo) for t in ("p1", "m1", "p2", "m2")}
-        F_Xo_p, A1 = self.neck_cross_att(Xc["m1"], Yo["m1"], Yo["p1"])
-        F_Yc_p, A2 = self.neck_cross_att(Yo["m2"], Xc["m2"], Xc["p2"])
-        conf_1 = self.regressor_conf(torch.cat([Xc["m1"], torch.bmm(Yo["m1"], A1)], dim=1))
-        conf_2 = self.regressor_conf_bi(torch.cat([torch.bmm(Xc["m2"], A2), Yo["m2"]], dim=1))
+        if self.train_attention == "fused":
+            def att(q, k, v):                     # (b, C, n) activations -> point-major copies; the keys are the second values
+                kt = k.transpose(1, 2).contiguous()
+                o1, o2 = CrossAttentionFn.apply(q.transpose(1, 2).contiguous(), kt, v.transpose(1, 2).contiguous(), kt)
+                return o1.transpose(1, 2).contiguous(), o2.transpose(1, 2).contiguous()
+            F_Xo_p, F_Xo_m = att(Xc["m1"], Yo["m1"], Yo["p1"])
+            F_Yc_p, F_Yc_m = att(Yo["m2"], Xc["m2"], Xc["p2"])
+        else:
+            F_Xo_p, A1 = self.neck_cross_att(Xc["m1"], Yo["m1"], Yo["p1"])
+            F_Yc_p, A2 = self.neck_cross_att(Yo["m2"], Xc["m2"], Xc["p2"])
+            F_Xo_m, F_Yc_m = torch.bmm(Yo["m1"], A1), torch.bmm(Xc["m2"], A2)
+        conf_1 = self.regressor_conf(torch.cat([Xc["m1"], F_Xo_m], dim=1))
+        conf_2 = self.regressor_conf_bi(torch.cat([F_Yc_m, Yo["m2"]], dim=1))
         conf = torch.sigmoid(torch.cat([conf_1, conf_2], dim=2))
         conf_softmax = torch.softmax(conf, dim=2)
         F_p = torch.cat([self.neck_fuser(torch.cat([Xc["p1"], F_Xo_p], dim=1)),

@@ -757,6 +757,38 @@ def cross_attention(b, Q, K, V1, O1, V2=None, O2=None, concurrent=1, planes=None
     return O1, O2
 
 
+def cross_attention_backward(b, Q, K, V1, V2, O1, O2, dO1, dO2=None):
+    """Gradients of one cross_attention call without the attention map (csrc/attention_bwd.hip; include/dclnet_hip.h at
+    dcl_cross_attention_bwd): the 2-D point-major operands cross_attention took and returned plus dO1 (b*nq, 256), dO2 (b*nq, 64)
+    or None (= zeros) -> (dQ, dK, dV1, dV2), new contiguous tensors.  Row strides are honoured.  dK and dV2 are separate
+    even where K and V2 are one tensor (the caller adds them).  Deterministic: the same inputs give the same bits."""
+    N.need_cuda(Q, K, V1, V2, O1, O2, dO1, dO2)
+    nq, nk = Q.shape[0] // b, K.shape[0] // b
+    assert Q.shape == (b * nq, 64) and K.shape == (b * nk, 64)
+    assert V1.shape[0] == b * nk and V2.shape[0] == b * nk and O1.shape == (b * nq, V1.shape[1]) and O2.shape == (b * nq, V2.shape[1])
+    assert dO1.shape == O1.shape and (dO2 is None or dO2.shape == O2.shape)
+    assert all(t is None or t.dtype == torch.float32 for t in (Q, K, V1, V2, O1, O2, dO1, dO2))
+    dev = Q.device
+    dQ, dK = torch.empty((b * nq, 64), dtype=torch.float32, device=dev), torch.empty((b * nk, 64), dtype=torch.float32, device=dev)
+    dV1, dV2 = torch.empty(V1.shape, dtype=torch.float32, device=dev), torch.empty(V2.shape, dtype=torch.float32, device=dev)
+    return cross_attention_backward_into(b, Q, K, V1, V2, O1, O2, dO1, dO2, dQ, dK, dV1, dV2)
+
+
+def cross_attention_backward_into(b, Q, K, V1, V2, O1, O2, dO1, dO2, dQ, dK, dV1, dV2):
+    """cross_attention_backward writing into the caller's dQ, dK, dV1, dV2 (which may be column blocks of wider buffers)."""
+    N.need_cuda(Q, K, V1, V2, O1, O2, dO1, dO2, dQ, dK, dV1, dV2)
+    nq, nk = Q.shape[0] // b, K.shape[0] // b
+    nbytes = C.c_int64(0)
+    N.check(N.lib().dcl_cross_attention_bwd_ws_bytes(int(b), nq, nk, C.byref(nbytes)), "cross_attention_bwd_ws_bytes")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=Q.device)
+    N.check(N.lib().dcl_cross_attention_bwd(int(b), nq, nk, N.ptr(Q), _ld(Q), N.ptr(K), _ld(K), N.ptr(V1), V1.shape[1], _ld(V1),
+                                            N.ptr(V2), V2.shape[1], _ld(V2), N.ptr(O1), _ld(O1), N.ptr(O2), _ld(O2),
+                                            N.ptr(dO1), _ld(dO1), N.ptr(dO2), 0 if dO2 is None else _ld(dO2),
+                                            N.ptr(dQ), _ld(dQ), N.ptr(dK), _ld(dK), N.ptr(dV1), _ld(dV1), N.ptr(dV2), _ld(dV2),
+                                            N.ptr(ws), C.c_int64(nbytes.value), N.stream()), "cross_attention_bwd")
+    return dQ, dK, dV1, dV2
+
+
 def conf_pool(b, logit1, logit2, F1, F2, affine=None, finish=True):
     """Confidence pooling: logits (b*n1,)/(b*n2,), F1 (b*n1,C), F2 (b*n2,C) point-major ->
     conf (b,n1+n2), pooled1 (b,C), pooled2 (b,C), wsum (b,2).

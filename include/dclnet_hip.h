@@ -425,6 +425,27 @@ int dcl_cross_attention_ws3(int b, int nq, int nk, const float *Q, int ldq, cons
                             int ldv2, float *O2, int ldo2, float *scratch, int64_t scratch_floats,
                             int concurrent_launches, void *planes, int64_t planes_bytes, dclStream_t stream);
 int dcl_cross_attention_scratch_floats(int b, int nq, int64_t *floats_host);
+/* Gradients of that contraction without the attention map (csrc/attention_bwd.hip), one direction per call.  With
+ * V = [V1|V2], O = [O1|O2], dO = [dO1|dO2] (320 ch) and, per query row i, delta_i = <dO[i,:], O[i,:]>:
+ *   dP[j,i] = <dO[i,:], V[j,:]>,  dS[j,i] = A[j,i] (dP[j,i] - delta_i),
+ *   dV[j,:] = sum_i A[j,i] dO[i,:],  dK[j,:] = sum_i dS[j,i] Q[i,:],  dQ[i,:] = sum_j dS[j,i] K[j,:].
+ * Q, K, V1, V2 as dcl_cross_attention took them, O1, O2 as it returned them; dO2 = NULL is a zero gradient for O2.  A is
+ * recomputed tile by tile from the per-query log-sum-exp of the scores (exact-fp32 MFMA products, like the fp32 forward):
+ * nothing of size nq*nk is stored.  ws: dcl_cross_attention_bwd_ws_bytes(b, nq, nk) bytes (two floats per query, so it does not
+ * depend on nk), 16-byte aligned.  dQ (b*nq rows, 64 ch), dK (b*nk, 64), dV1 (b*nk, 256), dV2 (b*nk, 64) are OVERWRITTEN;
+ * dK and dV2 are separate outputs even where the caller passed one tensor as K and V2 (it adds them).  Three launches, each
+ * owning the rows it writes: no float atomics, no workgroup waits on another, bit-identical results call after call.
+ * b, nq, nk >= 1 (any counts: ragged last tiles are masked); dv1 = 256 and dv2 = 64 only; all ld % 4 == 0, 16-B aligned.  Bad
+ * sizes, unsupported dv1 / dv2 and a NULL, misaligned or short workspace return DCL_EINVAL before any GPU work; the size
+ * query needs no GPU.                                                                                                    */
+int dcl_cross_attention_bwd_ws_bytes(int b, int nq, int nk, int64_t *bytes_host);
+int dcl_cross_attention_bwd(int b, int nq, int nk,
+        const float *Q, int ldq, const float *K, int ldk,
+        const float *V1, int dv1, int ldv1, const float *V2, int dv2, int ldv2,
+        const float *O1, int ldo1, const float *O2, int ldo2,
+        const float *dO1, int lddo1, const float *dO2, int lddo2,
+        float *dQ, int lddq, float *dK, int lddk, float *dV1, int lddv1, float *dV2, int lddv2,
+        void *ws, int64_t ws_bytes, dclStream_t stream);
 
 /* Confidence pooling (models/DCL_Net.py:217-228): conf = sigmoid(cat[logit1 (b,n1), logit2
  * (b,n2)]) -> conf (b,n1+n2); w = softmax(conf) -> w_scratch (b,n1+n2);
