@@ -2,7 +2,8 @@
 (libs/spconv/spconv/functional.py:20-166, libs/pointnet_sp/pointnet2_utils.py:41-86,
 libs/pointnet_lib/pointnet2_utils.py:40-76,144-238, libs/pointgroup_ops/functions/pointgroup_ops.py:42-75):
 forward = the inference kernels, backward = csrc/backward.hip; and of the correspondence attention (CrossAttentionFn:
-forward = dcl_cross_attention, backward = csrc/attention_bwd.hip), which the reference forms from bmm and softmax.
+forward = dcl_cross_attention, backward = csrc/attention_bwd.hip), which the reference forms from bmm and softmax;
+and of the losses' Chamfer distance (ChamferFn: csrc/chamfer.hip in both passes).
 Used by the module mirrors (spconv/, libs/) so that `Network(cfg, mode='train')` is trainable on the GPU."""
 import torch
 from torch.autograd import Function
@@ -154,3 +155,30 @@ class CrossAttentionFn(Function):
         g2 = None if dO2 is None else _ops.N.f32c(dO2).view(O2.shape)
         grads = _ops.cross_attention_backward(ctx.b, Q2, K2, V12, V22, O1, O2, g1, g2)
         return tuple(g.view(s) if n else None for g, s, n in zip(grads, ctx.shapes, ctx.needs_input_grad))
+
+
+class ChamferFn(Function):
+    """Nearest-neighbour distances between two clouds in both directions, the two halves of the reference's CD_Dis
+    (models/DCL_Net.py:306-312), without the pairwise matrix in either pass: pred (b,n,3), target (b,m,3), active (b,) i32 or
+    None -> dist_pt (b,n), dist_tp (b,m).  Forward = ops.chamfer, backward = ops.chamfer_backward (deterministic).  Only the
+    two clouds and the two index tensors are kept for the backward, and only the gradients that are asked for are computed."""
+
+    @staticmethod
+    def forward(ctx, pred, target, active=None):
+        pred, target = _ops.N.f32c(pred), _ops.N.f32c(target)
+        dist_pt, idx_pt, dist_tp, idx_tp = _ops.chamfer(pred, target, active)
+        ctx.save_for_backward(pred, target, idx_pt, idx_tp)
+        # the (b,) flag vector rides on ctx, not in save_for_backward: it is an int32 input that can never take a gradient and
+        # no output of this Function, so the saved set stays the two clouds and the two index tensors
+        ctx.active = active
+        return dist_pt, dist_tp
+
+    @staticmethod
+    def backward(ctx, g_pt, g_tp):
+        pred, target, idx_pt, idx_tp = ctx.saved_tensors
+        need_pred, need_target = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_pred or need_target):
+            return None, None, None
+        grad_pred, grad_target = _ops.chamfer_backward(pred, target, idx_pt, idx_tp, _ops.N.f32c(g_pt), _ops.N.f32c(g_tp),
+                                                       ctx.active, need_pred, need_target)
+        return grad_pred, grad_target, None

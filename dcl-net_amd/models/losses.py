@@ -2,11 +2,13 @@
 models/refiner.py:98-139) as plain torch modules over the GPU outputs of `Network` / `Refiner`.
 
 Point-set terms: `L2_Dis` = per-point Euclidean distance between corresponding points, `CD_Dis` = symmetric
-nearest-neighbour (Chamfer) distance for symmetric objects, from coordinate differences in row chunks."""
+nearest-neighbour (Chamfer) distance for symmetric objects, from coordinate differences in row chunks (`cd_dis`, the
+default) or, with chamfer="fused", from the library's own kernels without the pairwise matrix (`cd_dis_fused`)."""
 import torch
 import torch.nn as nn
 
 from .. import ops
+from ..autograd import ChamferFn
 
 
 def l2_dis(pred, target):
@@ -27,6 +29,20 @@ def cd_dis(pred, target, chunk=256):
     return 0.5 * (torch.cat(near_t, dim=1) + near_p)
 
 
+def cd_dis_fused(pred, target, active=None):
+    """cd_dis on csrc/chamfer.hip (autograd.ChamferFn): no (b,N,M) intermediate in the forward or kept for the backward,
+    which is deterministic.  active (b,) bool / int or None: crops whose flag is 0 are not computed; their rows are 0 and
+    take no gradient.  CUDA tensors only."""
+    assert pred.shape[1] == target.shape[1], "cd_dis adds the two directions point by point: n == m"
+    if not (pred.is_cuda and target.is_cuda):
+        raise RuntimeError("cd_dis_fused (chamfer='fused') runs on the GPU only: got %s / %s tensors; the chunked cd_dis "
+                           "serves CPU tensors" % (pred.device, target.device))
+    if active is not None:
+        active = active.to(device=pred.device, dtype=torch.int32).contiguous()
+    dist_pt, dist_tp = ChamferFn.apply(pred, target, active)
+    return 0.5 * (dist_pt + dist_tp)
+
+
 def get_cano_label(points_tmp, points_inp, rot_pred, trans_gt):
     """Observed points mapped to the canonical frame and snapped to their nearest template point (kNN, k = 1)."""
     cano = torch.bmm(points_inp - trans_gt, rot_pred)
@@ -37,34 +53,49 @@ def get_cano_label(points_tmp, points_inp, rot_pred, trans_gt):
 class _PoseLoss(nn.Module):
     L2_Dis = staticmethod(l2_dis)
     CD_Dis = staticmethod(cd_dis)
+    cd_dis_fused = staticmethod(cd_dis_fused)
     get_cano_label = staticmethod(get_cano_label)
 
+    def __init__(self, chamfer="chunked"):
+        super().__init__()
+        if chamfer not in ("chunked", "fused"):
+            raise ValueError("chamfer must be 'chunked' or 'fused', got %r" % (chamfer,))
+        self.chamfer = chamfer
+
+    def _cd(self, sym):
+        """the Chamfer term for this batch: the chunked function, or the fused one restricted to the crops whose term the
+        loss does not multiply by 0"""
+        if self.chamfer == "chunked":
+            return cd_dis
+        active = (sym != 0).int()                  # the int32 flags the kernels read, made once per forward
+        return lambda pred, target: cd_dis_fused(pred, target, active)
+
     @staticmethod
-    def _pose_term(posed, posed_gt, sym):
+    def _pose_term(posed, posed_gt, sym, cd):
         sym = sym.unsqueeze(1)
-        return ((1 - sym) * l2_dis(posed, posed_gt) + sym * cd_dis(posed, posed_gt)).mean(dim=1).mean()
+        return ((1 - sym) * l2_dis(posed, posed_gt) + sym * cd(posed, posed_gt)).mean(dim=1).mean()
 
 
 class losses(_PoseLoss):
     """loss_all = loss_pose + 5 loss_Xo + loss_Yc + loss_conf (models/DCL_Net.py:264-304)."""
 
-    def __init__(self, cfg=None):
-        super().__init__()
+    def __init__(self, cfg=None, chamfer="chunked"):
+        super().__init__(chamfer)
 
     def forward(self, pred, gt):
         R, t, sym, conf = pred["rot_pred"], pred["trans_pred"], pred["sym_flag"], pred["conf"]
         dev = R.device
         R_gt, t_gt = gt["rot_gt"].to(dev), gt["trans_gt"].to(dev)
         tmp, inp = gt["points_tmp"], gt["points_inp"]
-        s1 = sym.unsqueeze(1)
+        s1, cd = sym.unsqueeze(1), self._cd(sym)
         posed = torch.bmm(tmp, R.transpose(1, 2)) + t.unsqueeze(1)
         posed_gt = torch.bmm(tmp, R_gt.transpose(1, 2)) + t_gt.unsqueeze(1)
-        loss_pose = self._pose_term(posed, posed_gt, sym)
+        loss_pose = self._pose_term(posed, posed_gt, sym, cd)
         Xo, Yc = pred["Xo_pred"], pred["Yc_pred"]
         inp_cano_pred = torch.bmm(inp - t.unsqueeze(1), R).detach()
         inp_cano_gt = torch.bmm(inp - t_gt.unsqueeze(1), R_gt).detach()
-        loss_Xo = (1 - s1) * l2_dis(Xo, inp_cano_gt) + 0.5 * s1 * (cd_dis(Xo, tmp) + l2_dis(Xo, inp_cano_pred))
-        loss_Yc = (1 - s1) * l2_dis(Yc, posed_gt) + 0.5 * s1 * (cd_dis(Yc, posed_gt) + l2_dis(Yc, posed.detach()))
+        loss_Xo = (1 - s1) * l2_dis(Xo, inp_cano_gt) + 0.5 * s1 * (cd(Xo, tmp) + l2_dis(Xo, inp_cano_pred))
+        loss_Yc = (1 - s1) * l2_dis(Yc, posed_gt) + 0.5 * s1 * (cd(Yc, posed_gt) + l2_dis(Yc, posed.detach()))
         loss_conf = torch.mean(torch.cat([loss_Xo, loss_Yc], dim=1).detach() * conf - 0.01 * torch.log(conf))
         out = {"loss_pose": loss_pose, "loss_Xo": loss_Xo.mean(), "loss_Yc": loss_Yc.mean(), "loss_conf": loss_conf}
         out["loss_all"] = out["loss_pose"] + 5 * out["loss_Xo"] + 1 * out["loss_Yc"] + 1 * out["loss_conf"]
@@ -74,8 +105,8 @@ class losses(_PoseLoss):
 class losses_refiner(_PoseLoss):
     """Pose loss of the template posed by the refiner's delta and then by the current pose (models/refiner.py:101-125)."""
 
-    def __init__(self, cfg=None):
-        super().__init__()
+    def __init__(self, cfg=None, chamfer="chunked"):
+        super().__init__(chamfer)
 
     def forward(self, pred_refiner, trans_cur, rot_cur, points_tmp, sym_flag, gt):
         dR, dt = pred_refiner["rot_pred"], pred_refiner["trans_pred"]
@@ -84,5 +115,5 @@ class losses_refiner(_PoseLoss):
         posed_delta = torch.bmm(points_tmp, dR.transpose(1, 2)) + dt.unsqueeze(1)
         posed_gt = torch.bmm(points_tmp, R_gt.transpose(1, 2)) + t_gt.unsqueeze(1)
         refined = torch.bmm(posed_delta, rot_cur.transpose(1, 2)) + trans_cur.unsqueeze(1)
-        loss_pose = self._pose_term(refined, posed_gt, sym_flag)
+        loss_pose = self._pose_term(refined, posed_gt, sym_flag, self._cd(sym_flag))
         return {"loss_pose": loss_pose, "loss_all": loss_pose}

@@ -683,6 +683,46 @@ def three_nn(unknown, known):
     return dist2, idx
 
 
+def _chamfer_args(pred, target, active):
+    N.need_cuda(pred, target, active)
+    assert pred.dim() == 3 and target.dim() == 3 and pred.shape[2] == 3 and target.shape[2] == 3
+    assert pred.shape[0] == target.shape[0] and pred.dtype == torch.float32 and target.dtype == torch.float32
+    assert pred.is_contiguous() and target.is_contiguous()
+    assert active is None or (active.dtype == torch.int32 and active.shape == (pred.shape[0],) and active.is_contiguous())
+    return pred.shape[0], pred.shape[1], target.shape[1]
+
+
+def chamfer(pred, target, active=None):
+    """Nearest-neighbour distances in both directions without the pairwise matrix (csrc/chamfer.hip; include/dclnet_hip.h at
+    dcl_chamfer_fwd): pred (b,n,3), target (b,m,3) fp32 contiguous -> (dist_pt (b,n), idx_pt (b,n) i32, dist_tp (b,m),
+    idx_tp (b,m) i32).  active (b,) i32 or None: crops whose flag is 0 are not computed (distance 0, index -1)."""
+    b, n, m = _chamfer_args(pred, target, active)
+    dev = pred.device
+    dist_pt, idx_pt = torch.empty((b, n), dtype=torch.float32, device=dev), torch.empty((b, n), dtype=torch.int32, device=dev)
+    dist_tp, idx_tp = torch.empty((b, m), dtype=torch.float32, device=dev), torch.empty((b, m), dtype=torch.int32, device=dev)
+    N.check(N.lib().dcl_chamfer_fwd(b, n, m, N.ptr(pred), N.ptr(target), N.ptr(active), N.ptr(dist_pt), N.ptr(idx_pt),
+                                    N.ptr(dist_tp), N.ptr(idx_tp), N.stream()), "chamfer_fwd")
+    return dist_pt, idx_pt, dist_tp, idx_tp
+
+
+def chamfer_backward(pred, target, idx_pt, idx_tp, g_pt, g_tp, active=None, need_pred=True, need_target=True):
+    """Gradients of one chamfer call (dcl_chamfer_bwd): idx_pt, idx_tp as chamfer returned them, g_pt (b,n), g_tp (b,m) the
+    upstream gradients of the two distance outputs -> (grad_pred (b,n,3), grad_target (b,m,3)); a gradient that is not
+    needed is None and is not computed.  Deterministic: the same inputs give the same bits."""
+    b, n, m = _chamfer_args(pred, target, active)
+    N.need_cuda(idx_pt, idx_tp, g_pt, g_tp)
+    assert need_pred or need_target
+    assert idx_pt.shape == (b, n) and idx_tp.shape == (b, m) and idx_pt.dtype == torch.int32 and idx_tp.dtype == torch.int32
+    assert g_pt.shape == (b, n) and g_tp.shape == (b, m) and g_pt.dtype == torch.float32 and g_tp.dtype == torch.float32
+    assert idx_pt.is_contiguous() and idx_tp.is_contiguous() and g_pt.is_contiguous() and g_tp.is_contiguous()
+    grad_pred = torch.empty((b, n, 3), dtype=torch.float32, device=pred.device) if need_pred else None
+    grad_target = torch.empty((b, m, 3), dtype=torch.float32, device=pred.device) if need_target else None
+    N.check(N.lib().dcl_chamfer_bwd(b, n, m, N.ptr(pred), N.ptr(target), N.ptr(active), N.ptr(idx_pt), N.ptr(idx_tp),
+                                    N.ptr(g_pt), N.ptr(g_tp), N.ptr(grad_pred), N.ptr(grad_target), N.stream()),
+            "chamfer_bwd")
+    return grad_pred, grad_target
+
+
 def three_interpolate(features, idx, weight):
     N.need_cuda(features, idx, weight)
     assert features.is_contiguous() and idx.is_contiguous() and weight.is_contiguous()

@@ -634,6 +634,31 @@ int dcl_add_by_symmetry(int b, int P, const float *cld, const int32_t *cls, cons
                         const float *R_pred, const float *t_pred, const float *R_gt, const float *t_gt,
                         float *partial_scratch, float *out, dclStream_t stream);
 
+/* ------------------------------------------------------ training objective ---
+ * Both-direction nearest-neighbour (Chamfer) distances of the point-set losses (models/DCL_Net.py:306-312 `CD_Dis`) without
+ * the pairwise matrix (csrc/chamfer.hip).  pred (b,n,3), target (b,m,3) fp32 contiguous, any n, m >= 1.  One launch writes
+ *   dist_pt (b,n) = min_j |pred_i - target_j|, idx_pt (b,n) i32 = that j;  dist_tp (b,m), idx_tp (b,m): the other way round.
+ * Squared distance = fma(dz,dz, fma(dy,dy, dx*dx)) of fp32 differences (dcl_add_s's form); the minimum is taken on squared
+ * distances by an ascending scan with strict '<' (the lowest index wins a tie, as in dcl_three_nn / dcl_knn); sqrt is
+ * applied once, to the minimum.  active i32[b] (NULL: every crop): a crop whose flag is 0 does no distance work, its
+ * distances are written as 0 and its indices as -1.  No workspace.                                                       */
+int dcl_chamfer_fwd(int b, int n, int m, const float *pred, const float *target, const int32_t *active,
+                    float *dist_pt, int32_t *idx_pt, float *dist_tp, int32_t *idx_tp, dclStream_t stream);
+/* Gradients of that call with respect to both clouds.  idx_pt, idx_tp as dcl_chamfer_fwd returned them, g_pt (b,n) and
+ * g_tp (b,m) the upstream gradients of dist_pt and dist_tp.  With u(p,t) = (p - t)/|p - t|, 0 where |p - t| = 0 (torch's
+ * subgradient of norm at 0):
+ *   grad_pred[i]   =  g_pt[i] u(p_i, t_idx_pt[i]) + sum_{j ascending, idx_tp[j] = i} g_tp[j] u(p_i, t_j)
+ *   grad_target[j] = -g_tp[j] u(p_idx_tp[j], t_j) - sum_{i ascending, idx_pt[i] = j} g_pt[i] u(p_i, t_j)
+ * (each term evaluated as (g / |p - t|) (p - t)).  grad_pred (b,n,3) and grad_target (b,m,3) are OVERWRITTEN; either may be
+ * NULL and is then skipped (not both).  Crops whose flag is 0 get zero gradients; an index outside its cloud contributes
+ * nothing.  One launch, one lane per output point, which adds its own term and then the incoming ones in ascending index
+ * order: no float atomics, no workspace, no workgroup waits on another, bit-identical results call after call.
+ * Both calls: n < 1, m < 1, b < 0, a NULL required pointer with b > 0 (or both gradient outputs NULL) return DCL_EINVAL
+ * before any GPU call; b == 0 returns 0.                                                                                 */
+int dcl_chamfer_bwd(int b, int n, int m, const float *pred, const float *target, const int32_t *active,
+                    const int32_t *idx_pt, const int32_t *idx_tp, const float *g_pt, const float *g_tp,
+                    float *grad_pred, float *grad_target, dclStream_t stream);
+
 /* The loaders' point-sampling draws, bit for bit (host code, no GPU call): for each of k objects out[o*n .. o*n+n) =
  * np.random.permutation(m[o])[:n] = what np.random.choice(m[o], n, replace=False) returns (YCBV/dataloader_test_YCBV.py:166-169,
  * LM/dataloader_test_LM.py:176-181) -- numpy's legacy Fisher-Yates walk (mtrand.pyx: _shuffle_raw, random_interval: MT19937
