@@ -1155,28 +1155,43 @@ __global__ void k_ortho9d(int b, const float *__restrict__ o9, float *__restrict
 DCL_HOOK_INT(g_attn_variant, 0);     // 1 = shared-tile 8-wave kernel, 2 = 4-wave register-staged, 3 / 4 = LDS-DMA pipeline with 8 / 4 waves
 DCL_HOOK_INT(g_attn_split, 0);       // 0 = automatic key split of small attention launches, n = force n
 DCL_HOOK_INT(g_attn_xcd_remap, 1);   // 0 = plain blockIdx order (for traffic comparisons)
+DCL_HOOK_INT(g_attn_whatif, 0);      // what-if runs of k_cross_attn_split -- 1: no P.V phase, 2: no S phase, 4: no DMA after the first tile
+DCL_HOOK_INT(g_attn_bf16, 1);        // 0 = fp32 MFMA everywhere
+DCL_HOOK_INT(g_attn_pair_split, 1);  // 0 = a pair call is never cut into whole rounds + rest
 #ifdef DCL_DIAG
 DCL_API void dcl_debug_attention_split(int n) { g_attn_split = n; }
 DCL_API void dcl_debug_attention_xcd_remap(int on) { g_attn_xcd_remap = on; }
 DCL_API void dcl_debug_attention_variant(int v) { g_attn_variant = v; }
+DCL_API void dcl_debug_attention_pair_split(int on) { g_attn_pair_split = on; }
+DCL_API void dcl_debug_attention_bf16(int on) { g_attn_bf16 = on; }
+DCL_API void dcl_debug_attention_whatif(int bits) { g_attn_whatif = bits; }
 #endif
 
-DCL_API int dcl_cross_attention(int b, int nq, int nk, const float *Q, int ldq, const float *K, int ldk,
-                                const float *V1, int dv1, int ldv1, float *O1, int ldo1, const float *V2, int dv2,
-                                int ldv2, float *O2, int ldo2, dclStream_t stream) {
-  return dcl_cross_attention_ws(b, nq, nk, Q, ldq, K, ldk, V1, dv1, ldv1, O1, ldo1, V2, dv2, ldv2, O2, ldo2, nullptr, 0,
-                                stream);
-}
+// ---- the launch plan: what a call of a given size runs.  The size queries below are views of it and dcl_cross_attention_ws3
+//      issues it, so the three cannot disagree; g_attn_variant / _split / _bf16 / _pair_split are read here and nowhere else ----
+enum AttnKernel {
+  kAttnSplit,                        // k_cross_attn_split behind the two piece passes (k_attn_split_v, k_attn_split_k)
+  kAttnDma8, kAttnDma4,              // k_cross_attn_dma<8>, k_cross_attn_dma<4>
+  kAttnShared8, kAttnStaged4,        // diagnostic library: k_cross_attn_shared<8, N>, k_cross_attn<N>
+  kAttnNone                          // a channel split the product library has no kernel for
+};
+struct AttnPart { int crops; AttnKernel kernel; int nsplit; };   // nsplit > 1: partial records in `scratch` + k_cross_attn_combine
+struct AttnPlan { int nparts; AttnPart part[2]; };               // 2 parts: a pair call cut into whole rounds (0) + the rest (1)
+struct AttnOffer {                   // what the caller hands in besides the operands (planes: non-null / 16-byte aligned / size)
+  bool planes, planes_aligned; int64_t planes_bytes; bool scratch; int64_t scratch_floats;
+};
+
+// The split kernel is worth its 8-wave workgroups on fewer than 256 of them too when the key axis is long: the key split fills the
+// chip, and the fp32 4-wave kernel it would fall back to is 1.5x slower per flop -- 24 crops of 2048 queries x 12288 keys: 192
+// workgroups, whole forward 15.55 -> 14.0 ms.  The bound: four times the work of a lone 32 x 1024 x 1024 launch, where the two
+// kernels tie.
+static bool attn_split_big(long long blocks8, int nk) { return blocks8 >= 64 && blocks8 * dcl_div_up(nk, 32) >= 16384; }
 
 // crops of a PAIR of launches (the two directions side by side) that fill whole rounds of 8-wave workgroups: 256 workgroups per
 // round for the pair = 128 / ceil(nq / 256) crops of each direction (32 at nq = 1024); 0 = no such split for this call
-DCL_HOOK_INT(g_attn_whatif, 0);      // (diagnostic library: what-if runs of k_cross_attn_split -- 1: no P.V phase, 2: no S phase, 4: no DMA after the first tile)
-DCL_HOOK_INT(g_attn_bf16, 1);        // (diagnostic library: dcl_debug_attention_bf16; 0 = fp32 MFMA everywhere)
-static bool attn_split_big(long long blocks8, int nk) { return blocks8 >= 64 && blocks8 * dcl_div_up(nk, 32) >= 16384; }
-DCL_HOOK_INT(g_attn_pair_split, 1);  // (diagnostic library: dcl_debug_attention_pair_split; 0 = off)
 // (nk > 0: the call has scratch for the split-bf16 kernel -- a call that kernel takes as a whole is not cut into rounds + rest: the
 //  rest would run on the fp32 4-wave kernel, 2.7 ms for 8 of 24 stress-shape crops)
-static int attn_pair_full_crops(int b, int nq, int dv1, int dv2, int concurrent_launches, int nk = 0) {
+static int attn_pair_full_crops(int b, int nq, int dv1, int dv2, int concurrent_launches, int nk) {
   if (!g_attn_pair_split || g_attn_variant != 0 || concurrent_launches != 2 || dv1 != 256 || dv2 != 64 || nq <= 0) return 0;
   const int qb8 = dcl_div_up(nq, 256);
   if (nk > 0 && g_attn_bf16 && attn_split_big((long long)b * qb8, nk)) return 0;
@@ -1185,14 +1200,31 @@ static int attn_pair_full_crops(int b, int nq, int dv1, int dv2, int concurrent_
   const int full = b / per_round * per_round;
   return full > 0 && full < b ? full : 0;
 }
-#ifdef DCL_DIAG
-DCL_API void dcl_debug_attention_pair_split(int on) { g_attn_pair_split = on; }
-#endif
 
-// Key split of a 4-wave attention launch (fewer than 256 eight-wave workgroups): see the launcher below for the model.
-static int attn_small_split(int b, int nq, int ntiles) {
-  const int forced = g_attn_split;
-  if (forced > 0) return forced > 16 ? 16 : forced;
+// Key split the model picks for an 8-wave launch.  Wave quantisation: blocks8 workgroups run in ceil(blocks8/256) rounds of one
+// per CU.  When the last round is mostly empty (e.g. 320 workgroups = 2 rounds for 1.25 rounds of work) a key split of Z makes
+// the rounds Z times shorter: cost(Z) = ceil(blocks8*Z/256)/Z full-workgroup times; taken when it saves >= 0.2 of one and the
+// partial records (`per` floats per split) stay below ~512 MiB
+static int attn_auto_split8(long long blocks8, long long per) {
+  int nsplit = 1;
+  double best = (double)dcl_div_up(blocks8, 256);
+  for (int z = 2; z <= 8; z *= 2) {
+    const double cost = (double)dcl_div_up(blocks8 * z, 256) / z;
+    if (cost <= best - 0.2 && z * per <= (128ll << 20)) { best = cost; nsplit = z; }
+  }
+  return nsplit;
+}
+
+// Key split the model picks for a 4-wave launch (few workgroups, one per CU): a power of two z (the 32 key tiles of a 1024-key
+// crop divide evenly; 3 or 6 splits measured 2-4 % slower than 2 or 4) by a small time model in microseconds,
+//     rounds(z) * (tiles * 1.1 / z + 4)  +  (z > 1 ? 4 + 0.15 * z * b * nq / 1024 : 0),
+// rounds(z) = ceil(T z / 256) with T = 2 x blocks -- the two directions of a call run side by side (parallel branches of the
+// whole-forward graph, the path every call this small takes); the second term is the combine launch.  Fitted to same-job A/B
+// runs on the whole forward (tools/ab_hook.py dcl_debug_attention_split), best z at 1 / 2 / 4 / 6 / 8 / 12 / 16 / 20 / 32 crops of
+// 1024 x 1024: 16 / 8 / 4 / 2 / 2 / 1 / 1 / 2 / 1 -- what this picks (one crop: 16 splits of two tiles against 8 of four, whole
+// forward 0.414 vs 0.419 ms; two crops 0.547 vs 0.527: not there); against the former rule (fill 256 workgroups per launch)
+// 4 crops -3 %, 6: -1.8 %, 8: -1.3 %, 12: -5.4 %, 16: -1.6 %, 20: -2.5 %.
+static int attn_auto_split4(int b, int nq, int ntiles) {
   const long long T = 2ll * b * dcl_div_up(nq, 128);
   const double tiles_us = 1.1 * ntiles;
   double best = 1e30;
@@ -1201,83 +1233,214 @@ static int attn_small_split(int b, int nq, int ntiles) {
     const double cost = (double)dcl_div_up(T * z, 256) * (tiles_us / z + 4.0) + (z > 1 ? 4.0 + 0.15 * z * (double)b * nq / 1024.0 : 0.0);
     if (cost < best - 1e-9) { best = cost; nsplit = z; }
   }
+  return nsplit;
+}
+
+// Key split of a launch before the scratch limit: the forced one (dcl_debug_attention_split) or the model's, at most 8 ways in
+// the 8-wave form and 16 in the 4-wave form, and at least two key tiles per split
+static int attn_key_split(bool w8, int b, int nq, int ntiles) {
+  const int forced = g_attn_split, most = w8 ? 8 : 16;
+  int nsplit = forced > 0 ? forced
+               : w8       ? attn_auto_split8((long long)b * dcl_div_up(nq, 256), (long long)b * nq * kAttnPartPitch)
+                          : attn_auto_split4(b, nq, ntiles);
+  if (nsplit > most) nsplit = most;
   if (nsplit > ntiles / 2) nsplit = ntiles / 2;
   return nsplit < 1 ? 1 : nsplit;
 }
 
-DCL_API int dcl_cross_attention_scratch_floats(int b, int nq, int64_t *floats_host) {
-  // upper bound of what dcl_cross_attention_ws can use for (b, nq): small launches by their split model (up to 16 ways),
-  // large ones only while the records stay below 128 Mi floats
-  DCL_CHECK_ARG(b >= 0 && nq >= 0 && floats_host);
-  const long long per = (long long)b * nq * kAttnPartPitch;
-  const long long blocks8 = (long long)b * dcl_div_up(nq > 0 ? nq : 1, 256);
-  long long z = 1;
-  if (blocks8 < 256) {                                     // (the key count is not known here: the most any count would take)
-    for (int ntiles = 2; ntiles <= (1 << 16); ntiles *= 2) z = max(z, (long long)attn_small_split(b, nq, ntiles));
-  } else {
-    z = 1;
-    double best = (double)dcl_div_up(blocks8, 256);
-    for (int c = 2; c <= 8; c *= 2) {
-      const double cost = (double)dcl_div_up(blocks8 * c, 256) / c;
-      if (cost <= best - 0.2 && c * per <= (128ll << 20)) { best = cost; z = c; }
+// one launch of b crops (a whole call, or one part of a pair call)
+static AttnPart attn_plan_part(int b, int nq, int nk, int dv1, int dv2, int concurrent_launches, const AttnOffer &offer) {
+  const int variant = g_attn_variant;
+  const long long blocks8 = (long long)b * dcl_div_up(nq, 256);
+  AttnPart p = {b, kAttnNone, 1};
+  if (dv1 == 256 && dv2 == 64 && (variant == 0 || variant == 3 || variant == 4)) {
+    // LDS-DMA pipeline.  Large grids: 8-wave workgroups (256 queries) sharing a K/V tile, 2 waves/SIMD.  Small grids (fewer
+    // than one 8-wave workgroup per CU): 4-wave workgroups (128 queries) with double-buffered tiles, one per CU.
+    // Two launches side by side (the two directions of a forward on parallel branches) whose 8-wave workgroups TOGETHER make
+    // one round of the chip -- 32 crops of 1024 x 1024, the shipped configuration -- also take the 8-wave form, unsplit: the
+    // 4-wave workgroups (402 registers, one wave per SIMD) of the two launches cannot share a CU, so they run one after the
+    // other at one wave per SIMD; same-job A/B of the whole forward, 8-wave vs 4-wave: 32 crops 3.813 vs 3.880 ms; 28 (224
+    // workgroups) 3.706 vs 3.696, 36: 4.72 vs 4.69, 40: 4.97 vs 4.97, 24: 3.20 vs 3.15, 16: 2.31 vs 2.16 -- hence the window.
+    const int ntiles = dcl_div_up(nk, 32);
+    const bool pair8 = concurrent_launches == 2 && 2 * blocks8 > 240 && 2 * blocks8 <= 256;
+    // P.V (and S) on the bf16 matrix pipe at fp32-sized errors needs room for the K / V pieces of every tile; planes that are
+    // misaligned or too small leave the call on the fp32 kernel its size gets anyway
+    const bool planes_usable = offer.planes && offer.planes_aligned && g_attn_bf16 &&
+                               offer.planes_bytes >= (int64_t)b * ntiles * kAttnTileBytes;
+    const bool w8 = variant == 3 || (variant == 0 && (blocks8 >= 256 || pair8 || (planes_usable && attn_split_big(blocks8, nk))));
+    p.kernel = !w8 ? kAttnDma4 : planes_usable ? kAttnSplit : kAttnDma8;
+    if (offer.scratch && !(w8 && pair8 && g_attn_split == 0)) {
+      p.nsplit = attn_key_split(w8, b, nq, ntiles);
+      while (p.nsplit > 1 && (long long)p.nsplit * b * nq * kAttnPartPitch > offer.scratch_floats) --p.nsplit;
     }
   }
-  long long need = z > 1 ? z * per : 0;
-  // a pair call that is split into whole rounds + a rest (dcl_cross_attention_ws2): the rest is a call of its own size
-  const int full = attn_pair_full_crops(b, nq, 256, 64, 2);
-  if (full) {
-    int64_t rest = 0;
-    const int rc = dcl_cross_attention_scratch_floats(b - full, nq, &rest);
-    if (rc) return rc;
-    if (rest > need) need = rest;
-  }
-  *floats_host = need;
-  return 0;
-}
-
-DCL_API int dcl_cross_attention_ws(int b, int nq, int nk, const float *Q, int ldq, const float *K, int ldk,
-                                   const float *V1, int dv1, int ldv1, float *O1, int ldo1, const float *V2, int dv2,
-                                   int ldv2, float *O2, int ldo2, float *scratch, int64_t scratch_floats,
-                                   dclStream_t stream) {
-  return dcl_cross_attention_ws2(b, nq, nk, Q, ldq, K, ldk, V1, dv1, ldv1, O1, ldo1, V2, dv2, ldv2, O2, ldo2, scratch,
-                                 scratch_floats, 1, stream);
-}
-
-static int attn_dispatch(int b, int nq, int nk, const float *Q, int ldq, const float *K, int ldk, const float *V1, int dv1, int ldv1,
-                         float *O1, int ldo1, const float *V2, int dv2, int ldv2, float *O2, int ldo2, float *scratch,
-                         int64_t scratch_floats, int concurrent_launches, void *planes, int64_t planes_bytes, dclStream_t stream);
-
-// does a call of this size take the 8-wave workgroup form (see attn_dispatch), the one the split-bf16 kernel exists for?
-// (the split kernel is worth its 8-wave workgroups on fewer than 256 of them too when the key axis is long: the key split fills the
-//  chip, and the fp32 4-wave kernel it would fall back to is 1.5x slower per flop -- 24 crops of 2048 queries x 12288 keys: 192
-//  workgroups, whole forward 15.55 -> 14.0 ms.  The bound: four times the work of a lone 32 x 1024 x 1024 launch, where the two
-//  kernels tie.)
-static bool attn_takes_w8(int b, int nq, int nk, int concurrent_launches) {
-  const long long blocks8 = (long long)b * dcl_div_up(nq, 256);
-  const bool pair8 = concurrent_launches == 2 && 2 * blocks8 > 240 && 2 * blocks8 <= 256;
-  return g_attn_variant == 3 || (g_attn_variant == 0 && (blocks8 >= 256 || pair8 || attn_split_big(blocks8, nk)));
-}
-#ifdef DCL_DIAG
-DCL_API void dcl_debug_attention_bf16(int on) { g_attn_bf16 = on; }
-DCL_API void dcl_debug_attention_whatif(int bits) { g_attn_whatif = bits; }
+#ifdef DCL_DIAG   // the general-shape kernels, no key split
+  else p.kernel = ((blocks8 >= 256 && variant != 2) || variant == 1) ? kAttnShared8 : kAttnStaged4;
 #endif
+  return p;
+}
+
+// A pair of launches whose 8-wave workgroups make one or more WHOLE rounds of the chip plus a rest (40 crops of 1024 x 1024: 1.25
+// rounds): the whole rounds go as they are (8-wave, two waves per SIMD), the rest as the call of that many crops that it is, with
+// no planes (4-wave workgroups, keys split; or the pair window again) -- a quarter-filled last round costs a whole one.  Same
+// results per crop.
+static AttnPlan attn_plan(int b, int nq, int nk, int dv1, int dv2, int concurrent_launches, const AttnOffer &offer) {
+  const int full = attn_pair_full_crops(b, nq, dv1, dv2, concurrent_launches, offer.planes ? nk : 0);
+  AttnPlan plan = {};
+  plan.nparts = full ? 2 : 1;
+  plan.part[0] = attn_plan_part(full ? full : b, nq, nk, dv1, dv2, concurrent_launches, offer);
+  const AttnOffer rest = {false, false, 0, offer.scratch, offer.scratch_floats};
+  if (full) plan.part[1] = attn_plan_part(b - full, nq, nk, dv1, dv2, concurrent_launches, rest);
+  return plan;
+}
 
 DCL_API int dcl_cross_attention_split_crops(int b, int nq, int nk, int concurrent_launches) {
   // how many of the b crops take the split-bf16 kernel when `planes` are handed in: 0, all of them, or the whole rounds of a pair call
-  if (b <= 0 || nq <= 0 || nk <= 0 || !g_attn_bf16) return 0;
-  int crops = b;
-  const int full = attn_pair_full_crops(b, nq, 256, 64, concurrent_launches, nk);
-  if (full) crops = full;
-  return attn_takes_w8(crops, nq, nk, concurrent_launches) ? crops : 0;
+  // (the rest of such a call gets no planes)
+  if (b <= 0 || nq <= 0 || nk <= 0) return 0;
+  const AttnOffer ample_planes = {true, true, INT64_MAX, false, 0};
+  const AttnPart p = attn_plan(b, nq, nk, 256, 64, concurrent_launches, ample_planes).part[0];
+  return p.kernel == kAttnSplit ? p.crops : 0;
 }
 
 DCL_API int64_t dcl_cross_attention_planes_bytes(int b, int nq, int nk, int concurrent_launches) {
-  if (b <= 0 || nq <= 0 || nk <= 0 || !g_attn_bf16) return 0;
-  int crops = b;
-  const int full = attn_pair_full_crops(b, nq, 256, 64, concurrent_launches, nk);
-  if (full) crops = full;                                  // (the rest of such a call runs as a small call: 4-wave workgroups)
-  if (!attn_takes_w8(crops, nq, nk, concurrent_launches)) return 0;
-  return (int64_t)crops * dcl_div_up(nk, 32) * kAttnTileBytes;
+  return (int64_t)dcl_cross_attention_split_crops(b, nq, nk, concurrent_launches) * dcl_div_up(nk, 32) * kAttnTileBytes;
+}
+
+// upper bound of what dcl_cross_attention_ws can use for (b, nq): small launches by their split model (up to 16 ways), large ones
+// only while the records stay below 128 Mi floats
+static long long attn_scratch_bound(int b, int nq) {
+  const long long per = (long long)b * nq * kAttnPartPitch;
+  const long long blocks8 = (long long)b * dcl_div_up(nq > 0 ? nq : 1, 256);
+  long long z = 1;
+  if (blocks8 >= 256) z = attn_auto_split8(blocks8, per);
+  else                                                     // (the key count is not known here: the most any count would take)
+    for (int ntiles = 2; ntiles <= (1 << 16); ntiles *= 2) z = max(z, (long long)attn_key_split(false, b, nq, ntiles));
+  const long long need = z > 1 ? z * per : 0;
+  // a pair call that is cut into whole rounds + a rest: the rest is a call of its own size
+  const int full = attn_pair_full_crops(b, nq, 256, 64, 2, 0);
+  return full ? max(need, attn_scratch_bound(b - full, nq)) : need;
+}
+
+DCL_API int dcl_cross_attention_scratch_floats(int b, int nq, int64_t *floats_host) {
+  DCL_CHECK_ARG(b >= 0 && nq >= 0 && floats_host);
+  *floats_host = attn_scratch_bound(b, nq);
+  return 0;
+}
+
+// issues one part of the plan: argument checks, piece passes, the attention kernel, the combine of a key split
+static int attn_launch(const AttnPart &part, int nq, int nk, const float *Q, int ldq, const float *K, int ldk, const float *V1, int dv1,
+                       int ldv1, float *O1, int ldo1, const float *V2, int dv2, int ldv2, float *O2, int ldo2, float *scratch,
+                       void *planes, dclStream_t stream) {
+  const int b = part.crops, nsplit = part.nsplit;
+  DCL_CHECK_ARG(b >= 0 && nq >= 0 && nk > 0 && dv1 > 0 && dv1 % 32 == 0 && dv2 >= 0 && dv2 % 32 == 0);
+  if (b == 0 || nq == 0) return 0;
+  DCL_CHECK_ARG(Q && K && (V1 || planes) && O1 && (dv2 == 0 || (V2 && O2)) && b <= 65535);
+  DCL_CHECK_ARG(ldq >= 64 && ldk >= 64 && ldv1 >= dv1 && ldo1 >= dv1 && (dv2 == 0 || (ldv2 >= dv2 && ldo2 >= dv2)));
+  DCL_CHECK_ARG(ldq % 4 == 0 && ldk % 4 == 0 && ldv1 % 4 == 0 && ldo1 % 4 == 0 && ldv2 % 4 == 0 && ldo2 % 4 == 0);
+  DCL_CHECK_ARG((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V1 | (uintptr_t)O1 | (uintptr_t)V2 | (uintptr_t)O2) & 15) == 0);
+  const int nvt = (dv1 + dv2) / 32;
+  DCL_CHECK_ARG(nvt == 1 || nvt == 2 || nvt == 4 || nvt == 8 || nvt == 10);
+  if (part.kernel == kAttnNone) {
+    // the product library carries the one kernel the DCL-Net path uses (V = [256 | 64] channels, models/DCL_Net.py:206-215);
+    // its general-shape predecessors live in the diagnostic library only
+    dcl_set_error("dcl_cross_attention: only dv1 = 256, dv2 = 64 is built into the product library (got %d, %d)", dv1, dv2);
+    return DCL_EINVAL;
+  }
+  if (!V1 && part.kernel != kAttnSplit) {                  // (only the split kernel reads V1's pieces from `planes`)
+    dcl_set_error("dcl_cross_attention: V1 = NULL (pieces in `planes`) but this call does not take the split-bf16 kernel");
+    return DCL_EINVAL;
+  }
+  hipStream_t s = (hipStream_t)stream;
+#define ATT_DMA(W)                                                                                             \
+  do {                                                                                                         \
+    const size_t lds = (size_t)(32 * kKPitch + 2 * 32 * 256 + 2 * 32 * 64 + W * 32 * kKPitch) * sizeof(float);  \
+    (void)hipFuncSetAttribute((const void *)k_cross_attn_dma<W>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
+                              (int)lds);                                                                       \
+    hipLaunchKernelGGL(k_cross_attn_dma<W>, dim3(dcl_div_up(nq, 32 * W), b, nsplit), dim3(64 * W), lds, s, nq, nk, \
+                       Q, ldq, K, ldk, V1, ldv1, O1, ldo1, V2, ldv2, O2, ldo2, scratch, (int)g_attn_xcd_remap); \
+  } while (0)
+  switch (part.kernel) {
+    case kAttnSplit: {
+      // V as three exact bf16 pieces in tile order (one pass), K likewise, then the sweep
+      const int nht = 2 * dcl_div_up(nk, 32);
+      const int c_begin = V1 ? 0 : 256;                    // V1 == NULL: its pieces are in `planes` already
+      const long long total = (long long)b * nht * (320 - c_begin) * 2;
+      hipLaunchKernelGGL(k_attn_split_v, dim3(dcl_grid_1d(total, 256)), dim3(256), 0, s, nk, nht, V1, ldv1, V2, ldv2,
+                         (unsigned *)planes, total, c_begin);
+      unsigned char *kplanes = (unsigned char *)planes + (size_t)b * nht * kAttnHalfBytes;
+      const long long ktotal = (long long)b * (nht / 2) * 32 * 8;
+      hipLaunchKernelGGL(k_attn_split_k, dim3(dcl_grid_1d(ktotal, 256)), dim3(256), 0, s, nk, nht / 2, K, ldk, (unsigned *)kplanes, ktotal);
+      const size_t lds_sp = (size_t)2 * (2 * kAttnHalfBytes + kAttnKTileBytes);
+      (void)hipFuncSetAttribute((const void *)k_cross_attn_split, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sp);
+      hipLaunchKernelGGL(k_cross_attn_split, dim3(dcl_div_up(nq, 256), b, nsplit), dim3(512), lds_sp, s, nq, nk, Q, ldq,
+                         (const unsigned char *)planes, (const unsigned char *)kplanes, O1, ldo1, O2, ldo2, scratch,
+                         (int)g_attn_xcd_remap, (int)g_attn_whatif);
+    } break;
+    case kAttnDma8: ATT_DMA(8); break;
+    case kAttnDma4: ATT_DMA(4); break;
+#ifdef DCL_DIAG
+    case kAttnShared8: {
+      const size_t lds = (size_t)(32 * kKPitch + 32 * nvt * 32 + 8 * 32 * kKPitch) * sizeof(float);
+#define ATT8(N)                                                                                                \
+  do {                                                                                                         \
+    (void)hipFuncSetAttribute((const void *)k_cross_attn_shared<8, N>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                              (int)lds);                                                                       \
+    hipLaunchKernelGGL((k_cross_attn_shared<8, N>), dim3(dcl_div_up(nq, 256), b), dim3(512), lds, s, nq, nk, Q, \
+                       ldq, K, ldk, V1, dv1, ldv1, O1, ldo1, V2, dv2, ldv2, O2, ldo2);                         \
+  } while (0)
+      switch (nvt) {
+        case 1: ATT8(1); break;
+        case 2: ATT8(2); break;
+        case 4: ATT8(4); break;
+        case 8: ATT8(8); break;
+        default: ATT8(10); break;
+      }
+#undef ATT8
+    } break;
+    case kAttnStaged4: {
+      const size_t lds = (size_t)2 * (32 * kKPitch + 32 * nvt * 32) * sizeof(float);
+#define ATT(N)                                                                                                 \
+  do {                                                                                                         \
+    (void)hipFuncSetAttribute((const void *)k_cross_attn<N>, hipFuncAttributeMaxDynamicSharedMemorySize,       \
+                              (int)lds);                                                                       \
+    hipLaunchKernelGGL((k_cross_attn<N>), dim3(dcl_div_up(nq, 128), b), dim3(256), lds, s, nq, nk, Q, ldq, K,   \
+                       ldk, V1, dv1, ldv1, O1, ldo1, V2, dv2, ldv2, O2, ldo2);                                 \
+  } while (0)
+      switch (nvt) {
+        case 1: ATT(1); break;
+        case 2: ATT(2); break;
+        case 4: ATT(4); break;
+        case 8: ATT(8); break;
+        default: ATT(10); break;
+      }
+#undef ATT
+    } break;
+#endif
+    default: break;
+  }
+#undef ATT_DMA
+  if (nsplit > 1)
+    hipLaunchKernelGGL(k_cross_attn_combine, dim3(dcl_grid_1d((long long)b * nq * 80, 256)), dim3(256), 0, s, b * nq,
+                       nsplit, scratch, O1, ldo1, O2, ldo2);
+  DCL_LAUNCH_CHECK();
+  return 0;
+}
+
+DCL_API int dcl_cross_attention_ws3(int b, int nq, int nk, const float *Q, int ldq, const float *K, int ldk,
+                                    const float *V1, int dv1, int ldv1, float *O1, int ldo1, const float *V2, int dv2,
+                                    int ldv2, float *O2, int ldo2, float *scratch, int64_t scratch_floats,
+                                    int concurrent_launches, void *planes, int64_t planes_bytes, dclStream_t stream) {
+  DCL_CHECK_ARG(concurrent_launches == 1 || concurrent_launches == 2);
+  const AttnOffer offer = {planes != nullptr, ((uintptr_t)planes & 15) == 0, planes_bytes, scratch != nullptr, scratch_floats};
+  const AttnPlan plan = attn_plan(b, nq, nk, dv1, dv2, concurrent_launches, offer);
+  const int full = plan.nparts == 2 ? plan.part[0].crops : 0;
+  DCL_CHECK_ARG(!(full && !V1));                           // (V1 = NULL is for calls that take the split kernel as a whole: dcl_cross_attention_split_crops)
+  const int rc = attn_launch(plan.part[0], nq, nk, Q, ldq, K, ldk, V1, dv1, ldv1, O1, ldo1, V2, dv2, ldv2, O2, ldo2, scratch, planes, stream);
+  if (rc || !full) return rc;
+  const size_t qo = (size_t)full * nq, ko = (size_t)full * nk;
+  return attn_launch(plan.part[1], nq, nk, Q + qo * ldq, ldq, K + ko * ldk, ldk, V1 + ko * ldv1, dv1, ldv1, O1 + qo * ldo1, ldo1,
+                     V2 ? V2 + ko * ldv2 : nullptr, dv2, ldv2, O2 ? O2 + qo * ldo2 : nullptr, ldo2, scratch, nullptr, stream);
 }
 
 DCL_API int dcl_cross_attention_ws2(int b, int nq, int nk, const float *Q, int ldq, const float *K, int ldk,
@@ -1288,187 +1451,19 @@ DCL_API int dcl_cross_attention_ws2(int b, int nq, int nk, const float *Q, int l
                                  concurrent_launches, nullptr, 0, stream);
 }
 
-DCL_API int dcl_cross_attention_ws3(int b, int nq, int nk, const float *Q, int ldq, const float *K, int ldk,
-                                    const float *V1, int dv1, int ldv1, float *O1, int ldo1, const float *V2, int dv2,
-                                    int ldv2, float *O2, int ldo2, float *scratch, int64_t scratch_floats,
-                                    int concurrent_launches, void *planes, int64_t planes_bytes, dclStream_t stream) {
-  DCL_CHECK_ARG(concurrent_launches == 1 || concurrent_launches == 2);
-  // A pair of launches whose 8-wave workgroups make one or more WHOLE rounds of the chip plus a rest (40 crops of 1024 x 1024: 1.25
-  // rounds): the whole rounds go as they are (8-wave, two waves per SIMD), the rest as the call of that many crops that it is
-  // (4-wave workgroups, keys split) -- a quarter-filled last round costs a whole one.  Same results per crop.
-  const int full = (b > 0 && Q && K && O1) ? attn_pair_full_crops(b, nq, dv1, dv2, concurrent_launches, planes ? nk : 0) : 0;
-  DCL_CHECK_ARG(!(full && !V1));                           // (V1 = NULL is for calls that take the split kernel as a whole: dcl_cross_attention_split_crops)
-  if (full) {
-    int rc = attn_dispatch(full, nq, nk, Q, ldq, K, ldk, V1, dv1, ldv1, O1, ldo1, V2, dv2, ldv2, O2, ldo2, scratch, scratch_floats,
-                           concurrent_launches, planes, planes_bytes, stream);
-    if (rc) return rc;
-    const size_t qo = (size_t)full * nq, ko = (size_t)full * nk;
-    return attn_dispatch(b - full, nq, nk, Q + qo * ldq, ldq, K + ko * ldk, ldk, V1 + ko * ldv1, dv1, ldv1, O1 + qo * ldo1, ldo1,
-                         V2 ? V2 + ko * ldv2 : nullptr, dv2, ldv2, O2 ? O2 + qo * ldo2 : nullptr, ldo2, scratch, scratch_floats,
-                         concurrent_launches, nullptr, 0, stream);
-  }
-  return attn_dispatch(b, nq, nk, Q, ldq, K, ldk, V1, dv1, ldv1, O1, ldo1, V2, dv2, ldv2, O2, ldo2, scratch, scratch_floats,
-                       concurrent_launches, planes, planes_bytes, stream);
+DCL_API int dcl_cross_attention_ws(int b, int nq, int nk, const float *Q, int ldq, const float *K, int ldk,
+                                   const float *V1, int dv1, int ldv1, float *O1, int ldo1, const float *V2, int dv2,
+                                   int ldv2, float *O2, int ldo2, float *scratch, int64_t scratch_floats,
+                                   dclStream_t stream) {
+  return dcl_cross_attention_ws2(b, nq, nk, Q, ldq, K, ldk, V1, dv1, ldv1, O1, ldo1, V2, dv2, ldv2, O2, ldo2, scratch,
+                                 scratch_floats, 1, stream);
 }
 
-static int attn_dispatch(int b, int nq, int nk, const float *Q, int ldq, const float *K, int ldk, const float *V1, int dv1, int ldv1,
-                         float *O1, int ldo1, const float *V2, int dv2, int ldv2, float *O2, int ldo2, float *scratch,
-                         int64_t scratch_floats, int concurrent_launches, void *planes, int64_t planes_bytes, dclStream_t stream) {
-  DCL_CHECK_ARG(b >= 0 && nq >= 0 && nk > 0 && dv1 > 0 && dv1 % 32 == 0 && dv2 >= 0 && dv2 % 32 == 0);
-  if (b == 0 || nq == 0) return 0;
-  DCL_CHECK_ARG(Q && K && (V1 || planes) && O1 && (dv2 == 0 || (V2 && O2)) && b <= 65535);
-  DCL_CHECK_ARG(ldq >= 64 && ldk >= 64 && ldv1 >= dv1 && ldo1 >= dv1 && (dv2 == 0 || (ldv2 >= dv2 && ldo2 >= dv2)));
-  DCL_CHECK_ARG(ldq % 4 == 0 && ldk % 4 == 0 && ldv1 % 4 == 0 && ldo1 % 4 == 0 && ldv2 % 4 == 0 && ldo2 % 4 == 0);
-  DCL_CHECK_ARG((((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V1 | (uintptr_t)O1 | (uintptr_t)V2 | (uintptr_t)O2) & 15) == 0);
-  const bool v1_in_planes = V1 == nullptr;                 // (only the split kernel can take that: checked where it is chosen)
-  const int nvt = (dv1 + dv2) / 32;
-  DCL_CHECK_ARG(nvt == 1 || nvt == 2 || nvt == 4 || nvt == 8 || nvt == 10);
-  hipStream_t s = (hipStream_t)stream;
-  // Large grids: 8-wave workgroups sharing a K/V tile (2 waves/SIMD).  Small grids (fewer than one 8-wave
-  // workgroup per CU): 4-wave workgroups with double-buffered tiles, one per CU.
-  const long long blocks8 = (long long)b * dcl_div_up(nq, 256);
-  if (dv1 == 256 && dv2 == 64 && (g_attn_variant == 0 || g_attn_variant == 3 || g_attn_variant == 4)) {
-    // LDS-DMA pipeline: 8 waves (256 queries) per workgroup when that fills the chip, else 4 waves (128 queries)
-    // Two launches side by side (the two directions of a forward on parallel branches) whose 8-wave workgroups TOGETHER make
-    // one round of the chip -- 32 crops of 1024 x 1024, the shipped configuration -- also take the 8-wave form, unsplit: the
-    // 4-wave workgroups (402 registers, one wave per SIMD) of the two launches cannot share a CU, so they run one after the
-    // other at one wave per SIMD; same-job A/B of the whole forward, 8-wave vs 4-wave: 32 crops 3.813 vs 3.880 ms; 28 (224
-    // workgroups) 3.706 vs 3.696, 36: 4.72 vs 4.69, 40: 4.97 vs 4.97, 24: 3.20 vs 3.15, 16: 2.31 vs 2.16 -- hence the window.
-    const bool pair8 = concurrent_launches == 2 && 2 * blocks8 > 240 && 2 * blocks8 <= 256;
-    const bool split_usable = planes && g_attn_bf16 && (((uintptr_t)planes) & 15) == 0 &&
-                              planes_bytes >= (int64_t)b * dcl_div_up(nk, 32) * kAttnTileBytes;
-    const bool w8 = g_attn_variant == 3 ||
-                    (g_attn_variant == 0 && (blocks8 >= 256 || pair8 || (split_usable && attn_split_big(blocks8, nk))));
-    const int W = w8 ? 8 : 4;
-    const size_t lds = (size_t)(32 * kKPitch + 2 * 32 * 256 + 2 * 32 * 64 + W * 32 * kKPitch) * sizeof(float);
-    if (w8) {
-      // wave quantisation: blocks8 workgroups run in ceil(blocks8/256) rounds of one per CU.  When the last round is
-      // mostly empty (e.g. 320 workgroups = 2 rounds for 1.25 rounds of work) a key split of Z makes the rounds Z times
-      // shorter: cost(Z) = ceil(blocks8*Z/256)/Z full-workgroup times; taken when it saves >= 0.2 of one and the partial
-      // records stay below ~512 MiB
-      int nsplit = 1;
-      if (scratch && !(pair8 && g_attn_split == 0)) {
-        if (g_attn_split > 0) {
-          nsplit = g_attn_split;
-        } else {
-          double best = (double)dcl_div_up(blocks8, 256);
-          for (int z = 2; z <= 8; z *= 2) {
-            const double cost = (double)dcl_div_up(blocks8 * z, 256) / z;
-            if (cost <= best - 0.2 && (long long)z * b * nq * kAttnPartPitch <= (128ll << 20)) { best = cost; nsplit = z; }
-          }
-        }
-        const int ntiles = dcl_div_up(nk, 32);
-        if (nsplit > 8) nsplit = 8;
-        if (nsplit > ntiles / 2) nsplit = ntiles / 2;
-        while (nsplit > 1 && (long long)nsplit * b * nq * kAttnPartPitch > scratch_floats) --nsplit;
-        if (nsplit < 1) nsplit = 1;
-      }
-      const int nht = 2 * dcl_div_up(nk, 32);
-      const int64_t planes_need = (int64_t)b * (nht / 2) * kAttnTileBytes;
-      if (planes && planes_bytes >= planes_need && g_attn_bf16 && (((uintptr_t)planes) & 15) == 0) {
-        // P.V on the bf16 matrix pipe at fp32-sized errors: V as three exact bf16 pieces in tile order (one pass), then the sweep
-        const int c_begin = V1 ? 0 : 256;                  // V1 == NULL: its pieces are in `planes` already
-        const long long total = (long long)b * nht * (320 - c_begin) * 2;
-        hipLaunchKernelGGL(k_attn_split_v, dim3(dcl_grid_1d(total, 256)), dim3(256), 0, s, nk, nht, V1, ldv1, V2, ldv2,
-                           (unsigned *)planes, total, c_begin);
-        unsigned char *kplanes = (unsigned char *)planes + (size_t)b * nht * kAttnHalfBytes;
-        const long long ktotal = (long long)b * (nht / 2) * 32 * 8;
-        hipLaunchKernelGGL(k_attn_split_k, dim3(dcl_grid_1d(ktotal, 256)), dim3(256), 0, s, nk, nht / 2, K, ldk, (unsigned *)kplanes, ktotal);
-        const size_t lds_sp = (size_t)2 * (2 * kAttnHalfBytes + kAttnKTileBytes);
-        (void)hipFuncSetAttribute((const void *)k_cross_attn_split, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sp);
-        hipLaunchKernelGGL(k_cross_attn_split, dim3(dcl_div_up(nq, 256), b, nsplit), dim3(512), lds_sp, s, nq, nk, Q, ldq,
-                           (const unsigned char *)planes, (const unsigned char *)kplanes, O1, ldo1, O2, ldo2, scratch,
-                           (int)g_attn_xcd_remap, (int)g_attn_whatif);
-      } else {
-        if (v1_in_planes) {
-          dcl_set_error("dcl_cross_attention: V1 = NULL (pieces in `planes`) but this call does not take the split-bf16 kernel");
-          return DCL_EINVAL;
-        }
-        (void)hipFuncSetAttribute((const void *)k_cross_attn_dma<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k_cross_attn_dma<8>, dim3(dcl_div_up(nq, 256), b, nsplit), dim3(512), lds, s, nq, nk, Q, ldq, K, ldk,
-                           V1, ldv1, O1, ldo1, V2, ldv2, O2, ldo2, scratch, (int)g_attn_xcd_remap);
-      }
-      if (nsplit > 1)
-        hipLaunchKernelGGL(k_cross_attn_combine, dim3(dcl_grid_1d((long long)b * nq * 80, 256)), dim3(256), 0, s, b * nq,
-                           nsplit, scratch, O1, ldo1, O2, ldo2);
-    } else {
-      if (v1_in_planes) {
-        dcl_set_error("dcl_cross_attention: V1 = NULL (pieces in `planes`) but this call does not take the split-bf16 kernel");
-        return DCL_EINVAL;
-      }
-      // few workgroups (small batches): split the keys over up to 16 workgroups per query block, >= 2 tiles per split
-      int nsplit = 1;
-      if (scratch) {
-        // Key split of a 4-wave launch (one workgroup per CU): a power of two z (the 32 key tiles of a 1024-key crop divide
-        // evenly; 3 or 6 splits measured 2-4 % slower than 2 or 4) by a small time model in microseconds,
-        //     rounds(z) * (tiles * 1.1 / z + 4)  +  (z > 1 ? 4 + 0.15 * z * b * nq / 1024 : 0),
-        // rounds(z) = ceil(T z / 256) with T = 2 x blocks -- the two directions of a call run side by side (parallel branches
-        // of the whole-forward graph, the path every call this small takes); the second term is the combine launch.  Fitted
-        // to same-job A/B runs on the whole forward (tools/ab_hook.py dcl_debug_attention_split), best z at 1 / 2 / 4 / 6 / 8 /
-        // 12 / 16 / 20 / 32 crops of 1024 x 1024: 16 / 8 / 4 / 2 / 2 / 1 / 1 / 2 / 1 -- what this picks (one crop: 16 splits of two
-        // tiles against 8 of four, whole forward 0.414 vs 0.419 ms; two crops 0.547 vs 0.527: not there); against the former rule
-        // (fill 256 workgroups per launch) 4 crops -3 %, 6: -1.8 %, 8: -1.3 %, 12: -5.4 %, 16: -1.6 %, 20: -2.5 %.
-        nsplit = attn_small_split(b, nq, dcl_div_up(nk, 32));
-        const int ntiles = dcl_div_up(nk, 32);
-        if (nsplit > 16) nsplit = 16;
-        if (nsplit > ntiles / 2) nsplit = ntiles / 2;
-        while (nsplit > 1 && (long long)nsplit * b * nq * kAttnPartPitch > scratch_floats) --nsplit;
-        if (nsplit < 1) nsplit = 1;
-      }
-      (void)hipFuncSetAttribute((const void *)k_cross_attn_dma<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(k_cross_attn_dma<4>, dim3(dcl_div_up(nq, 128), b, nsplit), dim3(256), lds, s, nq, nk, Q, ldq, K,
-                         ldk, V1, ldv1, O1, ldo1, V2, ldv2, O2, ldo2, scratch, (int)g_attn_xcd_remap);
-      if (nsplit > 1)
-        hipLaunchKernelGGL(k_cross_attn_combine, dim3(dcl_grid_1d((long long)b * nq * 80, 256)), dim3(256), 0, s, b * nq,
-                           nsplit, scratch, O1, ldo1, O2, ldo2);
-    }
-  }
-#ifdef DCL_DIAG
-  else if ((blocks8 >= 256 && g_attn_variant != 2) || g_attn_variant == 1) {
-    const size_t lds = (size_t)(32 * kKPitch + 32 * nvt * 32 + 8 * 32 * kKPitch) * sizeof(float);
-#define ATT8(N)                                                                                                \
-  do {                                                                                                         \
-    (void)hipFuncSetAttribute((const void *)k_cross_attn_shared<8, N>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (int)lds);                                                                       \
-    hipLaunchKernelGGL((k_cross_attn_shared<8, N>), dim3(dcl_div_up(nq, 256), b), dim3(512), lds, s, nq, nk, Q, \
-                       ldq, K, ldk, V1, dv1, ldv1, O1, ldo1, V2, dv2, ldv2, O2, ldo2);                         \
-  } while (0)
-    switch (nvt) {
-      case 1: ATT8(1); break;
-      case 2: ATT8(2); break;
-      case 4: ATT8(4); break;
-      case 8: ATT8(8); break;
-      default: ATT8(10); break;
-    }
-#undef ATT8
-  } else {
-    const size_t lds = (size_t)2 * (32 * kKPitch + 32 * nvt * 32) * sizeof(float);
-#define ATT(N)                                                                                                 \
-  do {                                                                                                         \
-    (void)hipFuncSetAttribute((const void *)k_cross_attn<N>, hipFuncAttributeMaxDynamicSharedMemorySize,       \
-                              (int)lds);                                                                       \
-    hipLaunchKernelGGL((k_cross_attn<N>), dim3(dcl_div_up(nq, 128), b), dim3(256), lds, s, nq, nk, Q, ldq, K,   \
-                       ldk, V1, dv1, ldv1, O1, ldo1, V2, dv2, ldv2, O2, ldo2);                                 \
-  } while (0)
-    switch (nvt) {
-      case 1: ATT(1); break;
-      case 2: ATT(2); break;
-      case 4: ATT(4); break;
-      case 8: ATT(8); break;
-      default: ATT(10); break;
-    }
-#undef ATT
-  }
-#else
-  else {
-    // the product library carries the one kernel the DCL-Net path uses (V = [256 | 64] channels, models/DCL_Net.py:206-215);
-    // its general-shape predecessors live in the diagnostic library only
-    dcl_set_error("dcl_cross_attention: only dv1 = 256, dv2 = 64 is built into the product library (got %d, %d)", dv1, dv2);
-    return DCL_EINVAL;
-  }
-#endif
-  DCL_LAUNCH_CHECK();
-  return 0;
+DCL_API int dcl_cross_attention(int b, int nq, int nk, const float *Q, int ldq, const float *K, int ldk,
+                                const float *V1, int dv1, int ldv1, float *O1, int ldo1, const float *V2, int dv2,
+                                int ldv2, float *O2, int ldo2, dclStream_t stream) {
+  return dcl_cross_attention_ws(b, nq, nk, Q, ldq, K, ldk, V1, dv1, ldv1, O1, ldo1, V2, dv2, ldv2, O2, ldo2, nullptr, 0,
+                                stream);
 }
 
 DCL_API int dcl_conf_pool(int b, int c, int n1, int n2, const float *logit1, const float *logit2, const float *F1,
