@@ -13,7 +13,9 @@
 // offset: both operands are read straight from global memory with the 32 lanes of a half-wave on 32 consecutive channels
 // (coalesced 128-B segments), split over row ranges into partial sums that a second kernel adds in split order
 // (deterministic; the reference's cuBLAS order is unspecified, so parity is by tolerance).  pointnet_sp's interpolation
-// gradient keeps the reference's atomic scatter (its summation order is unspecified there too).  pointnet_lib's three
+// gradient is an ordered gather of its own (readout_grad.hip: row-major (n, C) rows, flat over all crops, a workspace linear
+// in the problem); the reference's atomic scatter stays below as dcl_three_interpolate_grad_sp, the unspecified-order form
+// that tests and tools/bench_readout_grad.py compare it with, and nothing on the training path calls it.  pointnet_lib's three
 // gradients are gathers too: an inverse index of idx (each point's positions in ascending order, built once per call and
 // shared by all channels) drives an LDS-staged pass that adds each point's contributions in that order -- deterministic,
 // and equal to a sequential scatter in position order bit for bit.

@@ -1431,7 +1431,30 @@ def sparse_avgpool_backward(dout, nbr, n_out, n_in, rf):
 
 
 def three_interpolate_grad_sp(grad_out, idx, weight, m):
-    """three_interpolate_grad_wrapper of libs/pointnet_sp -> grad_points (m, C)."""
+    """three_interpolate_grad_wrapper of libs/pointnet_sp -> grad_points (m, C): every row's contributions added in ascending
+    flat position of idx (csrc/readout_grad.hip) -- numpy.add.at on float32, the same bits on every call.  grad_out (n, C) with
+    unit channel stride and a row stride >= C (a column block of a wider tensor) is read where it lies."""
+    N.need_cuda(grad_out, idx, weight)
+    n, c = grad_out.shape
+    m = int(m)
+    if grad_out.dtype == torch.float32 and grad_out.stride(1) == 1 and grad_out.stride(0) >= c:
+        stride = grad_out.stride(0)
+    else:
+        grad_out, stride = N.f32c(grad_out), c
+    idx, weight = N.i32c(idx), N.f32c(weight)
+    assert tuple(idx.shape) == (n, 3) and tuple(weight.shape) == (n, 3)
+    gp = torch.empty((m, c), dtype=torch.float32, device=grad_out.device)
+    ws, nb = _pn_grad_ws(N.lib().dcl_three_interpolate_grad_sp_ws_bytes, (c, n, m), grad_out.device,
+                         "three_interpolate_grad_sp")
+    N.check(N.lib().dcl_three_interpolate_grad_sp_ordered(c, n, m, N.ptr(grad_out), C.c_int64(stride), N.ptr(idx),
+                                                          N.ptr(weight), N.ptr(gp), N.ptr(ws), C.c_int64(nb), N.stream()),
+            "three_interpolate_grad_sp_ordered")
+    return gp
+
+
+def three_interpolate_grad_sp_atomic(grad_out, idx, weight, m):
+    """The same gradient by the reference's atomic scatter (interpolate_gpu.cu:124-148; the order of a row's adds is
+    whatever the hardware serves): what tools/bench_readout_grad.py and the tests compare the ordered form with."""
     N.need_cuda(grad_out, idx, weight)
     n, c = grad_out.shape
     gp = torch.zeros((m, c), dtype=torch.float32, device=grad_out.device)

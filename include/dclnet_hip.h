@@ -583,6 +583,20 @@ int dcl_sparse_avgpool_bwd(const float *dout, const int32_t *inv, int cap_in, in
 /* three_interpolate_grad of libs/pointnet_sp (interpolate_gpu.cu:124-148): atomic scatter into a ZEROED (m,c) buffer.  */
 int dcl_three_interpolate_grad_sp(int c, int n, int m, const float *grad_out, const int32_t *idx, const float *weight,
                                   float *grad_points_zeroed, dclStream_t stream);
+/* The same gradient as an ordered gather (csrc/readout_grad.hip), what autograd.ThreeInterpolateFn uses: grad_points (m,c)
+ * is WRITTEN WHOLE (rows nobody names get +0; the caller does not zero it); element [j][ch] is the sum, from +0, over the
+ * flat positions q = 3p + k with idx[q] == j in ascending q of fmul(grad_out[p*grad_stride + ch], weight[q]), one rounded add
+ * at a time -- numpy.add.at on float32 bit for bit, the same bits on every call, and one of the orders the atomic form can
+ * take.  grad_out has row stride grad_stride >= c (floats): a column block of a wider tensor is read in place.  Indices
+ * outside [0, m) contribute nothing and are never used as addresses; a query may name a row more than once.  ws: at least
+ * the _ws_bytes of the same sizes (linear: 12 bytes per position, 8 per row, 4 KiB), 4-byte aligned.  No float atomics, no
+ * read-back: capturable.  DCL_EINVAL before any device work for negative sizes, 3n >= 2^31 - 8192, m >= 2^30, c > 65535,
+ * grad_stride < c, a null buffer of a non-empty problem or a short workspace; c == 0 or m == 0 does nothing; n == 0
+ * zero-fills grad_points.  The size query needs no GPU.                                                                 */
+int dcl_three_interpolate_grad_sp_ws_bytes(int c, int n, int m, int64_t *bytes_host);
+int dcl_three_interpolate_grad_sp_ordered(int c, int n, int m, const float *grad_out, int64_t grad_stride,
+                                          const int32_t *idx, const float *weight, float *grad_points,
+                                          void *ws, int64_t ws_bytes, dclStream_t stream);
 /* voxelize_bp (voxelize.cu:35-50): d_feats[rules[v][1+i]] += (average ? 1/n_v : 1) * d_out[v]; d_feats ZEROED (N,C).   */
 int dcl_voxelize_bp(const float *d_out, const int32_t *rules, float *d_feats_zeroed, int n_rows, int max_active, int c,
                     int average, dclStream_t stream);
