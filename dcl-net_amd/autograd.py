@@ -3,10 +3,12 @@
 libs/pointnet_lib/pointnet2_utils.py:40-76,144-238, libs/pointgroup_ops/functions/pointgroup_ops.py:42-75):
 forward = the inference kernels, backward = csrc/backward.hip; and of the correspondence attention (CrossAttentionFn:
 forward = dcl_cross_attention, backward = csrc/attention_bwd.hip), which the reference forms from bmm and softmax;
-and of the losses' Chamfer distance (ChamferFn: csrc/chamfer.hip in both passes).
+and of the losses' Chamfer distance (ChamferFn: csrc/chamfer.hip in both passes); and of the rotation head's projection
+(Ortho9dFn: forward = dcl_ortho9d_to_matrix, backward = csrc/rotation_grad.hip).
 Used by the module mirrors (spconv/, libs/) so that `Network(cfg, mode='train')` is trainable on the GPU."""
 import torch
 from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from . import ops as _ops
 
@@ -182,3 +184,26 @@ class ChamferFn(Function):
         grad_pred, grad_target = _ops.chamfer_backward(pred, target, idx_pt, idx_tp, _ops.N.f32c(g_pt), _ops.N.f32c(g_tp),
                                                        ctx.active, need_pred, need_target)
         return grad_pred, grad_target, None
+
+
+class Ortho9dFn(Function):
+    """ortho9d2matrix (models/DCL_Net.py:15-36) with its gradient on the device: o9 (b,9) -> R (b,3,3).  Forward =
+    ops.ortho9d_to_matrix, so a train-mode rotation is the eval kernel's bit for bit; backward = ops.ortho9d_backward, the
+    closed form of the polar factor's derivative (denominators s_i + s_j, about 2 for near-orthonormal axes; autograd through
+    an SVD's U and V divides by s_i^2 - s_j^2).  Only o9 is kept, nothing is copied to the host, and the same inputs give the
+    same bits.  CUDA tensors only."""
+
+    @staticmethod
+    def forward(ctx, o9):
+        if not o9.is_cuda:
+            raise RuntimeError("Ortho9dFn (train_rotation='device') runs on the GPU only: got a %s tensor; the 'host' "
+                               "composition serves CPU tensors" % (o9.device,))
+        o9 = _ops.N.f32c(o9)
+        ctx.save_for_backward(o9)
+        return _ops.ortho9d_to_matrix(o9)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_R):
+        o9, = ctx.saved_tensors
+        return _ops.ortho9d_backward(o9, _ops.N.f32c(grad_R))

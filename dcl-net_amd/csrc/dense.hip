@@ -14,6 +14,7 @@
 // and one final division by the softmax denominator.  Bound: fp32 MFMA (157 TFLOP/s spec);
 // algorithmic flop = 2*(dk+dv)*Nq*Nk per crop per direction.
 #include "common.h"
+#include "ortho9d.h"
 #include <atomic>
 #include <math.h>
 
@@ -1075,74 +1076,12 @@ __global__ __launch_bounds__(256) void k_conf_pool_small(int c, int n1, int n2, 
 
 // ---- ortho9d2matrix (models/DCL_Net.py:15-36) ------------------------------------------------------
 // R = U diag(1,1,det(U V^T)) V^T of the column-stacked, normalised raw vectors: one thread per crop,
-// one-sided Jacobi SVD in fp64 (the reference calls a batched LAPACK/MAGMA gesdd, ms-scale latency).
+// one-sided Jacobi SVD in fp64 (ortho9d.h, shared with the gradient in rotation_grad.hip).
 // With A V = U Sigma:  R = u1 v1^T + u2 v2^T + det(V) (u1 x u2) v3^T   (sign-ambiguity free).
 __device__ void ortho9d_one(const float *__restrict__ o9, float *__restrict__ R, int i) {
-  double A[3][3], V[3][3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float x = o9[i * 9 + c * 3], y = o9[i * 9 + c * 3 + 1], z = o9[i * 9 + c * 3 + 2];
-    const float mag = sqrtf((x * x + y * y) + z * z) + 1e-8f;       // utils/transform3D.py:18-20 (fp32)
-    A[0][c] = (double)(x / mag); A[1][c] = (double)(y / mag); A[2][c] = (double)(z / mag);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) V[r][c] = r == c ? 1.0 : 0.0;
-  }
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    double off = 0.0;
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-      for (int q = p + 1; q < 3; ++q) {
-        double alpha = 0, beta = 0, gamma = 0;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) { alpha += A[r][p] * A[r][p]; beta += A[r][q] * A[r][q]; gamma += A[r][p] * A[r][q]; }
-        off = fmax(off, fabs(gamma) / sqrt(alpha * beta + 1e-300));
-        if (fabs(gamma) < 1e-300) continue;
-        const double zeta = (beta - alpha) / (2.0 * gamma);
-        const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-        const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-          const double ap = A[r][p], aq = A[r][q];
-          A[r][p] = cs * ap - sn * aq; A[r][q] = sn * ap + cs * aq;
-          const double vp = V[r][p], vq = V[r][q];
-          V[r][p] = cs * vp - sn * vq; V[r][q] = sn * vp + cs * vq;
-        }
-      }
-    if (off < 1e-15) break;
-  }
-  // sort the three (column of A, column of V) pairs by descending singular value with explicit swaps -- no
-  // dynamically indexed local arrays, so the kernel needs no scratch memory
-  double a0[3] = {A[0][0], A[1][0], A[2][0]}, a1[3] = {A[0][1], A[1][1], A[2][1]}, a2[3] = {A[0][2], A[1][2], A[2][2]};
-  double v0[3] = {V[0][0], V[1][0], V[2][0]}, v1[3] = {V[0][1], V[1][1], V[2][1]}, v2[3] = {V[0][2], V[1][2], V[2][2]};
-  double s0 = sqrt(a0[0] * a0[0] + a0[1] * a0[1] + a0[2] * a0[2]);
-  double s1 = sqrt(a1[0] * a1[0] + a1[1] * a1[1] + a1[2] * a1[2]);
-  double s2 = sqrt(a2[0] * a2[0] + a2[1] * a2[1] + a2[2] * a2[2]);
-#define DCL_SWAP_COLS(sa, sb, aa, ab, va, vb)                                  \
-  if (sa < sb) {                                                               \
-    double t_ = sa; sa = sb; sb = t_;                                          \
-    for (int r_ = 0; r_ < 3; ++r_) {                                           \
-      t_ = aa[r_]; aa[r_] = ab[r_]; ab[r_] = t_;                               \
-      t_ = va[r_]; va[r_] = vb[r_]; vb[r_] = t_;                               \
-    }                                                                          \
-  }
-  DCL_SWAP_COLS(s0, s1, a0, a1, v0, v1)
-  DCL_SWAP_COLS(s1, s2, a1, a2, v1, v2)
-  DCL_SWAP_COLS(s0, s1, a0, a1, v0, v1)
-#undef DCL_SWAP_COLS
-  double u1[3], u2[3], u3[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) { u1[r] = a0[r] / s0; u2[r] = a1[r] / s1; }
-  u3[0] = u1[1] * u2[2] - u1[2] * u2[1];
-  u3[1] = u1[2] * u2[0] - u1[0] * u2[2];
-  u3[2] = u1[0] * u2[1] - u1[1] * u2[0];
-  const double detV = v0[0] * (v1[1] * v2[2] - v1[2] * v2[1]) - v0[1] * (v1[0] * v2[2] - v1[2] * v2[0]) +
-                      v0[2] * (v1[0] * v2[1] - v1[1] * v2[0]);
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      R[i * 9 + r * 3 + c] = (float)(u1[r] * v0[c] + u2[r] * v1[c] + detV * u3[r] * v2[c]);
+  Ortho9dFactors f;
+  ortho9d_factors(o9 + i * 9, f);
+  ortho9d_compose(f, R + i * 9);
 }
 __global__ void k_ortho9d(int b, const float *__restrict__ o9, float *__restrict__ R) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

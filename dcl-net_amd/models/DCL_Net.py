@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..autograd import CrossAttentionFn
+from ..autograd import CrossAttentionFn, Ortho9dFn
 from .. import spconv
 from ..libs.pointgroup_ops.functions import pointgroup_ops
 from .losses import losses  # noqa: F401  (reference: models/DCL_Net.py::losses)
@@ -47,12 +47,25 @@ def normalize_vector(v):
     return v / (torch.sqrt(v.pow(2).sum(1, keepdim=True)) + 1e-8)
 
 
-def ortho9d2matrix(x_raw, y_raw, z_raw):
+TRAIN_ROTATION_MODES = ("host", "device")
+
+
+def check_train_rotation(train_rotation):
+    if train_rotation not in TRAIN_ROTATION_MODES:
+        raise ValueError('train_rotation must be "host" or "device", got %r' % (train_rotation,))
+    return train_rotation
+
+
+def ortho9d2matrix(x_raw, y_raw, z_raw, train_rotation="host"):
     """Rotation from three raw axes (reference models/DCL_Net.py:15-36): on-device 3x3 SVD kernel.  When a gradient is
-    needed (training) the same projection is composed from differentiable torch ops -- normalised axes as columns,
-    U diag(1, 1, det(U V^T)) V^T -- with the batched 3x3 SVD on the host (b tiny matrices)."""
+    needed (training), train_rotation says how.  "host" (default): the same projection composed from differentiable torch
+    ops -- normalised axes as columns, U diag(1, 1, det(U V^T)) V^T -- with the batched 3x3 SVD on the host (b tiny
+    matrices, a blocking copy each way).  "device": autograd.Ortho9dFn -- the eval kernel forward, the closed-form gradient
+    kernel backward, nothing leaves the GPU."""
     if not (torch.is_grad_enabled() and (x_raw.requires_grad or y_raw.requires_grad or z_raw.requires_grad)):
         return ops.ortho9d_to_matrix(torch.cat([x_raw, y_raw, z_raw], dim=1))
+    if check_train_rotation(train_rotation) == "device":
+        return Ortho9dFn.apply(torch.cat([x_raw, y_raw, z_raw], dim=1))
     dev = x_raw.device
     m = torch.stack([normalize_vector(x_raw), normalize_vector(y_raw), normalize_vector(z_raw)], dim=2).cpu()
     U, _, Vh = torch.linalg.svd(m)
@@ -72,7 +85,7 @@ def _fuser():
 class Network(nn.Module):
     def __init__(self, cfg, mode="train", fused=True, graph_max_batch=8, async_inputs=False, graph_max_points=98304,
                  single_stream=False, pipeline_chunks=1, capture_graph=True, pair_features=None,
-                 train_attention="materialised"):
+                 train_attention="materialised", train_rotation="host"):
         """graph_max_batch > 0 (default 8): eval-mode calls with at most that many crops go through forward_graphed (one
         whole-forward hipGraph per batch size, captured on first use) -- the one-image-at-a-time eval loops of the
         reference (tools/test_LM.py:104-112: one object per call) are launch-bound otherwise: 0.53 instead of 1.1 ms
@@ -99,8 +112,13 @@ class Network(nn.Module):
         as a (b, M, N) map that autograd keeps for the backward pass, followed by two more bmm with it; "fused" = one
         autograd.CrossAttentionFn per direction (forward dcl_cross_attention, backward csrc/attention_bwd.hip), which stores
         nothing of the map's size in either pass.
+        train_rotation: how the same path differentiates the rotation head's projection (ortho9d2matrix).  "host" (default) =
+        torch ops around a batched SVD on the host, two blocking copies per step; "device" = autograd.Ortho9dFn, the eval
+        kernel forward and csrc/rotation_grad.hip backward, no host synchronisation, and a gradient that stays accurate for
+        near-orthonormal axes.  Calls that need no gradient do not read it.
         These are constructor arguments on purpose: nothing on the call path reads the environment."""
         super().__init__()
+        self.train_rotation = check_train_rotation(train_rotation)
         if train_attention not in ("materialised", "fused"):
             raise ValueError('train_attention must be "materialised" or "fused", got %r' % (train_attention,))
         self.train_attention = train_attention
@@ -987,7 +1005,7 @@ class Network(nn.Module):
                          self.neck_fuser_bi(torch.cat([F_Yc_p, Yo["p2"]], dim=1))], dim=2)
         F_p_wei = torch.sum(F_p * conf_softmax, dim=2, keepdim=True)
         o9 = self.regressor_rot(F_p_wei).squeeze(-1)
-        rot_pred = ortho9d2matrix(o9[:, :3], o9[:, 3:6], o9[:, 6:])
+        rot_pred = ortho9d2matrix(o9[:, :3], o9[:, 3:6], o9[:, 6:], self.train_rotation)
         trans_pred = self.regressor_trans(F_p_wei).squeeze(-1)
         prediction = {"trans_pred": trans_pred, "rot_pred": rot_pred, "conf": conf.squeeze(1), "F_Xo_p": F_Xo_p}
         if self.mode != "test":

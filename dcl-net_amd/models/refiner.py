@@ -14,10 +14,10 @@ from .Modules import Head_MultiLayerPerceptron
 from .losses import losses_refiner  # noqa: F401  (reference: models/refiner.py::losses_refiner)
 
 
-def ortho9d2matrix(x_raw, y_raw, z_raw):
+def ortho9d2matrix(x_raw, y_raw, z_raw, train_rotation="host"):
     """models/refiner.py:34-56 == models/DCL_Net.py:15-36; differentiable when a gradient is needed (DCL_Net.ortho9d2matrix)"""
     from .DCL_Net import ortho9d2matrix as _o
-    return _o(x_raw, y_raw, z_raw)
+    return _o(x_raw, y_raw, z_raw, train_rotation)
 
 
 _VERSION_OF = __import__("operator").attrgetter("_version")
@@ -35,8 +35,12 @@ def _param_version(mod):
 class Refiner(nn.Module):
     POSE_HEADS_MAX = 128      # crops up to which the two heads run as dcl_pose_heads (two launches; Network.POSE_HEADS_MAX)
 
-    def __init__(self, cfg=None):
+    def __init__(self, cfg=None, train_rotation="host"):
+        """train_rotation: "host" (default) or "device" -- how a call that needs a gradient differentiates the rotation
+        head's projection; see DCL_Net.Network."""
         super().__init__()
+        from .DCL_Net import check_train_rotation
+        self.train_rotation = check_train_rotation(train_rotation)
         self.MLP_share = Head_MultiLayerPerceptron([256 + 3, 512, 512, 1024], ["relu"] * 3, [False] * 3, [0.0] * 3)
         self.regressor_rot2 = Head_MultiLayerPerceptron([1024, 512, 128, 9], ["relu", "relu", "none"], [False] * 3,
                                                         [0.0] * 3)
@@ -129,7 +133,7 @@ class Refiner(nn.Module):
         shared = (self.MLP_share(x) * conf_softmax).sum(dim=2, keepdim=True)
         o9 = self.regressor_rot2(shared).squeeze(-1)
         delta_t = self.regressor_trans2(shared).squeeze(-1)
-        return {"trans_pred": delta_t, "rot_pred": ortho9d2matrix(o9[:, :3], o9[:, 3:6], o9[:, 6:])}
+        return {"trans_pred": delta_t, "rot_pred": ortho9d2matrix(o9[:, :3], o9[:, 3:6], o9[:, 6:], self.train_rotation)}
 
     def forward(self, input_dict):
         """reference contract: {"input_features" (b,259,n), "conf" (b,n+m), "obj_idx"} ->

@@ -1269,6 +1269,36 @@ def ortho9d_to_matrix(o9):
     return R
 
 
+def _ortho9d_bwd_args(o9, grad_R):
+    b = o9.shape[0]
+    assert o9.shape == (b, 9) and grad_R.shape == (b, 3, 3), (tuple(o9.shape), tuple(grad_R.shape))
+    assert o9.dtype == torch.float32 and grad_R.dtype == torch.float32
+    assert o9.is_contiguous() and grad_R.is_contiguous()
+    return b
+
+
+def ortho9d_backward(o9, grad_R):
+    """Gradient of ortho9d_to_matrix (dcl_ortho9d_bwd): o9 (b,9), grad_R (b,3,3) = dL/dR, both contiguous fp32 -> dL/do9 (b,9).
+    One launch, no host synchronisation, no workspace; the same inputs give the same bits.  A crop with a non-finite o9 or
+    grad_R gets NaN in its nine outputs and touches no other crop (include/dclnet_hip.h has the formula and the guards)."""
+    N.need_cuda(o9, grad_R)
+    b = _ortho9d_bwd_args(o9, grad_R)
+    out = torch.empty((b, 9), dtype=torch.float32, device=o9.device)
+    N.check(N.lib().dcl_ortho9d_bwd(b, N.ptr(o9), N.ptr(grad_R), N.ptr(out), N.stream()), "ortho9d_bwd")
+    return out
+
+
+def ortho9d_backward_host(o9, grad_R):
+    """ortho9d_backward on CPU tensors (dcl_ortho9d_bwd_host: the kernel's routine compiled for the host).  For checking the
+    mathematics where there is no GPU; no model path calls it."""
+    if o9.is_cuda or grad_R.is_cuda:
+        raise RuntimeError("ortho9d_backward_host is the host twin: pass CPU tensors (ortho9d_backward takes the GPU's)")
+    b = _ortho9d_bwd_args(o9, grad_R)
+    out = torch.empty((b, 9), dtype=torch.float32)
+    N.check(N.lib().dcl_ortho9d_bwd_host(b, N.ptr(o9), N.ptr(grad_R), N.ptr(out)), "ortho9d_bwd_host")
+    return out
+
+
 def add_s(cld, R_pred, t_pred, R_gt, t_gt, cls=None, sym_flag=None, mode="adds"):
     """ADD-S per object (tools/test_YCBV_stage1.py:186-189) without the (b,P,P,3) intermediate.
     cld (n_clouds,P,3) f32; cls (b,) int32 picks each object's cloud (None: cloud o for object o) -> (b,) f32.

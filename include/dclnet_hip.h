@@ -567,6 +567,20 @@ int dcl_linear_group_fwd(const DclLinearJob *jobs, int njobs, dclStream_t stream
 /* ortho9d2matrix (models/DCL_Net.py:15-36): o9 (b,9) -> R (b,3,3).             */
 int dcl_ortho9d_to_matrix(int b, const float *o9, float *R, dclStream_t stream);
 
+/* Its gradient (csrc/rotation_grad.hip): grad_R (b,3,3) = dL/dR -> grad_o9 (b,9) = dL/do9, one launch, nothing saved by
+ * the forward but o9, no workspace and no atomics: two calls give the same bits.  With M = the normalised axes as columns
+ * and the projection's own factors U' = [u1, u2, u1 x u2], V' = [v1, v2, det(V) v3], M = U' diag(s') V'^T (s'_3 signed),
+ *     B = U'^T grad_R V',   Y_ij = (B_ij - B_ji) / (s'_i + s'_j)  (i != j, Y_ii = 0),   dL/dM = U' Y V'^T,
+ * evaluated in fp64, then through the normalisation of every raw axis r (mag = |r| + 1e-8, g = its column of dL/dM):
+ *     dL/dr = g / mag - r (r . g) / (|r| mag^2),   the second term 0 where |r| = 0.
+ * Guards: a term of Y whose denominator has |s'_i + s'_j| <= 1e-12 s'_1 contributes 0 (left-handed axes whose second and
+ * third singular values agree, rank <= 1: the projection is not differentiable there); at most 30 Jacobi sweeps; finite
+ * inputs give finite outputs (unless a value itself exceeds fp32), parallel axes, zero axes and all zeros included; a crop
+ * with a non-finite value in its o9 or grad_R gets NaN in its own nine outputs and no other crop is touched.
+ * b == 0 is not an error.  dcl_ortho9d_bwd_host runs the same routine on HOST pointers and makes no GPU call.          */
+int dcl_ortho9d_bwd(int b, const float *o9, const float *grad_R, float *grad_o9, dclStream_t stream);
+int dcl_ortho9d_bwd_host(int b, const float *o9, const float *grad_R, float *grad_o9);
+
 /* ------------------------------------------------------------ training-side kernels (csrc/backward.hip) ---
  * Transposed rulebook: inv[k][i] = o for every nbr[k][o] = i >= 0, -1 elsewhere (inv: i32[kvol][cap_in]).  With it the
  * input gradient of indice_conv (spconv_ops.h:351-438) is dcl_sparse_conv_fwd(dOut, inv, W^T per offset).            */
