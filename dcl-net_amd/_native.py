@@ -11,7 +11,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "libdclnet_hip.so")
-DIAG_SO_PATH = os.path.join(os.path.dirname(_HERE), "tests", "_diag", "libdclnet_hip_diag.so")
+DIAG_SO_PATH = os.path.join(os.path.dirname(_HERE), "tools", "_bin", "libdclnet_hip_diag.so")
 _LIB = None
 
 vp = C.c_void_p
@@ -19,7 +19,7 @@ vp = C.c_void_p
 
 def build(verbose=False, diag=False):
     """hipcc --offload-arch=gfx950 build of csrc/ into libdclnet_hip.so (in-tree); diag=True also builds the diagnostic
-    library (tests/_diag/libdclnet_hip_diag.so: the same sources with -DDCL_DIAG, see csrc/Makefile)."""
+    library (tools/_bin/libdclnet_hip_diag.so: the same sources with -DDCL_DIAG, see csrc/Makefile)."""
     out = None if verbose else subprocess.DEVNULL
     subprocess.check_call(["make", "-C", os.path.join(_HERE, "csrc"), "-j8"] + (["all", "diag"] if diag else []), stdout=out)
     return SO_PATH
@@ -52,7 +52,7 @@ def lib():
 
 class diagnostic_library(object):
     """`with _native.diagnostic_library() as L:` -- tests/ and tools/ only.  Inside the block every op of this package
-    calls into the DIAGNOSTIC build (tests/_diag/libdclnet_hip_diag.so or `path`: same sources, -DDCL_DIAG) whose
+    calls into the DIAGNOSTIC build (tools/_bin/libdclnet_hip_diag.so or `path`: same sources, -DDCL_DIAG) whose
     dcl_debug_* hooks select kernel variants; the product library is restored on exit."""
 
     def __init__(self, path=None):

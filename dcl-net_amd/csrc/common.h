@@ -9,7 +9,7 @@
 
 // A/B and tuning switches.  The PRODUCT library (libdclnet_hip.so) is built without DCL_DIAG: every switch is a compile-time
 // constant, no dcl_debug_* symbol is exported, superseded kernel variants are not compiled and nothing reads the environment.
-// The DIAGNOSTIC library (make diag -> tests/_diag/libdclnet_hip_diag.so, -DDCL_DIAG) turns them into process-wide atomics
+// The DIAGNOSTIC library (make diag -> tools/_bin/libdclnet_hip_diag.so, -DDCL_DIAG) turns them into process-wide atomics
 // set through the dcl_debug_* entry points of include/dclnet_hip.h; tests and tools/ select kernel variants through it.
 #ifdef DCL_DIAG
 #include <atomic>

@@ -10,7 +10,7 @@
 //                           the column max/sum is 16 registers + one lane^32 exchange
 //     O += [V_p;V_m] P      the S accumulator registers ARE the B operand of the second MFMA
 //                           (register e of lane-half h holds key (e&3)+8(e>>2)+4h), no shuffle/LDS
-// with a lazily updated reference maximum (rescale only when the running max grows by > kThr),
+// with a lazily updated reference maximum (a query rescales only when its running max grows by > kThr),
 // and one final division by the softmax denominator.  Bound: fp32 MFMA (157 TFLOP/s spec);
 // algorithmic flop = 2*(dk+dv)*Nq*Nk per crop per direction.
 #include "common.h"
@@ -139,8 +139,9 @@ __global__ __launch_bounds__(256, 1) void k_cross_attn(
     }
     m_tile = fmaxf(m_tile, __shfl_xor(m_tile, 32, 64));
     if (__ballot(m_tile > m_ref + kThr) != 0ull) {       // rare, wave-uniform
-      const float m_new = fmaxf(m_ref, m_tile);
-      const float f = __expf(m_ref - m_new);             // exp(-inf) = 0 on the first tile
+      const bool up = m_tile > m_ref + kThr;             // only the queries that asked: the others multiply by an exact 1,
+      const float m_new = up ? m_tile : m_ref;           // so a query's bits never depend on its wave mates' data
+      const float f = up ? __expf(m_ref - m_new) : 1.0f; // exp(-inf) = 0 on the first tile
       l_part *= f;
 #pragma unroll
       for (int t = 0; t < NVT; ++t)
@@ -271,8 +272,9 @@ __global__ __launch_bounds__(WAVES * 64, WAVES >= 8 ? 2 : 1) void k_cross_attn_s
     }
     m_tile = fmaxf(m_tile, __shfl_xor(m_tile, 32, 64));
     if (__ballot(m_tile > m_ref + kThr) != 0ull) {       // rare, wave-uniform
-      const float m_new = fmaxf(m_ref, m_tile);
-      const float f = __expf(m_ref - m_new);             // exp(-inf) = 0 on the first tile
+      const bool up = m_tile > m_ref + kThr;             // only the queries that asked: the others multiply by an exact 1,
+      const float m_new = up ? m_tile : m_ref;           // so a query's bits never depend on its wave mates' data
+      const float f = up ? __expf(m_ref - m_new) : 1.0f; // exp(-inf) = 0 on the first tile
       l_part *= f;
 #pragma unroll
       for (int t = 0; t < NVT; ++t)
@@ -477,8 +479,9 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void k_cross_attn_dma(
     }
     m_tile = fmaxf(m_tile, __shfl_xor(m_tile, 32, 64));
     if (__ballot(m_tile > m_ref + kThr) != 0ull) {
-      const float m_new = fmaxf(m_ref, m_tile);
-      const float f = __expf(m_ref - m_new);
+      const bool up = m_tile > m_ref + kThr;               // (only the queries that asked; see k_cross_attn)
+      const float m_new = up ? m_tile : m_ref;
+      const float f = up ? __expf(m_ref - m_new) : 1.0f;
       l_part *= f;
 #pragma unroll
       for (int t = 0; t < NVT; ++t)
@@ -749,8 +752,9 @@ __global__ __launch_bounds__(512, 2) void k_cross_attn_split(
     for (int e = 0; e < 16; ++e) m_tile = fmaxf(m_tile, S[e]);
     m_tile = fmaxf(m_tile, __shfl_xor(m_tile, 32, 64));
     if (__ballot(m_tile > m_ref + kThr) != 0ull) {
-      const float m_new = fmaxf(m_ref, m_tile);
-      const float f = __expf(m_ref - m_new);
+      const bool up = m_tile > m_ref + kThr;               // (only the queries that asked; see k_cross_attn)
+      const float m_new = up ? m_tile : m_ref;
+      const float f = up ? __expf(m_ref - m_new) : 1.0f;
       l_part *= f;
 #pragma unroll
       for (int t = 0; t < NVT; ++t)

@@ -402,7 +402,7 @@ static bool conv_launch_is_few(const DclConvSides &sides, int nsides) {
   if (hinted || !capacity_mode) return rows <= limit;         // expected (capacity mode with a hint) or exact row counts
   return conv_few_rows(rows, capacity_mode);
 }
-// A/B and tuning switches: process-wide atomics set through dcl_debug_* in the DIAGNOSTIC library (-DDCL_DIAG, tests/_diag/),
+// A/B and tuning switches: process-wide atomics set through dcl_debug_* in the DIAGNOSTIC library (-DDCL_DIAG, tools/_bin/),
 // compile-time constants in the product library -- the product has no hooks, no superseded kernels and no getenv
 DCL_HOOK_INT(g_conv_xcd_remap, 1);   // 0 = plain blockIdx order
 #ifdef DCL_CONV_STAMPS

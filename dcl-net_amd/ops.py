@@ -1067,6 +1067,8 @@ def linear_rowdot(x, Wt, bias, w3, b3, out=None):
     if out is None:
         out = torch.empty((M, 1), dtype=torch.float32, device=x.device)
     assert out.is_contiguous() and out.numel() == M
+    if M == 0:                                              # (an empty tensor has no address to pass)
+        return out
     pitch = lambda t: int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))   # noqa: E731
     N.check(N.lib().dcl_linear_rowdot_fwd(N.ptr(x), C.c_int64(pitch(x)), N.ptr(Wt), C.c_int64(pitch(Wt)), N.ptr(bias), N.ptr(w3),
                                           C.c_int64(int(w3.stride(0))), N.ptr(b3), N.ptr(out), int(M), int(n), int(K), N.stream()),
@@ -1158,6 +1160,8 @@ def linear_split_rowdot(x, sw, bias, w3, b3, out=None):
     if out is None:
         out = torch.empty((M, 1), dtype=torch.float32, device=x.device)
     assert out.is_contiguous() and out.numel() == M
+    if M == 0:                                              # (an empty tensor has no address to pass)
+        return out
     pitch = lambda t: int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))   # noqa: E731
     N.check(N.lib().dcl_linear_split_rowdot_fwd(N.ptr(x), C.c_int64(pitch(x)), N.ptr(sw.planes), N.ptr(bias), N.ptr(w3),
                                                 C.c_int64(int(w3.stride(0))), N.ptr(b3), N.ptr(out), int(M), int(n), int(K), N.stream()),

@@ -523,7 +523,14 @@ int dcl_linear_rowdot_fwd(const float *x, int64_t ldx, const float *Wt, int64_t 
  * kernel's tile order, into `planes` (dcl_linear_split_weight_bytes(K, N) bytes, 16-byte aligned; 0 = K is no multiple of 16).
  * dcl_linear_split_fwd / _pool_fwd / _rowdot_fwd then mirror dcl_linear_dma_fwd / dcl_linear_pool_fwd / dcl_linear_rowdot_fwd with
  * `planes` in the place of (Wt, ldw); x 16-byte aligned, ldx % 4 == 0, K % 16 == 0; workgroup tiles of 256 rows x 128 columns: for
- * launches of at least a few hundred tiles (the fp32-MFMA core keeps the rest). */
+ * launches of at least a few hundred tiles (the fp32-MFMA core keeps the rest).
+ * Error: against exact arithmetic an output is off by at most 1.5 x what a k-ordered fp32 FMA chain is off by on the same
+ * operands, both in units of 2^-24 (sum_k |x_k| |w_k| + |bias|) (a row with s non-zeros: at most 6 s + 2 units); the pooling and
+ * row-dot epilogues add 66 and 10 units of their own sums' magnitudes (tests/test_gpu_split_arithmetic.py).
+ * Range: operands of magnitude < 2^-110 lose up to 2^-126 |w| (|x|) per product (third pieces below the bf16 range).  NOT
+ * supported: |v| >= 3.3962e38 (bits 0x7F7F8000: finite in fp32, inf as a bf16 first piece), +-inf and NaN -- every output of such a
+ * row of x (column of Wt) is NaN, also where the fp32 core gives +-inf, and 0 behind a ReLU epilogue; every other row and column
+ * of the launch has exactly the bits it has without that value. */
 int64_t dcl_linear_split_weight_bytes(int K, int N);
 int dcl_linear_split_weight(const float *Wt, int64_t ldw, int K, int N, void *planes, dclStream_t stream);
 int dcl_linear_split_fwd(const float *x, int64_t ldx, const void *planes, const float *bias, float *y, int64_t ldy, int M, int N,
@@ -709,7 +716,7 @@ int dcl_profile_conv_end(double *ms_total_host, int32_t *calls_host);
 int dcl_profile_conv_end_calls(double *ms_total_host, int32_t *calls_host, float *ms_per_call_host, int32_t *what_per_call_host,
                                int32_t cap);
 
-/* ---- DIAGNOSTIC library only (csrc/Makefile `make diag` -> tests/_diag/libdclnet_hip_diag.so, built with -DDCL_DIAG) ----
+/* ---- DIAGNOSTIC library only (csrc/Makefile `make diag` -> tools/_bin/libdclnet_hip_diag.so, built with -DDCL_DIAG) ----
  * The dcl_debug_* entry points are TEST / TUNING hooks, not part of the operator API and NOT exported by the product library
  * libdclnet_hip.so (where every switch is a compile-time constant and the superseded kernel variants are not compiled):
  * each sets one process-wide atomic switch that later calls from any thread read (A/B kernel variants in tests, tuning

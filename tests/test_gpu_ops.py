@@ -16,7 +16,7 @@ def cuda(a, dtype=None):
 
 
 def enter_diag(dcl, request):
-    """switch the package to the DIAGNOSTIC library (tests/_diag/libdclnet_hip_diag.so, built with -DDCL_DIAG: the product
+    """switch the package to the DIAGNOSTIC library (tools/_bin/libdclnet_hip_diag.so, built with -DDCL_DIAG: the product
     library exports no dcl_debug_* hook and carries no superseded kernel variant) until the test ends; returns its handle"""
     ctx = dcl._native.diagnostic_library()
     lib = ctx.__enter__()
@@ -133,7 +133,7 @@ def test_sparse_conv_matches_oracle(request, dcl, oracle, cin, cout, subm):
     tol = 2e-5 * max(1.0, np.abs(want).max())                  # fp32, different summation association
     assert np.abs(got - want).max() <= tol
     # MFMA kernel vs plain VALU kernel on the device (A/B)
-    lib = enter_diag(dcl, request)      # kernel variants live in the diagnostic library only (tests/_diag)
+    lib = enter_diag(dcl, request)      # kernel variants live in the diagnostic library only (tools/_bin)
     for mode in (1, 2, 4, 5):                                  # 1: VALU, 2: MFMA no LDS, 4: reg-staged tiles, 5: 4-wave 128x64
         lib.dcl_debug_force_valu_conv(mode)
         try:
@@ -238,7 +238,7 @@ def test_sparse_conv_split_k_in_launch_combine(request, dcl, oracle, cin, cout, 
     tol = 2e-5 * max(1.0, np.abs(want).max())
     f, Wd = cuda(feat), cuda(W).reshape(27, cin, cout).contiguous()
     s_, t_ = cuda(rng.uniform(0.5, 1.5, cout).astype(np.float32)), cuda(rng.normal(size=cout).astype(np.float32))
-    lib = enter_diag(dcl, request)      # kernel variants live in the diagnostic library only (tests/_diag)
+    lib = enter_diag(dcl, request)      # kernel variants live in the diagnostic library only (tools/_bin)
     res = {}
     try:
         for ns in (-2, 2, 5, 8, 0):                      # -2: never split ... 0: the automatic choice
@@ -280,7 +280,7 @@ def test_sparse_conv_decompositions_agree_across_sizes(request, dcl, cin, cout):
     Cin 16 / 32 -> 32 channels once a launch is not a few-row one); every one must agree with the plain VALU kernel on the
     same rulebook, with and without the BN+ReLU epilogue -- and the filter-resident kernel with the LDS-DMA kernel it replaces"""
     rng = np.random.default_rng(cin)
-    lib = enter_diag(dcl, request)      # kernel variants live in the diagnostic library only (tests/_diag)
+    lib = enter_diag(dcl, request)      # kernel variants live in the diagnostic library only (tools/_bin)
     W = cuda((rng.normal(size=(27, cin, cout)) / np.sqrt(9 * cin)).astype(np.float32))
     s_, t_ = cuda(rng.uniform(0.5, 1.5, cout).astype(np.float32)), cuda(rng.normal(size=cout).astype(np.float32))
     for b, S, per in ((1, 8, 130), (2, 16, 900), (6, 16, 1500), (8, 32, 5000)):
@@ -808,7 +808,7 @@ def test_cross_attention_matches_fp64(request, dcl, b, nq, nk, scale):
     V1 = torch.randn(b, nk, 256, generator=g).cuda()
     V2 = torch.randn(b, nk, 64, generator=g).cuda()
     want = _attn_ref(Q, K, torch.cat([V1, V2], 2))
-    lib = enter_diag(dcl, request)      # kernel variants live in the diagnostic library only (tests/_diag)
+    lib = enter_diag(dcl, request)      # kernel variants live in the diagnostic library only (tools/_bin)
     for variant in (0, 1, 2, 3, 4):            # auto, shared-tile 8-wave, register-staged 4-wave, LDS-DMA 8 / 4 waves
         O1 = torch.empty(b * nq, 256, device="cuda")
         O2 = torch.empty(b * nq, 64, device="cuda")
@@ -833,7 +833,7 @@ def test_cross_attention_forced_rescale(request, dcl):
     K[0, 300] = Q[0, 40] * 5.0
     V = torch.randn(b, nk, 64, generator=g)
     want = _attn_ref(Q, K, V)[0]
-    lib = enter_diag(dcl, request)      # kernel variants live in the diagnostic library only (tests/_diag)
+    lib = enter_diag(dcl, request)      # kernel variants live in the diagnostic library only (tools/_bin)
     for variant in (1, 2):
         O = torch.empty(b * nq, 64, device="cuda")
         lib.dcl_debug_attention_variant(variant)
@@ -855,7 +855,7 @@ def test_cross_attention_key_split(request, dcl):
     K[1, 1010] = Q[1, 199] * 6.0
     V1, V2 = torch.randn(b, nk, 256, generator=g), torch.randn(b, nk, 64, generator=g)
     want = _attn_ref(Q, K, torch.cat([V1, V2], 2))
-    lib = enter_diag(dcl, request)      # kernel variants live in the diagnostic library only (tests/_diag)
+    lib = enter_diag(dcl, request)      # kernel variants live in the diagnostic library only (tools/_bin)
     Kd, V1d, V2d = K.cuda().reshape(-1, 64), V1.cuda().reshape(-1, 256), V2.cuda().reshape(-1, 64)
     try:
         for variant in (0, 3):                     # 4-wave kernel (small launch) and the 8-wave one (badly quantised grids)
@@ -900,7 +900,7 @@ def test_cross_attention_dma_variant_ragged_and_rescale(request, dcl):
     K[1, 1012] = Q[1, 299] * 6.0                      # spike in the very last (partial) tile
     V1, V2 = torch.randn(b, nk, 256, generator=g), torch.randn(b, nk, 64, generator=g)
     want = _attn_ref(Q, K, torch.cat([V1, V2], 2))
-    lib = enter_diag(dcl, request)      # kernel variants live in the diagnostic library only (tests/_diag)
+    lib = enter_diag(dcl, request)      # kernel variants live in the diagnostic library only (tools/_bin)
     O1 = torch.empty(b * nq, 256, device="cuda")
     O2 = torch.empty(b * nq, 64, device="cuda")
     lib.dcl_debug_attention_variant(3)
@@ -1514,7 +1514,7 @@ def test_backbone_feature_stage_of_both_sides_in_one_launch_sequence(dcl, oracle
 def test_geometry_one_launch_mask_chain_equals_chained_launches(request, dcl):
     """the 8 active sets of a pass from the one-workgroup-per-crop LDS chain (default on 64^3 grids) and from the 8 chained
     mask launches: same counts, same voxel rows at every level -- on the awkward sets and on a 32-crop batch"""
-    lib = enter_diag(dcl, request)      # kernel variants live in the diagnostic library only (tests/_diag)
+    lib = enter_diag(dcl, request)      # kernel variants live in the diagnostic library only (tools/_bin)
     rng = np.random.default_rng(23)
     occ_e, b_e = _edge_voxels(rng)
     data = dcl.synth.make_batch(32, 1024, 64, first=3)
@@ -1604,7 +1604,7 @@ def test_point_neighbours_grid_search_is_exact(request, dcl, scales, unit):
         q.append(np.c_[np.full(20, bi), rng.uniform(-0.5, 0.5, (20, 3))])                               # partly outside the grid
     q.append(np.c_[np.array([-1.0, b, 0.5, np.nan]), np.zeros((4, 3))])                                 # crop ids that match nothing
     pb4 = cuda(np.concatenate(q).astype(np.float32))
-    lib = enter_diag(dcl, request)      # kernel variants live in the diagnostic library only (tests/_diag)
+    lib = enter_diag(dcl, request)      # kernel variants live in the diagnostic library only (tools/_bin)
     res = {}
     try:
         for mode in (0, 1, 2, 3, 4, 5):              # scan / automatic / forced fallback / 1, 4, 8 lanes per query
@@ -1636,7 +1636,7 @@ def test_split_bf16_gemm_core_matches_float64_like_the_fp32_core(dcl):
     fp32 core's tolerance), ragged row counts, column counts that are no multiple of a tile, a lone output column, operands and
     outputs that are column blocks of wider buffers (neighbours untouched), values spread over many binades, exact zeros"""
     g = torch.Generator().manual_seed(33)
-    worst = 0.0
+    worst, where = 0.0, None
     for M, K, n in ((1000, 256, 64), (4096, 480, 1024), (37, 128, 1), (2048, 512, 512), (333, 512, 96), (517, 256, 256), (129, 16, 260),
                     (70000, 48, 130)):
         wide = torch.randn(M, K + 40, generator=g) * torch.exp2(torch.randint(-6, 7, (M, 1), generator=g).float())
@@ -1656,12 +1656,19 @@ def test_split_bf16_gemm_core_matches_float64_like_the_fp32_core(dcl):
             if K % 32 == 0:
                 ref = dcl.ops.linear_dma(x, dcl.ops.pad_linear_weight(Wt), bias if with_bias else None, relu)
                 err32 = float((ref.double() - want).abs().max())
-                worst = max(worst, err / max(err32, 1e-30))
+                ratio = err / max(err32, 1e-30)
+                print("split-arithmetic\texisting gemm ratio M=%d K=%d N=%d relu=%d\tratio=%.3f" % (M, K, n, relu, ratio))
+                if ratio > worst:
+                    worst, where = ratio, (M, K, n, relu)
             buf = torch.full((M, n + 24), 7.0).cuda()
             dcl.ops.linear_split(x, sw, bias if with_bias else None, relu, out=buf[:, 16:16 + n])
             assert torch.equal(buf[:, 16:16 + n], got)
             assert bool((buf[:, :16] == 7.0).all()) and bool((buf[:, 16 + n:] == 7.0).all())
-    assert worst <= 4.0, "split-bf16 errors against float64 should be the size of the fp32 core's: worst ratio %.2f" % worst
+    print("split-arithmetic\texisting gemm ratio\tworst=%.3f at (M, K, N, relu)=%s" % (worst, where))
+    # measured 2.725 (profiles/split_arithmetic.txt) x 1.25.  Above 1.5 because the yardstick here is the fp32-MFMA core, whose own
+    # error is a third to a half of a k-ordered fp32 chain's; against that chain the split core measures <= 1.16 (same file)
+    assert worst <= 3.41, "split-bf16 errors against float64 should be the size of the fp32 core's: worst ratio %.2f at " \
+        "(M, K, N, relu) = %s" % (worst, where)
     with pytest.raises(AssertionError):
         dcl.ops.SplitWeight(torch.zeros(40, 64).cuda())                                # K % 16 != 0
 
@@ -1692,7 +1699,7 @@ def test_cross_attention_split_bf16_form_matches_float64_like_the_fp32_form(requ
     a forced key split (partial records + combine), V2 aliasing K as in the forward; errors of the same size"""
     lib = enter_diag(dcl, request)
     lib.dcl_debug_attention_variant(3)                                   # the 8-wave form whatever the size
-    worst = 0.0
+    worst, where = 0.0, None
     try:
         for b, nq, nk, scale, split in ((2, 256, 256, 1.0, 0), (1, 200, 500, 1.0, 0), (3, 64, 96, 6.0, 0), (1, 1000, 132, 0.3, 0),
                                         (2, 300, 1029, 1.0, 0), (2, 300, 1029, 1.0, 4), (1, 96, 320, 1.0, 0)):
@@ -1718,12 +1725,18 @@ def test_cross_attention_split_bf16_form_matches_float64_like_the_fp32_form(requ
                 errs[bf16] = float((got - want).abs().max())
                 assert errs[bf16] <= tol, (b, nq, nk, split, bf16, errs[bf16], tol)
                 assert bool((O1[:, 256:] == 7.0).all())
-            worst = max(worst, errs[1] / max(errs[0], 1e-30))
+            ratio = errs[1] / max(errs[0], 1e-30)
+            print("split-arithmetic\texisting attention ratio b=%d nq=%d nk=%d split=%d\tratio=%.3f" % (b, nq, nk, split, ratio))
+            if ratio > worst:
+                worst, where = ratio, (b, nq, nk, split)
     finally:
         lib.dcl_debug_attention_variant(0)
         lib.dcl_debug_attention_bf16(1)
         lib.dcl_debug_attention_split(0)
-    assert worst <= 4.0, "split-bf16 attention errors against float64 should be the size of the fp32 form's: worst ratio %.2f" % worst
+    print("split-arithmetic\texisting attention ratio\tworst=%.3f at (b, nq, nk, split)=%s" % (worst, where))
+    # measured 1.591 (profiles/split_arithmetic.txt) x 1.25; a ratio of two maxima over different outputs, each a few units
+    assert worst <= 1.99, "split-bf16 attention errors against float64 should be the size of the fp32 form's: worst ratio %.2f at " \
+        "(b, nq, nk, split) = %s" % (worst, where)
 
 
 def test_v_stack_written_as_attention_pieces_equals_the_piece_pass(request, dcl):

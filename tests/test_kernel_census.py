@@ -2,7 +2,7 @@
 bench numbers and roofline fractions are quoted on -- must have been LAUNCHED by a test that compares its results with the
 oracle or a reference-generated fixture.
 
-The diagnostic library (tests/_diag/libdclnet_hip_diag.so, same sources as the product, -DDCL_DIAG) counts every launch by
+The diagnostic library (tools/_bin/libdclnet_hip_diag.so, same sources as the product, -DDCL_DIAG) counts every launch by
 kernel, template arguments included (csrc/common.h: launch census).  This test switches the package to that library, runs
 the oracle-comparing tests that mirror the profiled workloads -- the same shapes, so the same template instances and the
 same size-dependent kernel choices -- and then reads profiles/<round>_*_kernel_stats.csv: a library kernel named there that

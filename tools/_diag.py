@@ -1,4 +1,4 @@
-"""tools/ only: route the package's ops through the DIAGNOSTIC library (tests/_diag/libdclnet_hip_diag.so, `make -C
+"""tools/ only: route the package's ops through the DIAGNOSTIC library (tools/_bin/libdclnet_hip_diag.so, `make -C
 dcl-net_amd/csrc diag`; DCL_HIP_LIB=<path> picks another diagnostic build, e.g. the stamps library) -- the product library has no
 dcl_debug_* hooks.  The environment switches below are read here, in the tool, never by the product."""
 import os

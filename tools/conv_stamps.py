@@ -2,7 +2,7 @@
 """Where the workgroups of ONE LDS-DMA sparse-conv launch of the backbone runner spend their time (the runner's own launches:
 implicit rulebooks, both backbones grouped or one side).  Needs the stamps library (make -C dcl-net_amd/csrc stamps:
 in-kernel s_memrealtime stamps, 100 MHz ticks, 8 per segment of a workgroup).
-usage: DCL_HIP_LIB=tests/_diag/libdclnet_hip_stamps.so tools/conv_stamps.py [launch 0-5] [pair|inp|tmp] [ref|stress] [b]
+usage: DCL_HIP_LIB=tools/_bin/libdclnet_hip_stamps.so tools/conv_stamps.py [launch 0-5] [pair|inp|tmp] [ref|stress] [b]
 launch = index among the LDS-DMA launches of a feature stage: 0 L1 conv 32->32 (pair only), 1 L1 subm 32->64, 2 L2 conv,
 3 L2 subm, 4 L3 conv, 5 L3 subm (one side: L1 conv runs the filter-resident kernel, so 0 = L1 subm, ...)."""
 import ctypes, importlib, os, sys
@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 dcl = importlib.import_module("dcl-net_amd")
 from _diag import use_diag
-os.environ.setdefault("DCL_HIP_LIB", os.path.join(ROOT, "tests", "_diag", "libdclnet_hip_stamps.so"))
+os.environ.setdefault("DCL_HIP_LIB", os.path.join(ROOT, "tools", "_bin", "libdclnet_hip_stamps.so"))
 DIAG = use_diag(dcl)
 ops = dcl.ops
 sel = int(sys.argv[1]) if len(sys.argv) > 1 else 1
