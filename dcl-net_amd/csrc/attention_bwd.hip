@@ -22,11 +22,10 @@
 // registers instead of 192.  k_attn_bwd_stats adds the two 32-channel chains of S in the same order, so the exponent
 // S - lse is formed from the same bits in all three kernels.
 #include "common.h"
+#include "mfma_tile.h"
 #include <math.h>
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kDK = 64, kDV1 = 256, kDV2 = 64, kDV = kDV1 + kDV2;
 constexpr int kRowF4 = (kDK + kDV) / 4;                 // float4 per streamed row: 96
@@ -34,9 +33,6 @@ constexpr int kPitch = kDK + kDV + 4;                   // floats per row of the
 constexpr int kTileFloats = 32 * kPitch;
 constexpr int kXchFloats = 4 * 8 * 64 * 4;              // per wave: 8 float4 (partial S, partial dP) per lane
 constexpr size_t kSweepLds = (size_t)(2 * kTileFloats + kXchFloats) * sizeof(float);
-
-// accumulator register e of lane half h holds row rowmap(e, h) of a 32x32 MFMA result (column = lane & 31)
-__device__ __forceinline__ int rowmap(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
 
 __device__ __forceinline__ float f4at(const float4 &v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
 
@@ -279,13 +275,13 @@ __global__ __launch_bounds__(256, 1) void k_attn_bwd_sweep(int nf, int ns, int n
       const float *tcol = cur + 4 * h * kPitch + r;
 #pragma unroll
       for (int e = 0; e < 16; ++e)
-        acc64 = __builtin_amdgcn_mfma_f32_32x32x2f32(tcol[((e & 3) + 8 * (e >> 2)) * kPitch + 32 * p], dS[e], acc64, 0, 0, 0);
+        acc64 = __builtin_amdgcn_mfma_f32_32x32x2f32(tcol[rowmap(e, 0) * kPitch + 32 * p], dS[e], acc64, 0, 0, 0);
       if (KEYS_FIXED) {
 #pragma unroll
         for (int tt = 0; tt < 5; ++tt) {
 #pragma unroll
           for (int e = 0; e < 16; ++e)
-            acc320[tt] = __builtin_amdgcn_mfma_f32_32x32x2f32(tcol[((e & 3) + 8 * (e >> 2)) * kPitch + kDK + 160 * p + 32 * tt],
+            acc320[tt] = __builtin_amdgcn_mfma_f32_32x32x2f32(tcol[rowmap(e, 0) * kPitch + kDK + 160 * p + 32 * tt],
                                                               P[e], acc320[tt], 0, 0, 0);
         }
       }

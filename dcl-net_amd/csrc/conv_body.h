@@ -4,10 +4,9 @@
 // (models/Modules.py:153-159).
 #pragma once
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // offset visiting order: reference adds the centre GEMM first for subm, then k ascending.
 __device__ __forceinline__ int offset_at(int step, int kvol, int subm) {
@@ -322,7 +321,7 @@ __device__ __forceinline__ void conv_wlds_body(const DclConvSides &sides, int ns
     const bool have_scale = Se.scale != nullptr;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const int orow = tile * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+      const int orow = tile * 32 + rowmap(e, h);
       if (orow < n) {
         float x = acc[e];
         if (have_scale) x = x * sc + sh;
@@ -340,42 +339,10 @@ __device__ __forceinline__ void conv_wlds_body(const DclConvSides &sides, int ns
 // contiguous LDS, bank conflicts are avoided by swizzling instead of padding: the 16-B column c of row r is stored at
 // column c ^ (r & 15) (A), and W rows with bit 2 of their index set swap their 32-column halves (B).
 __device__ float4 g_conv_zero_line = {0.f, 0.f, 0.f, 0.f};
-typedef __attribute__((address_space(3))) void conv_lds_void_t;
-__device__ __forceinline__ void conv_glds16(const void *gsrc, unsigned lds_byte_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(lds_byte_addr)
-               : "memory");
-}
-// N pieces whose LDS destinations are 1 KiB apart, ONE M0 value: the destination of piece i is the instruction's offset
-// field (i * 1024), which the hardware adds to the GLOBAL address as well -- the caller's source pointer of piece i is
-// pre-decremented by i * 1024 bytes.  One wave pays ~45 cycles per piece for this form against ~58 for an M0 write per
-// piece (tools/ubench_glds.hip; four waves issuing at once: 83 against 119).
-template <int N>
-__device__ __forceinline__ void conv_glds16_group(const float *const *gsrc, unsigned lds_byte_addr) {
-  static_assert(N == 1 || N == 2 || N == 4, "pieces per group");
-  unsigned keep;
-  if constexpr (N == 1)
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc[0]), "s"(lds_byte_addr) : "memory");
-  else if constexpr (N == 2)
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-                 "global_load_lds_dwordx4 %2, off offset:1024\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc[0]), "v"(gsrc[1]), "s"(lds_byte_addr) : "memory");
-  else
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-                 "global_load_lds_dwordx4 %2, off offset:1024\n\tglobal_load_lds_dwordx4 %3, off offset:2048\n\t"
-                 "global_load_lds_dwordx4 %4, off offset:3072\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc[0]), "v"(gsrc[1]), "v"(gsrc[2]), "v"(gsrc[3]), "s"(lds_byte_addr) : "memory");
-}
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // 16-B write-through (sc1) store: the payload of an in-launch hand-off (cdna_hip_programming.md Guideline 16, R1)
 __device__ __forceinline__ void conv_store16_wt(f32x4 *p, f32x4 v) {
   asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
-}
-__device__ __forceinline__ unsigned conv_lds_addr(const float *p) {
-  return __builtin_amdgcn_readfirstlane((unsigned)(size_t)(conv_lds_void_t *)p);
 }
 
 // Tile shape: WR x WCW waves, each 32 rows x (32*NT) channels => BM = 32*WR rows, BN = 32*NT*WCW channels per workgroup,
@@ -431,10 +398,7 @@ __device__ __forceinline__ void conv_dma_body(
   // workgroups sharing an XCD (= one L2) hold neighbouring unit ranges (column tiles of a row tile, neighbouring row
   // tiles, whose gathered input rows overlap) -- not in capacity mode, where the live work occupies the low ids only
   int wid = wid_in;
-  if (xcd_remap && sides.s[0].n_dev == nullptr) {
-    const int xq = G >> 3, xr = G & 7, xcd = wid & 7;
-    wid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (wid >> 3);
-  }
+  if (xcd_remap && sides.s[0].n_dev == nullptr) wid = xcd_first(wid, G) + (wid >> 3);
   const int nblk0 = (n0 + BM - 1) / BM, nblk1 = (n1 + BM - 1) / BM, ncol = cout / BN;
   const int C = (kvol * CIN + KC - 1) / KC;                    // chunks per tile
   // (32-bit unit arithmetic: tiles * C < 2^31 for every launch the host code makes -- 64-bit divisions would cost
@@ -642,7 +606,7 @@ __device__ __forceinline__ void conv_dma_body(
       }
     };
     // prep(j): the global source of every DMA piece of chunk j (registers), piece i of a group of GRP pieces pre-decremented
-    // by i KiB (conv_glds16_group); fire_all(stage): the chunk's pieces go out, W first (their sources are ready first).
+    // by i KiB (glds16_group); fire_all(stage): the chunk's pieces go out, W first (their sources are ready first).
     constexpr int NPIECE = A_PER + B_PER;
     constexpr int AGRP = A_PER >= 4 ? 4 : A_PER, BGRP = B_PER >= 4 ? 4 : B_PER;
     static_assert(A_PER % AGRP == 0 && B_PER % BGRP == 0 && (AGRP == 1 || AGRP == 2 || AGRP == 4) && (BGRP == 1 || BGRP == 2 || BGRP == 4), "DMA groups");
@@ -689,9 +653,9 @@ __device__ __forceinline__ void conv_dma_body(
     auto fire_all = [&](int stage) {
       float *As = conv_lds + stage * ST, *Bs = As + AT;
 #pragma unroll
-      for (int g = 0; g < B_PER; g += BGRP) conv_glds16_group<BGRP>(psrc + A_PER + g, conv_lds_addr(Bs + (iwave * B_PER + g) * 256));
+      for (int g = 0; g < B_PER; g += BGRP) glds16_group<BGRP>(psrc + A_PER + g, lds_addr(Bs + (iwave * B_PER + g) * 256));
 #pragma unroll
-      for (int g = 0; g < A_PER; g += AGRP) conv_glds16_group<AGRP>(psrc + g, conv_lds_addr(As + (iwave * A_PER + g) * 256));
+      for (int g = 0; g < A_PER; g += AGRP) glds16_group<AGRP>(psrc + g, lds_addr(As + (iwave * A_PER + g) * 256));
     };
     // steps under which at least one of THIS WAVE's 32 rows has a neighbour (wave-level skip of a chunk's MFMA block)
     const unsigned wsmask = __builtin_amdgcn_readfirstlane(steps_of(s_kmask[wr]));
@@ -870,7 +834,7 @@ __device__ __forceinline__ void conv_dma_body(
           const float sh = scale ? shift[co] : 0.0f;
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
-            const int slot = wr * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int slot = wr * 32 + rowmap(e, h);
             const int orow = ordered ? s_rows[slot] : (row0 + slot < n ? row0 + slot : -1);
             if (orow >= 0) {
               float x = acc[t][e];
@@ -897,7 +861,7 @@ __device__ __forceinline__ void conv_dma_body(
       const float sh = scale ? shift[co] : 0.0f;
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int slot = wr * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        const int slot = wr * 32 + rowmap(e, h);
         const int orow = ordered ? s_rows[slot] : (row0 + slot < n ? row0 + slot : -1);
         if (orow >= 0) {
           float x = acc[t][e];

@@ -14,18 +14,15 @@
 // and one final division by the softmax denominator.  Bound: fp32 MFMA (157 TFLOP/s spec);
 // algorithmic flop = 2*(dk+dv)*Nq*Nk per crop per direction.
 #include "common.h"
+#include "mfma_tile.h"
 #include "ortho9d.h"
 #include <atomic>
 #include <math.h>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kKPitch = 68;        // floats per key row of the K tile in LDS: 64 ch + 4 pad (b128 conflict-free)
 constexpr float kThr = 20.0f;      // lazy-rescale threshold (e^20 ~ 5e8: far inside fp32 range)
-
-__device__ __forceinline__ int rowmap(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
 
 #ifdef DCL_DIAG   // general-shape predecessors of k_cross_attn_dma: diagnostic library only (A/B references)
 // All operands POINT-major: X[(b*n + p)*ld + c]  (the layout the 3-NN interpolation produces and the
@@ -161,7 +158,7 @@ __global__ __launch_bounds__(256, 1) void k_cross_attn(
       const float *vcol = Vs + t * 32 + r + 4 * h * DV;
 #pragma unroll
       for (int e = 0; e < 16; ++e)
-        O[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(vcol[((e & 3) + 8 * (e >> 2)) * DV], S[e], O[t], 0, 0, 0);
+        O[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(vcol[rowmap(e, 0) * DV], S[e], O[t], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);                  // keep the LDS reads of tile t+1.. from piling up in VGPRs
     }
     if (more) stage_write(attn_lds + (cur ^ 1) * TILE);
@@ -294,7 +291,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES >= 8 ? 2 : 1) void k_cross_attn_s
       const float *vcol = Vs + t * 32 + r + 4 * h * DV;
 #pragma unroll
       for (int e = 0; e < 16; ++e)
-        O[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(vcol[((e & 3) + 8 * (e >> 2)) * DV], S[e], O[t], 0, 0, 0);
+        O[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(vcol[rowmap(e, 0) * DV], S[e], O[t], 0, 0, 0);
     }
   }
 
@@ -325,29 +322,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES >= 8 ? 2 : 1) void k_cross_attn_s
 // Two barriers per tile as before, but no global-memory latency between them:
 //   A (__syncthreads: drains this wave's DMA + K write)  ->  issue DMA V(t+1)  ->  S = K Q^T, softmax
 //   B (raw s_barrier, lgkmcnt only: K tile free)         ->  load K(t+1)       ->  O += V^T P  ->  write K(t+1)
-typedef __attribute__((address_space(3))) void lds_void_t;
 constexpr int kAttnPartPitch = 324;                // floats per (key split, query) partial record: 320 channels, m, l, pad
-
-// One LDS-DMA wave-instruction: 64 lanes x 16 B from per-lane global addresses to LDS at (wave-uniform) lds_byte_addr +
-// lane*16.  Inline asm on purpose: issued through the builtin, hipcc drains it (vmcnt(0)) before the next ds_read of the
-// same LDS array, which would serialise the pipeline; an asm load is not in the compiler's counters, so the kernel waits
-// for it itself (s_waitcnt vmcnt(0) before barrier A).  M0 is saved/restored inside the statement (guide section 5.7).
-__device__ __forceinline__ void glds16(const void *gsrc, unsigned lds_byte_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(lds_byte_addr)
-               : "memory");
-}
-// the same with the source as (wave-uniform base in an SGPR pair) + (per-lane 32-bit byte offset): no vector address arithmetic
-__device__ __forceinline__ void glds16_s(unsigned voff, const void *sbase, unsigned lds_byte_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_byte_addr) : "memory");
-}
-__device__ __forceinline__ unsigned lds_addr_of(const float *p) {
-  return __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_void_t *)p);
-}
 
 template <int WAVES>
 __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void k_cross_attn_dma(
@@ -368,8 +343,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void k_cross_attn_dma(
   int bx, b;
   {
     const int nwg = gridDim.x * gridDim.y, id = blockIdx.x + gridDim.x * blockIdx.y;
-    const int xq = nwg >> 3, xr = nwg & 7, xcd = id & 7;
-    const int swz = !xcd_remap ? id : (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (id >> 3);
+    const int swz = !xcd_remap ? id : xcd_first(id, nwg) + (id >> 3);
     bx = swz % (int)gridDim.x;
     b = swz / (int)gridDim.x;
   }
@@ -396,13 +370,13 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void k_cross_attn_dma(
     for (int i = 0; i < RPW; ++i) {
       const int key = wave * RPW + i;
       const float *src = V1 + (krow0 + min(kb + key, last_key)) * ldv1 + lane * 4;
-      glds16(src, lds_addr_of(V1s + buf * V1T + key * 256));
+      glds16(src, lds_addr(V1s + buf * V1T + key * 256));
     }
 #pragma unroll
     for (int i = 0; i < RPW / 4; ++i) {
       const int key2 = wave * RPW + i * 4 + (lane >> 4);
       const float *src2 = V2 + (krow0 + min(kb + key2, last_key)) * ldv2 + (lane & 15) * 4;
-      glds16(src2, lds_addr_of(V2s + buf * V2T + (wave * RPW + i * 4) * 64));
+      glds16(src2, lds_addr(V2s + buf * V2T + (wave * RPW + i * 4) * 64));
     }
   };
   // this thread's float4(s) of the K tile: 512 per tile over WAVES*64 threads
@@ -501,7 +475,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void k_cross_attn_dma(
     for (int t = 0; t < NVT; ++t) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int krow = (e & 3) + 8 * (e >> 2);
+        const int krow = rowmap(e, 0);
         const float a = t < 8 ? v1b[krow * 256 + t * 32] : v2b[krow * 64 + (t - 8) * 32];
         O[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, S[e], O[t], 0, 0, 0);
       }
@@ -549,33 +523,9 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void k_cross_attn_dma(
 // split in registers every tile: as pieces it would take 96 KiB of LDS or 48 registers.  P = exp(S - m) is split in registers once
 // per tile and wave; the S accumulators become the B operand of P.V as before, piece by piece.  Per 32-key tile and wave: 24 + 120
 // bf16 MFMAs (4608 cycles) against 192 fp32 MFMAs (12288).  The sweep's structure is described at k_cross_attn_split.
-typedef __bf16 at_bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 at_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float at_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned at_u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kAttnHalfBytes = 3 * 320 * 2 * 16;   // one 16-key half tile of V pieces: [piece][channel][lane half][8 keys] bf16 = 30 KiB
 constexpr int kAttnKTileBytes = 3 * 32 * 128;      // one 32-key tile of K pieces: [piece][key][8 groups of 8 channels] bf16 = 12 KiB
 constexpr int kAttnTileBytes = 2 * kAttnHalfBytes + kAttnKTileBytes;     // scratch per 32-key tile and crop
-
-__device__ __forceinline__ unsigned at_cvt2(float a, float b) {
-  const at_f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, at_bf16x2));
-}
-__device__ __forceinline__ void at_split2(float x0, float x1, unsigned &h, unsigned &m, unsigned &l) {     // x = h + m + l exactly
-  // (the empty asm statements keep a pair's subtractions scalar: see linear_split.hip, sp_split2)
-  h = at_cvt2(x0, x1);
-  float r0 = x0 - __uint_as_float(h << 16);
-  asm volatile("" : "+v"(r0));
-  float r1 = x1 - __uint_as_float(h & 0xffff0000u);
-  asm volatile("" : "+v"(r1));
-  m = at_cvt2(r0, r1);
-  float s0 = r0 - __uint_as_float(m << 16);
-  asm volatile("" : "+v"(s0));
-  float s1 = r1 - __uint_as_float(m & 0xffff0000u);
-  asm volatile("" : "+v"(s1));
-  l = at_cvt2(s0, s1);
-}
-__device__ __forceinline__ at_bf16x8 at_bf(at_u32x4 v) { return __builtin_bit_cast(at_bf16x8, v); }
 
 // planes[crop][half tile][piece][channel c][slot hs][8] (bf16), slot hs holds lane half h = hs ^ bit 3 of c (bank swizzle), element
 // e = key 16 ht + (e & 3) + 8 (e >> 2) + 4 h; keys >= nk are zeros.  One thread per (crop, half tile, c, hs).
@@ -600,7 +550,7 @@ __global__ __launch_bounds__(256) void k_attn_split_v(int nk, int nht, const flo
     }
     unsigned ph[4], pm[4], pl[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) at_split2(v[2 * e], v[2 * e + 1], ph[e], pm[e], pl[e]);
+    for (int e = 0; e < 4; ++e) bf16_split2(v[2 * e], v[2 * e + 1], ph[e], pm[e], pl[e]);
     unsigned *dst = planes + (size_t)cht * (kAttnHalfBytes / 4) + (size_t)(c * 2 + hs) * 4;
 #pragma unroll
     for (int e = 0; e < 4; ++e) { dst[e] = ph[e]; dst[320 * 2 * 4 + e] = pm[e]; dst[2 * 320 * 2 * 4 + e] = pl[e]; }
@@ -623,10 +573,10 @@ __global__ __launch_bounds__(256) void k_attn_split_k(int nk, int ntiles, const 
       b = *reinterpret_cast<const float4 *>(row + 4);
     }
     unsigned ph[4], pm[4], pl[4];
-    at_split2(a.x, a.y, ph[0], pm[0], pl[0]);
-    at_split2(a.z, a.w, ph[1], pm[1], pl[1]);
-    at_split2(b.x, b.y, ph[2], pm[2], pl[2]);
-    at_split2(b.z, b.w, ph[3], pm[3], pl[3]);
+    bf16_split2(a.x, a.y, ph[0], pm[0], pl[0]);
+    bf16_split2(a.z, a.w, ph[1], pm[1], pl[1]);
+    bf16_split2(b.x, b.y, ph[2], pm[2], pl[2]);
+    bf16_split2(b.z, b.w, ph[3], pm[3], pl[3]);
     unsigned *dst = kplanes + (size_t)ct * (kAttnKTileBytes / 4) + (size_t)(key * 8 + ps) * 4;
 #pragma unroll
     for (int e = 0; e < 4; ++e) { dst[e] = ph[e]; dst[32 * 32 + e] = pm[e]; dst[2 * 32 * 32 + e] = pl[e]; }
@@ -653,8 +603,7 @@ __global__ __launch_bounds__(512, 2) void k_cross_attn_split(
   int bx, b;
   {
     const int nwg = gridDim.x * gridDim.y, id = blockIdx.x + gridDim.x * blockIdx.y;
-    const int xq = nwg >> 3, xr = nwg & 7, xcd = id & 7;
-    const int swz = !xcd_remap ? id : (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (id >> 3);
+    const int swz = !xcd_remap ? id : xcd_first(id, nwg) + (id >> 3);
     bx = swz % (int)gridDim.x;
     b = swz / (int)gridDim.x;
   }
@@ -671,8 +620,8 @@ __global__ __launch_bounds__(512, 2) void k_cross_attn_split(
   const unsigned char *vsrc = planes + (size_t)b * nht * kAttnHalfBytes;             // (wave-uniform: SGPRs)
   const unsigned char *ksrc = kplanes + (size_t)b * (nht >> 1) * kAttnKTileBytes;
   const unsigned lane16 = (unsigned)lane * 16u;
-  const unsigned vp0 = lds_addr_of(reinterpret_cast<const float *>(Vp));
-  const unsigned kp0 = lds_addr_of(reinterpret_cast<const float *>(Kp));
+  const unsigned vp0 = lds_addr(Vp);
+  const unsigned kp0 = lds_addr(Kp);
   // a tile = 12 one-KiB DMA pieces of K pieces + 60 of V pieces: wave w issues K piece w (and w + 8 if w < 4), V pieces w, w + 8, ...
   // (sources = scalar bases + the one per-lane offset: no vector address arithmetic beside the other group's MFMAs)
   auto dma_tile = [&](int tile, int buf) {
@@ -693,11 +642,11 @@ __global__ __launch_bounds__(512, 2) void k_cross_attn_split(
 #pragma unroll
     for (int e = 0; e < 16; ++e) O[t][e] = 0.0f;
   float m_ref = -INFINITY, l_part = 0.0f;
-  at_u32x4 pp[2][3];                               // the current tile's weights as bf16 pieces (S interval -> P.V interval)
+  u32x4 pp[2][3];                               // the current tile's weights as bf16 pieces (S interval -> P.V interval)
 #pragma unroll
   for (int hf = 0; hf < 2; ++hf)
 #pragma unroll
-    for (int p = 0; p < 3; ++p) pp[hf][p] = at_u32x4{0u, 0u, 0u, 0u};
+    for (int p = 0; p < 3; ++p) pp[hf][p] = u32x4{0u, 0u, 0u, 0u};
 
   const int ntiles_all = (nk + 31) >> 5;
   const int t_begin = (int)((long long)blockIdx.z * ntiles_all / gridDim.z);
@@ -726,21 +675,21 @@ __global__ __launch_bounds__(512, 2) void k_cross_attn_split(
         qn1 = *reinterpret_cast<const float4 *>(qrow + 16 * (st + 1) + 4);
       }
       const unsigned char *kf = kfb + (((2 * st + h) ^ ksw) << 4);
-      const at_u32x4 kh = *reinterpret_cast<const at_u32x4 *>(kf);
-      const at_u32x4 km = *reinterpret_cast<const at_u32x4 *>(kf + 32 * 128);
-      const at_u32x4 kl = *reinterpret_cast<const at_u32x4 *>(kf + 2 * 32 * 128);
-      at_u32x4 qh, qm, ql;
+      const u32x4 kh = *reinterpret_cast<const u32x4 *>(kf);
+      const u32x4 km = *reinterpret_cast<const u32x4 *>(kf + 32 * 128);
+      const u32x4 kl = *reinterpret_cast<const u32x4 *>(kf + 2 * 32 * 128);
+      u32x4 qh, qm, ql;
       unsigned a0, a1, a2;
-      at_split2(qc0.x, qc0.y, a0, a1, a2); qh[0] = a0; qm[0] = a1; ql[0] = a2;
-      at_split2(qc0.z, qc0.w, a0, a1, a2); qh[1] = a0; qm[1] = a1; ql[1] = a2;
-      at_split2(qc1.x, qc1.y, a0, a1, a2); qh[2] = a0; qm[2] = a1; ql[2] = a2;
-      at_split2(qc1.z, qc1.w, a0, a1, a2); qh[3] = a0; qm[3] = a1; ql[3] = a2;
-      S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at_bf(kl), at_bf(qh), S, 0, 0, 0);
-      S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at_bf(kh), at_bf(ql), S, 0, 0, 0);
-      S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at_bf(km), at_bf(qm), S, 0, 0, 0);
-      S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at_bf(km), at_bf(qh), S, 0, 0, 0);
-      S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at_bf(kh), at_bf(qm), S, 0, 0, 0);
-      S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at_bf(kh), at_bf(qh), S, 0, 0, 0);
+      bf16_split2(qc0.x, qc0.y, a0, a1, a2); qh[0] = a0; qm[0] = a1; ql[0] = a2;
+      bf16_split2(qc0.z, qc0.w, a0, a1, a2); qh[1] = a0; qm[1] = a1; ql[1] = a2;
+      bf16_split2(qc1.x, qc1.y, a0, a1, a2); qh[2] = a0; qm[2] = a1; ql[2] = a2;
+      bf16_split2(qc1.z, qc1.w, a0, a1, a2); qh[3] = a0; qm[3] = a1; ql[3] = a2;
+      S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(kl), as_bf16x8(qh), S, 0, 0, 0);
+      S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(kh), as_bf16x8(ql), S, 0, 0, 0);
+      S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(km), as_bf16x8(qm), S, 0, 0, 0);
+      S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(km), as_bf16x8(qh), S, 0, 0, 0);
+      S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(kh), as_bf16x8(qm), S, 0, 0, 0);
+      S = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(kh), as_bf16x8(qh), S, 0, 0, 0);
     }
     float m_tile = -INFINITY;
     if (kb + 32 > nk) {                                    // (wave-uniform) the ragged last tile: keys past nk score -inf
@@ -773,7 +722,7 @@ __global__ __launch_bounds__(512, 2) void k_cross_attn_split(
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         unsigned ph, pm, pl;
-        at_split2(S[8 * hf + 2 * e], S[8 * hf + 2 * e + 1], ph, pm, pl);
+        bf16_split2(S[8 * hf + 2 * e], S[8 * hf + 2 * e + 1], ph, pm, pl);
         pp[hf][0][e] = ph; pp[hf][1][e] = pm; pp[hf][2][e] = pl;
       }
   };
@@ -785,15 +734,15 @@ __global__ __launch_bounds__(512, 2) void k_cross_attn_split(
       const unsigned char *vb = vbuf + hf * kAttnHalfBytes;
 #pragma unroll
       for (int t = 0; t < NVT; ++t) {
-        const at_u32x4 vh = *reinterpret_cast<const at_u32x4 *>(vb + t * 1024);
-        const at_u32x4 vm = *reinterpret_cast<const at_u32x4 *>(vb + 320 * 32 + t * 1024);
-        const at_u32x4 vl = *reinterpret_cast<const at_u32x4 *>(vb + 2 * 320 * 32 + t * 1024);
-        O[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at_bf(vl), at_bf(pp[hf][0]), O[t], 0, 0, 0);
-        O[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at_bf(vh), at_bf(pp[hf][2]), O[t], 0, 0, 0);
-        O[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at_bf(vm), at_bf(pp[hf][1]), O[t], 0, 0, 0);
-        O[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at_bf(vm), at_bf(pp[hf][0]), O[t], 0, 0, 0);
-        O[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at_bf(vh), at_bf(pp[hf][1]), O[t], 0, 0, 0);
-        O[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at_bf(vh), at_bf(pp[hf][0]), O[t], 0, 0, 0);
+        const u32x4 vh = *reinterpret_cast<const u32x4 *>(vb + t * 1024);
+        const u32x4 vm = *reinterpret_cast<const u32x4 *>(vb + 320 * 32 + t * 1024);
+        const u32x4 vl = *reinterpret_cast<const u32x4 *>(vb + 2 * 320 * 32 + t * 1024);
+        O[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(vl), as_bf16x8(pp[hf][0]), O[t], 0, 0, 0);
+        O[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(vh), as_bf16x8(pp[hf][2]), O[t], 0, 0, 0);
+        O[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(vm), as_bf16x8(pp[hf][1]), O[t], 0, 0, 0);
+        O[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(vm), as_bf16x8(pp[hf][0]), O[t], 0, 0, 0);
+        O[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(vh), as_bf16x8(pp[hf][1]), O[t], 0, 0, 0);
+        O[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(vh), as_bf16x8(pp[hf][0]), O[t], 0, 0, 0);
       }
     }
   };
@@ -1734,7 +1683,7 @@ __global__ __launch_bounds__(256) void k_mlp128_to1(int M, const float *__restri
     dcl_lds_barrier();                                 // every wave has read the x tile: it becomes the hidden tile
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const int m = (e & 3) + 8 * (e >> 2) + 4 * h;
+      const int m = rowmap(e, h);
       xs[m * kMlpXP + 32 * w + r] = fmaxf(acc[e] + bias1, 0.0f);
     }
     dcl_lds_barrier();

@@ -22,26 +22,12 @@
 // weighted column-sum kernel disappears; dcl_pool_finish adds a crop's tile partials in a fixed order (deterministic).
 #include <hip/hip_runtime.h>
 #include "common.h"
+#include "linear_epilogue.h"
 
 namespace {
 
-typedef float ld_f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void ld_lds_void_t;
-
 constexpr int kLdKC = 32;                                            // k per chunk
 
-__device__ __forceinline__ unsigned ld_lds_addr(const float *p) {
-  return __builtin_amdgcn_readfirstlane((unsigned)(size_t)(ld_lds_void_t *)p);
-}
-// One LDS-DMA piece: 64 lanes x 16 B from (wave-uniform 64-bit base in an SGPR pair) + (per-lane 32-bit byte offset) to LDS at
-// (wave-uniform) lds_byte_addr + lane * 16.  Inline asm on purpose (cdna guide 5.7; dense.hip: glds16): issued through the
-// builtin hipcc drains the DMA before the next ds_read of the array; an asm load is not in the compiler's counters, the
-// kernel waits for it itself.  M0 is saved / restored inside the statement.
-__device__ __forceinline__ void ld_glds16_s(unsigned voff, const float *sbase, unsigned lds_byte_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_byte_addr) : "memory");
-}
 struct LinDmaArgs {
   const float *x, *Wt, *bias;
   float *y;
@@ -55,8 +41,6 @@ struct LinDmaArgs {
   long long ldp;
   int xcd_remap;
 };
-
-__device__ __forceinline__ int ld_rowmap(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
 
 // KS = 2 (launches of few tiles: a handful of crops): EIGHT waves per tile, two groups of four that take the even / the odd
 // 32-deep chunks of K -- a tile's chain of chunks is half as long, which is what a launch that cannot fill the chip is bound
@@ -85,18 +69,7 @@ __global__ __launch_bounds__(256 * KS, KS == 4 ? 4 : 2) void k_linear_dma(const 
   // with stride gridDim / 8 -- the workgroups that share an L2 work on neighbouring tiles of the same row blocks.
   const int ntn = (a.N + BN - 1) / BN, ntm = (a.M + BM - 1) / BM, tiles = ntm * ntn;
   int t_lo, t_hi, t_stride;                                // this workgroup's tiles: t_lo, t_lo + t_stride, ... < t_hi
-  {
-    const int id = blockIdx.x, nwg = gridDim.x;
-    if (a.xcd_remap && (nwg & 7) == 0) {
-      const int xq = tiles >> 3, xr = tiles & 7, xcd = id & 7;
-      const int x_lo = xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq;
-      t_lo = x_lo + (id >> 3);
-      t_hi = x_lo + xq + (xcd < xr ? 1 : 0);
-      t_stride = nwg >> 3;
-    } else {
-      t_lo = id; t_hi = tiles; t_stride = nwg;
-    }
-  }
+  xcd_tile_range(a.xcd_remap, tiles, t_lo, t_hi, t_stride);
   if (t_lo >= t_hi) return;
   const int tid = threadIdx.x, lane = tid & 63, wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int grp = KS == 1 ? 0 : wave8 >> 2, wave = KS == 1 ? wave8 : (wave8 & 3);      // K group, wave inside it
@@ -105,7 +78,7 @@ __global__ __launch_bounds__(256 * KS, KS == 4 ? 4 : 2) void k_linear_dma(const 
   const int kchunks = a.K / kLdKC;                         // 32-deep chunks of K
   const int nchunks = (kchunks + KS - 1) / KS;             // steps of the chunk loop: group g takes chunk step * KS + g
   const long long bchunk = (long long)kLdKC * a.ldw;
-  const unsigned lds0 = ld_lds_addr(ld_lds);
+  const unsigned lds0 = lds_addr(ld_lds);
   const int n4 = (a.N + 3) & ~3;
 
   // ---- the producer: which chunk of which tile is fetched next.  A wave's DMA pieces per chunk: x pieces APW*wave .. (8 rows of
@@ -149,11 +122,11 @@ __global__ __launch_bounds__(256 * KS, KS == 4 ? 4 : 2) void k_linear_dma(const 
   //  nothing and, below, multiplies nothing)
   auto issue_a = [&](int i, int stage) {
     if (KS == 1 || p_chunk * KS + grp < kchunks)
-      ld_glds16_s(aoff[i], abase, lds0 + (unsigned)(((stage * KS + grp) * ST + (APW * wave + i) * 256) * 4));
+      glds16_s(aoff[i], abase, lds0 + (unsigned)(((stage * KS + grp) * ST + (APW * wave + i) * 256) * 4));
   };
   auto issue_b = [&](int i, int stage) {
     if (KS == 1 || p_chunk * KS + grp < kchunks)
-      ld_glds16_s(boff[i], bbase, lds0 + (unsigned)(((stage * KS + grp) * ST + AT + (BPW * wave + i) * 256) * 4));
+      glds16_s(boff[i], bbase, lds0 + (unsigned)(((stage * KS + grp) * ST + AT + (BPW * wave + i) * 256) * 4));
   };
 
   const int sw = (r >> 1) & 7;
@@ -171,7 +144,7 @@ __global__ __launch_bounds__(256 * KS, KS == 4 ? 4 : 2) void k_linear_dma(const 
 #pragma unroll
     for (int q = 0; q < 4; ++q) f.b[n][q] = bcol[(8 * i + q) * BN + n * 32];
   };
-  ld_f32x16 acc[MB][NB];
+  f32x16 acc[MB][NB];
   auto mfma_group = [&](const Frag &f, int q) {
 #pragma unroll
     for (int m = 0; m < MB; ++m) {
@@ -273,65 +246,16 @@ __global__ __launch_bounds__(256 * KS, KS == 4 ? 4 : 2) void k_linear_dma(const 
     }
     if constexpr (EPI == 0) {
       if (KS > 1 && grp > 0) continue;                     // group 0 holds the sums
-      float *__restrict__ y = a.y;
       const bool whole = row0 + BM <= a.M && col0 + BN <= a.N;     // (workgroup-uniform) interior tile: no per-element checks
-      float bias[NB];
-#pragma unroll
-      for (int n = 0; n < NB; ++n) {
-        const int co = col0 + wc * WN + n * 32 + r;
-        bias[n] = (a.bias && co < a.N) ? a.bias[co] : 0.0f;
-      }
-      if (whole) {
-#pragma unroll
-        for (int m = 0; m < MB; ++m)
-#pragma unroll
-          for (int n = 0; n < NB; ++n) {
-            float *yp = y + (size_t)(row0 + wr * WM + m * 32 + 4 * h) * a.ldy + (col0 + wc * WN + n * 32 + r);
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-              float v = acc[m][n][e] + bias[n];
-              if (a.relu) v = fmaxf(v, 0.0f);
-              yp[(size_t)((e & 3) + 8 * (e >> 2)) * a.ldy] = v;
-            }
-          }
-      } else {
-#pragma unroll
-        for (int m = 0; m < MB; ++m)
-#pragma unroll
-          for (int n = 0; n < NB; ++n) {
-            const int co = col0 + wc * WN + n * 32 + r;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-              const int orow = row0 + wr * WM + m * 32 + ld_rowmap(e, h);
-              float v = acc[m][n][e] + bias[n];
-              if (a.relu) v = fmaxf(v, 0.0f);
-              if (orow < a.M && co < a.N) y[(size_t)orow * a.ldy + co] = v;
-            }
-          }
-      }
+      lin_epi_store<false>(acc, a, whole, row0 + wr * WM, col0 + wc * WN, r, h);
     } else if constexpr (EPI == 2) {
       // row-dot epilogue (the confidence regressor's last two layers, models/DCL_Net.py:115-126: ... -> 128 -> 1): the tile
       // spans all N <= BN columns;  out[row] = sum_c relu(acc[row][c] + bias[c]) * w3[c] + b3  -- per lane over its column
       // blocks, over the 32 lanes of a half wave by a butterfly, over the WGC waves of a row through LDS in wave order.
-      float w3c[NB], bias[NB];
-#pragma unroll
-      for (int n = 0; n < NB; ++n) {
-        const int co = col0 + wc * WN + n * 32 + r;
-        bias[n] = (a.bias && co < a.N) ? a.bias[co] : 0.0f;
-        w3c[n] = co < a.N ? a.roww[(size_t)co * a.w_stride] : 0.0f;
-      }
       float *red = ld_lds + RING;                          // [WGC][BM]
-#pragma unroll
-      for (int m = 0; m < MB; ++m)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          float sdot = 0.0f;
-#pragma unroll
-          for (int n = 0; n < NB; ++n) sdot = __fmaf_rn(fmaxf(acc[m][n][e] + bias[n], 0.0f), w3c[n], sdot);
-#pragma unroll
-          for (int d = 16; d >= 1; d >>= 1) sdot += __shfl_xor(sdot, d, 64);
-          if (r == 0) red[wc * BM + wr * WM + m * 32 + ld_rowmap(e, h)] = sdot;
-        }
+      lin_epi_rowdot(acc, a, wc * BM + wr * WM, col0 + wc * WN, r, h, [&](int slot, float sdot) {
+        if (r == 0) red[slot] = sdot;
+      });
       dcl_lds_barrier();
       if (tid < BM && row0 + tid < a.M) {
         float sdot = red[tid];
@@ -345,29 +269,8 @@ __global__ __launch_bounds__(256 * KS, KS == 4 ? 4 : 2) void k_linear_dma(const 
       // waves of a column through LDS in wave order -- a fixed order, the same bits every run.  (The tile's row weights sit
       // in LDS behind the ring since the tile's first barrier; the sums go behind them: the ring itself may be receiving the
       // next tile's first chunk.)
-      const float *wl = ld_lds + RING + wr * WM + 4 * h;
       float *red = ld_lds + RING + BM;                     // [WGR][BN]
-#pragma unroll
-      for (int n = 0; n < NB; ++n) {
-        const int cl = wc * WN + n * 32 + r, co = col0 + cl;
-        const float bias = (a.bias && co < a.N) ? a.bias[co] : 0.0f;
-        float s = 0.0f;
-#pragma unroll
-        for (int m = 0; m < MB; ++m)
-#pragma unroll
-          for (int g4 = 0; g4 < 4; ++g4) {
-            const float4 w4 = *reinterpret_cast<const float4 *>(wl + m * 32 + 8 * g4);    // rows 8 g4 + 4 h + 0..3 = e 4 g4 .. + 3
-            const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              float v = acc[m][n][4 * g4 + j] + bias;
-              if (a.relu) v = fmaxf(v, 0.0f);
-              s = __fmaf_rn(v, wv[j], s);
-            }
-          }
-        s += __shfl_xor(s, 32, 64);
-        if (h == 0) red[wr * BN + cl] = s;
-      }
+      lin_epi_colsum(acc, a, ld_lds + RING, red + wr * BN, wr * WM, col0, wc * WN, r, h);
       dcl_lds_barrier();
       if (tid < BN && col0 + tid < a.N) {
         float s = red[tid];

@@ -16,6 +16,7 @@
 // sum runs over k ascending inside one accumulator -- the order of a plain dot product.
 #include <hip/hip_runtime.h>
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
@@ -23,20 +24,6 @@ constexpr int kLgBM = 64, kLgBN = 64, kLgKC = 32, kLgStages = 5;   // 80 KiB of 
 constexpr int kLgAT = kLgBM * kLgKC, kLgBT = kLgKC * kLgBN, kLgST = kLgAT + kLgBT;   // floats per stage (16 KiB)
 
 __device__ __attribute__((aligned(256))) float g_lg_zero[256];      // the zero line (static storage: all zero)
-
-typedef __attribute__((address_space(3))) void lg_lds_void_t;
-typedef float lg_f32x16 __attribute__((ext_vector_type(16)));
-__device__ __forceinline__ unsigned lg_lds_addr(const float *p) {
-  return __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lg_lds_void_t *)p);
-}
-// two pieces whose LDS destinations are 1 KiB apart under ONE M0 value (see conv_glds16_group, sparse_conv.hip): the second
-// source pointer is pre-decremented by 1 KiB because the instruction's offset field moves the global address too
-__device__ __forceinline__ void lg_glds16_pair(const float *g0, const float *g1_minus_1k, unsigned lds_byte_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-               "global_load_lds_dwordx4 %2, off offset:1024\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(g0), "v"(g1_minus_1k), "s"(lds_byte_addr) : "memory");
-}
 
 __global__ __launch_bounds__(256) void k_linear_group(const DclLinearJobs jobs, int njobs) {
   extern __shared__ __attribute__((aligned(16))) float lg_lds[];    // kLgStages x [A 64x32 | B 32x64]
@@ -73,15 +60,15 @@ __global__ __launch_bounds__(256) void k_linear_group(const DclLinearJobs jobs, 
   }
   auto issue = [&](int chunk, int stage) {
     float *As = lg_lds + stage * kLgST, *Bs = As + kLgAT;
-    const float *a0 = asrc[0] ? asrc[0] + chunk * kLgKC : zero;
-    const float *a1 = (asrc[1] ? asrc[1] + chunk * kLgKC : zero) - 256;
-    const float *b0 = bsrc[0] ? bsrc[0] + (size_t)chunk * kLgKC * ldw : zero;
-    const float *b1 = (bsrc[1] ? bsrc[1] + (size_t)chunk * kLgKC * ldw : zero) - 256;
-    lg_glds16_pair(b0, b1, lg_lds_addr(Bs + (2 * wave) * 256));
-    lg_glds16_pair(a0, a1, lg_lds_addr(As + (2 * wave) * 256));
+    // (two pieces 1 KiB apart under one M0 value: the second source is pre-decremented by 1 KiB, see glds16_group)
+    const float *const ap[2] = {asrc[0] ? asrc[0] + chunk * kLgKC : zero, (asrc[1] ? asrc[1] + chunk * kLgKC : zero) - 256};
+    const float *const bp[2] = {bsrc[0] ? bsrc[0] + (size_t)chunk * kLgKC * ldw : zero,
+                                (bsrc[1] ? bsrc[1] + (size_t)chunk * kLgKC * ldw : zero) - 256};
+    glds16_group<2>(bp, lds_addr(Bs + (2 * wave) * 256));
+    glds16_group<2>(ap, lds_addr(As + (2 * wave) * 256));
   };
 
-  lg_f32x16 acc;
+  f32x16 acc;
 #pragma unroll
   for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
   const int nchunks = K / kLgKC;
@@ -121,7 +108,7 @@ __global__ __launch_bounds__(256) void k_linear_group(const DclLinearJobs jobs, 
     const long long ldy = J.ldy;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const int orow = row0 + wr * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+      const int orow = row0 + wr * 32 + rowmap(e, h);
       if (orow < M) {
         float v = acc[e] + bias;
         if (J.relu) v = fmaxf(v, 0.0f);

@@ -21,15 +21,9 @@
 // Bound: bf16 MFMA at six products per fp32 product; algorithmic work 2 M N K flop (12 M N K bf16 flop executed).
 #include <hip/hip_runtime.h>
 #include "common.h"
+#include "linear_epilogue.h"
 
 namespace {
-
-typedef float sp_f32x16 __attribute__((ext_vector_type(16)));
-typedef float sp_f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 sp_bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 sp_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned sp_u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void sp_lds_void_t;
 
 constexpr int kSpKC = 16;                                  // k per chunk = one MFMA k step
 constexpr int kSpBM = 256, kSpBN = 128;                    // workgroup tile
@@ -37,39 +31,6 @@ constexpr int kSpA = kSpBM * kSpKC * 4;                    // bytes of an x tile
 constexpr int kSpP = kSpBN * kSpKC * 2;                    // bytes of one weight-piece tile (4 KiB)
 constexpr int kSpB = 3 * kSpP;                             // ... of the three             (12 KiB)
 constexpr int kSpST = kSpA + kSpB;                         // a stage                      (28 KiB)
-
-__device__ __forceinline__ unsigned sp_lds_addr(const void *p) {
-  return __builtin_amdgcn_readfirstlane((unsigned)(size_t)(sp_lds_void_t *)p);
-}
-// one LDS-DMA piece: 64 lanes x 16 B from (wave-uniform base, SGPR pair) + (per-lane byte offset) to LDS at lds_byte_addr + lane * 16
-// (inline asm on purpose, see linear_dma.hip: ld_glds16_s)
-__device__ __forceinline__ void sp_glds16(unsigned voff, const void *sbase, unsigned lds_byte_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_byte_addr) : "memory");
-}
-// two floats -> two bf16 (round to nearest even: v_cvt_pk_bf16_f32), low half = a
-__device__ __forceinline__ unsigned sp_cvt2(float a, float b) {
-  const sp_f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, sp_bf16x2));
-}
-// (x0, x1) -> packed pieces h, m, l with x = h + m + l exactly
-__device__ __forceinline__ void sp_split2(float x0, float x1, unsigned &h, unsigned &m, unsigned &l) {
-  // (the empty asm statements keep the two subtractions of a pair from being fused into one v_pk_add_f32: packed fp32 VALU beside
-  //  MFMAs costs more than the two scalar instructions it replaces -- MI355X_MICROARCH.md, cycle constants)
-  h = sp_cvt2(x0, x1);
-  float r0 = x0 - __uint_as_float(h << 16);
-  asm volatile("" : "+v"(r0));
-  float r1 = x1 - __uint_as_float(h & 0xffff0000u);
-  asm volatile("" : "+v"(r1));
-  m = sp_cvt2(r0, r1);
-  float s0 = r0 - __uint_as_float(m << 16);
-  asm volatile("" : "+v"(s0));
-  float s1 = r1 - __uint_as_float(m & 0xffff0000u);
-  asm volatile("" : "+v"(s1));
-  l = sp_cvt2(s0, s1);
-}
-__device__ __forceinline__ sp_bf16x8 sp_bf(sp_u32x4 v) { return __builtin_bit_cast(sp_bf16x8, v); }
 
 struct LinSplitArgs {
   const float *x;
@@ -87,8 +48,6 @@ struct LinSplitArgs {
   int xcd_remap;
 };
 
-__device__ __forceinline__ int sp_rowmap(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
-
 // weight pieces in tile order: [K/16 chunks][ceil(N/128) column tiles][3 pieces][128 columns][2 halves of the 16 k][8 bf16], the
 // half index XORed with bit 3 of the column (the fragment reads of sixteen consecutive columns then cover all LDS banks)
 __global__ __launch_bounds__(256) void k_split_weight(const float *__restrict__ Wt, long long ldw, int K, int N, unsigned *__restrict__ planes) {
@@ -103,7 +62,7 @@ __global__ __launch_bounds__(256) void k_split_weight(const float *__restrict__ 
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float w0 = col < N ? Wt[(size_t)(k0 + 2 * e) * ldw + col] : 0.0f, w1 = col < N ? Wt[(size_t)(k0 + 2 * e + 1) * ldw + col] : 0.0f;
-      sp_split2(w0, w1, h[e], m[e], l[e]);
+      bf16_split2(w0, w1, h[e], m[e], l[e]);
     }
     unsigned *dst = planes + (size_t)ct * (kSpB / 4) + (size_t)(c * 2 + hs) * 4;
 #pragma unroll
@@ -118,23 +77,12 @@ __global__ __launch_bounds__(256, 2) void k_linear_split(const LinSplitArgs a) {
   // workgroup ids are dealt round-robin over the 8 XCDs: XCD x owns a contiguous range of tiles in (row block, column block) order,
   // so the workgroups that share an L2 work on the column tiles of the same row blocks (linear_dma.hip)
   int t_lo, t_hi, t_stride;
-  {
-    const int id = blockIdx.x, nwg = gridDim.x;
-    if ((a.xcd_remap & 1) && (nwg & 7) == 0) {
-      const int xq = tiles >> 3, xr = tiles & 7, xcd = id & 7;
-      const int x_lo = xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq;
-      t_lo = x_lo + (id >> 3);
-      t_hi = x_lo + xq + (xcd < xr ? 1 : 0);
-      t_stride = nwg >> 3;
-    } else {
-      t_lo = id; t_hi = tiles; t_stride = nwg;
-    }
-  }
+  xcd_tile_range(a.xcd_remap & 1, tiles, t_lo, t_hi, t_stride);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
   const int nchunks = a.K / kSpKC;
   const int whatif = a.xcd_remap >> 1;                     // (diagnostic library: timing-only what-if runs; 0 in the product)
-  const unsigned lds0 = sp_lds_addr(sp_lds);
+  const unsigned lds0 = lds_addr(sp_lds);
   const size_t bstep = (size_t)ntn * kSpB;                 // bytes from a column tile's chunk to its next chunk
 
   // fragment addresses inside a stage (bytes): x[row][8 h .. 8 h + 7] of row block i = pieces 2 h, 2 h + 1 of the row, swizzled by
@@ -162,15 +110,15 @@ __global__ __launch_bounds__(256, 2) void k_linear_split(const LinSplitArgs a) {
     // the 7 DMA pieces of a chunk: 3 of the weight pieces, 4 x-row groups; bases advance behind the last one
     auto issue_piece = [&](int k, int stage) {
       const unsigned s0 = lds0 + (unsigned)(stage * kSpST);
-      if (k < 3) sp_glds16(boff + (unsigned)(k * 4096), bbase, s0 + (unsigned)(kSpA + k * 4096 + wave * 1024));
-      else sp_glds16(aoff[k - 3], abase, s0 + (unsigned)((wave * 64 + (k - 3) * 16) * 64));
+      if (k < 3) glds16_s(boff + (unsigned)(k * 4096), bbase, s0 + (unsigned)(kSpA + k * 4096 + wave * 1024));
+      else glds16_s(aoff[k - 3], abase, s0 + (unsigned)((wave * 64 + (k - 3) * 16) * 64));
       if (k == 6) { abase += kSpKC; bbase += bstep; }
     };
     auto issue = [&](int stage) {
 #pragma unroll
       for (int k = 0; k < 7; ++k) issue_piece(k, stage);
     };
-    sp_f32x16 acc[2][4];
+    f32x16 acc[2][4];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -198,19 +146,19 @@ __global__ __launch_bounds__(256, 2) void k_linear_split(const LinSplitArgs a) {
       const bool more = c + 1 < nchunks;
       const unsigned char *sa = afrag + st * kSpST, *sb = bfrag + st * kSpST;
       float4 av[2][2];
-      sp_u32x4 ap[2][3], bp[4][3];
+      u32x4 ap[2][3], bp[4][3];
       auto read_a = [&](int i) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) av[i][q] = *reinterpret_cast<const float4 *>(sa + i * 32 * 64 + (((2 * h + q) ^ asw) << 4));
       };
       auto read_b = [&](int j) {
 #pragma unroll
-        for (int p = 0; p < 3; ++p) bp[j][p] = *reinterpret_cast<const sp_u32x4 *>(sb + p * kSpP + j * 32 * 32);
+        for (int p = 0; p < 3; ++p) bp[j][p] = *reinterpret_cast<const u32x4 *>(sb + p * kSpP + j * 32 * 32);
       };
       auto split_a = [&](int i, int part) {                // values 2 part, 2 part + 1 of the row block's eight
         unsigned ph, pm, pl;
         const float4 v = av[i][part >> 1];
-        if (part & 1) sp_split2(v.z, v.w, ph, pm, pl); else sp_split2(v.x, v.y, ph, pm, pl);
+        if (part & 1) bf16_split2(v.z, v.w, ph, pm, pl); else bf16_split2(v.x, v.y, ph, pm, pl);
         ap[i][0][part] = ph; ap[i][1][part] = pm; ap[i][2][part] = pl;
       };
       read_a(0);
@@ -223,19 +171,19 @@ __global__ __launch_bounds__(256, 2) void k_linear_split(const LinSplitArgs a) {
         for (int part = 0; part < 4; ++part) split_a(0, part);
       } else {
 #pragma unroll
-        for (int p = 0; p < 3; ++p) ap[0][p] = sp_u32x4{__float_as_uint(av[0][0].x), __float_as_uint(av[0][0].y), __float_as_uint(av[0][1].x), __float_as_uint(av[0][1].y)};
+        for (int p = 0; p < 3; ++p) ap[0][p] = u32x4{__float_as_uint(av[0][0].x), __float_as_uint(av[0][0].y), __float_as_uint(av[0][1].x), __float_as_uint(av[0][1].y)};
       }
       read_b(1);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int blk = 0; blk < 8; ++blk) {
         const int i = blk >> 2, j = blk & 3;               // small terms first
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_bf(ap[i][2]), sp_bf(bp[j][0]), acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_bf(ap[i][0]), sp_bf(bp[j][2]), acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_bf(ap[i][1]), sp_bf(bp[j][1]), acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_bf(ap[i][1]), sp_bf(bp[j][0]), acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_bf(ap[i][0]), sp_bf(bp[j][1]), acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(sp_bf(ap[i][0]), sp_bf(bp[j][0]), acc[i][j], 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(ap[i][2]), as_bf16x8(bp[j][0]), acc[i][j], 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(ap[i][0]), as_bf16x8(bp[j][2]), acc[i][j], 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(ap[i][1]), as_bf16x8(bp[j][1]), acc[i][j], 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(ap[i][1]), as_bf16x8(bp[j][0]), acc[i][j], 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(ap[i][0]), as_bf16x8(bp[j][1]), acc[i][j], 0, 0, 0);
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(ap[i][0]), as_bf16x8(bp[j][0]), acc[i][j], 0, 0, 0);
         if (blk < 4) {
           if (!(whatif & 2)) split_a(1, blk);
           else { ap[1][0][blk] = __float_as_uint(av[1][blk >> 1].x); ap[1][1][blk] = __float_as_uint(av[1][blk >> 1].y); ap[1][2][blk] = __float_as_uint(av[1][blk >> 1].z); }
@@ -249,42 +197,9 @@ __global__ __launch_bounds__(256, 2) void k_linear_split(const LinSplitArgs a) {
 
     if constexpr (EPI == 0) {
       if (whatif & 4) continue;
-      float *__restrict__ y = a.y;
       const bool whole = row0 + kSpBM <= a.M && col0 + kSpBN <= a.N;
-      float bias[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int co = col0 + j * 32 + r;
-        bias[j] = (a.bias && co < a.N) ? a.bias[co] : 0.0f;
-      }
-      if (whole) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            float *yp = y + (size_t)(row0 + wave * 64 + i * 32 + 4 * h) * a.ldy + (col0 + j * 32 + r);
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-              float v = acc[i][j][e] + bias[j];
-              if (a.relu) v = fmaxf(v, 0.0f);
-              __builtin_nontemporal_store(v, yp + (size_t)((e & 3) + 8 * (e >> 2)) * a.ldy);   // (an activation of hundreds of MB: read
-            }                                                                                  //  once by the next layer, from HBM anyway)
-          }
-      } else {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int co = col0 + j * 32 + r;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-              const int orow = row0 + wave * 64 + i * 32 + sp_rowmap(e, h);
-              float v = acc[i][j][e] + bias[j];
-              if (a.relu) v = fmaxf(v, 0.0f);
-              if (orow < a.M && co < a.N) y[(size_t)orow * a.ldy + co] = v;
-            }
-          }
-      }
+      // (whole tiles leave by non-temporal stores: an activation of hundreds of MB, read once by the next layer, from HBM anyway)
+      lin_epi_store<true>(acc, a, whole, row0 + wave * 64, col0, r, h);
     } else if constexpr (EPI == 3) {
       // attention-V epilogue: the activation leaves the kernel AS the three bf16 pieces the attention's P.V product reads
       // (csrc/dense.hip: k_cross_attn_split; layout of k_attn_split_v, which this makes unnecessary for these channels) and is
@@ -304,20 +219,20 @@ __global__ __launch_bounds__(256, 2) void k_linear_split(const LinSplitArgs a) {
 #pragma unroll
           for (int hf = 0; hf < 2; ++hf) {
             const long long ht = (long long)crop * a.ldp + ((key0 + wave * 64 + i * 32) >> 4) + hf;
-            sp_u32x4 ph, pm, pl;
+            u32x4 ph, pm, pl;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               float v0 = acc[i][j][8 * hf + 2 * e] + bias, v1 = acc[i][j][8 * hf + 2 * e + 1] + bias;
               if (a.relu) { v0 = fmaxf(v0, 0.0f); v1 = fmaxf(v1, 0.0f); }
               unsigned qh, qm, ql;
-              sp_split2(v0, v1, qh, qm, ql);
+              bf16_split2(v0, v1, qh, qm, ql);
               ph[e] = qh; pm[e] = qm; pl[e] = ql;
             }
             unsigned char *dst = vp + (size_t)ht * (3 * 320 * 32) + (size_t)(c * 2 + hs) * 16;
             if (c < a.N) {
-              *reinterpret_cast<sp_u32x4 *>(dst) = ph;
-              *reinterpret_cast<sp_u32x4 *>(dst + 320 * 32) = pm;
-              *reinterpret_cast<sp_u32x4 *>(dst + 2 * 320 * 32) = pl;
+              *reinterpret_cast<u32x4 *>(dst) = ph;
+              *reinterpret_cast<u32x4 *>(dst + 320 * 32) = pm;
+              *reinterpret_cast<u32x4 *>(dst + 2 * 320 * 32) = pl;
             }
           }
       }
@@ -325,52 +240,19 @@ __global__ __launch_bounds__(256, 2) void k_linear_split(const LinSplitArgs a) {
       // row-dot epilogue (the confidence regressor's last two layers, models/DCL_Net.py:115-126: ... -> 128 -> 1): the tile spans all
       // N <= 128 columns and a wave all of them:  out[row] = sum_c relu(acc[row][c] + bias[c]) * w3[c] + b3 -- per lane over its four
       // column blocks, then a butterfly over the 32 lanes of a half wave
-      float w3c[4], bias[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int co = col0 + j * 32 + r;
-        bias[j] = (a.bias && co < a.N) ? a.bias[co] : 0.0f;
-        w3c[j] = co < a.N ? a.roww[(size_t)co * a.w_stride] : 0.0f;
-      }
+      // (what the callable reads goes in by value: reached through references, r == 0 and orow < M become two branches per row)
       const float b3 = a.b3[0];
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          float sdot = 0.0f;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) sdot = __fmaf_rn(fmaxf(acc[i][j][e] + bias[j], 0.0f), w3c[j], sdot);
-#pragma unroll
-          for (int d = 16; d >= 1; d >>= 1) sdot += __shfl_xor(sdot, d, 64);
-          const int orow = row0 + wave * 64 + i * 32 + sp_rowmap(e, h);
-          if (r == 0 && orow < a.M) a.part[orow] = sdot + b3;
-        }
+      float *out = a.part;
+      const int M = a.M;
+      lin_epi_rowdot(acc, a, row0 + wave * 64, col0, r, h, [=](int orow, float sdot) {
+        if (r == 0 && orow < M) out[orow] = sdot + b3;
+      });
     } else {
       // weighted column sums per 128-row pooling tile (waves 0, 1 / 2, 3): per wave over its 64 rows (registers, then the two
       // lane halves), then the two waves of a pooling tile through LDS in wave order -- a fixed order, the same bits every run
-      const float *wl = reinterpret_cast<const float *>(sp_lds + 2 * kSpST) + wave * 64 + 4 * h;
+      const float *wts = reinterpret_cast<const float *>(sp_lds + 2 * kSpST);
       float *red = reinterpret_cast<float *>(sp_lds + 2 * kSpST) + kSpBM;          // [4 waves][128]
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int cl = j * 32 + r, co = col0 + cl;
-        const float bias = (a.bias && co < a.N) ? a.bias[co] : 0.0f;
-        float s = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int g4 = 0; g4 < 4; ++g4) {
-            const float4 w4 = *reinterpret_cast<const float4 *>(wl + i * 32 + 8 * g4);
-            const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              float v = acc[i][j][4 * g4 + q] + bias;
-              if (a.relu) v = fmaxf(v, 0.0f);
-              s = __fmaf_rn(v, wv[q], s);
-            }
-          }
-        s += __shfl_xor(s, 32, 64);
-        if (h == 0) red[wave * kSpBN + cl] = s;
-      }
+      lin_epi_colsum(acc, a, wts, red + wave * kSpBN, wave * 64, col0, 0, r, h);
       dcl_lds_barrier();
       {
         const int pt = tid >> 7, cl = tid & 127;           // pooling tile inside the workgroup tile, column

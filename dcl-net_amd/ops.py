@@ -145,7 +145,7 @@ def pad_copy_many(jobs):
             assert src.is_cuda and src.dim() == 2 and src.stride(1) == 1 and src.element_size() in (4, 8)
             assert src.element_size() == 4 or src.dtype == torch.int64
             q.src, q.rows_src, q.cols_src = src.data_ptr(), src.shape[0], src.shape[1]
-            q.src_pitch = src.stride(0) if src.shape[0] > 1 else src.shape[1]
+            q.src_pitch = _pitch(src)
             q.src_is_i64 = int(src.dtype == torch.int64)
         else:
             q.src, q.fill_value = None, int(src)
@@ -936,26 +936,47 @@ def linear(x, Wt, bias=None, relu=False, out=None):
     return linear_lt(x, Wt, bias, relu, out)
 
 
+def _pitch(t):
+    """row pitch of a 2-D tensor in elements (a single row has none of its own: at least its width)"""
+    return int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))
+
+
+def _layer_io(x, K, n, bias, out, dense=()):
+    """The operand checks of a (M, K) -> (M, n) layer with linear()'s conventions (dense: further 2-D operands whose rows must be
+    dense).  Returns out, allocated if None."""
+    assert x.dim() == 2 and x.shape[1] == K and x.dtype == torch.float32
+    M = x.shape[0]
+    if out is None:
+        out = torch.empty((M, n), dtype=torch.float32, device=x.device)
+    assert out.shape == (M, n) and out.dtype == torch.float32 and out.is_cuda
+    for t in (x,) + dense + (out,):
+        assert t.stride(1) == 1 or t.shape[1] == 1, "rows must be dense"
+    if bias is not None:
+        assert bias.is_cuda and bias.dtype == torch.float32 and bias.numel() == n and bias.is_contiguous()
+    return out
+
+
+def _linear_fp32(x, Wt, bias, relu, out, vendor):
+    """linear_lt / linear_dma: the same operands, one entry point each"""
+    N.need_cuda(x, Wt)
+    assert Wt.dim() == 2 and Wt.dtype == torch.float32
+    K, n = Wt.shape
+    out = _layer_io(x, K, n, bias, out, dense=(Wt,))
+    M = x.shape[0]
+    args = (N.ptr(x), C.c_int64(_pitch(x)), N.ptr(Wt), C.c_int64(_pitch(Wt)), N.ptr(bias), N.ptr(out), C.c_int64(_pitch(out)),
+            int(M), int(n), int(K), int(bool(relu)))
+    if vendor:
+        N.check(N.lib().dcl_linear_fwd(*args, None, C.c_int64(0), N.stream()), "linear_fwd")
+    else:
+        N.check(N.lib().dcl_linear_dma_fwd(*args, N.stream()), "linear_dma_fwd")
+    return out
+
+
 def linear_lt(x, Wt, bias=None, relu=False, out=None):
     """linear() as a vendor-library GEMM (hipBLASLt, bias / ReLU epilogue) called through the C-ABI (dcl_linear_fwd): only
     algorithms that ask for NO workspace are ever taken (csrc/linear.cpp: two workspace-exchanging stream-K kernels side by
     side hang the GPU); the call fails when the library has none for the shape."""
-    N.need_cuda(x, Wt)
-    assert x.dim() == 2 and Wt.dim() == 2 and x.shape[1] == Wt.shape[0] and x.dtype == Wt.dtype == torch.float32
-    M, K = x.shape
-    n = Wt.shape[1]
-    if out is None:
-        out = torch.empty((M, n), dtype=torch.float32, device=x.device)
-    assert out.shape == (M, n) and out.dtype == torch.float32 and out.is_cuda
-    for t in (x, Wt, out):
-        assert t.stride(1) == 1 or t.shape[1] == 1, "rows must be dense"
-    if bias is not None:
-        assert bias.is_cuda and bias.dtype == torch.float32 and bias.numel() == n and bias.is_contiguous()
-    pitch = lambda t: int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))   # noqa: E731
-    N.check(N.lib().dcl_linear_fwd(N.ptr(x), C.c_int64(pitch(x)), N.ptr(Wt), C.c_int64(pitch(Wt)), N.ptr(bias), N.ptr(out),
-                                   C.c_int64(pitch(out)), int(M), int(n), int(K), int(bool(relu)), None,
-                                   C.c_int64(0), N.stream()), "linear_fwd")
-    return out
+    return _linear_fp32(x, Wt, bias, relu, out, vendor=True)
 
 
 def linear_dma_ok(x, Wt):
@@ -970,21 +991,7 @@ def linear_dma_ok(x, Wt):
 def linear_dma(x, Wt, bias=None, relu=False, out=None):
     """linear() on the library's OWN fp32 MFMA GEMM core (csrc/linear_dma.hip; no vendor library): act(x @ Wt + bias), same
     conventions -- x (M,K), Wt (K,N), out (M,N) row-major with free row pitches."""
-    N.need_cuda(x, Wt)
-    assert x.dim() == 2 and Wt.dim() == 2 and x.shape[1] == Wt.shape[0] and x.dtype == Wt.dtype == torch.float32
-    M, K = x.shape
-    n = Wt.shape[1]
-    if out is None:
-        out = torch.empty((M, n), dtype=torch.float32, device=x.device)
-    assert out.shape == (M, n) and out.dtype == torch.float32 and out.is_cuda
-    for t in (x, Wt, out):
-        assert t.stride(1) == 1 or t.shape[1] == 1, "rows must be dense"
-    if bias is not None:
-        assert bias.is_cuda and bias.dtype == torch.float32 and bias.numel() == n and bias.is_contiguous()
-    pitch = lambda t: int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))   # noqa: E731
-    N.check(N.lib().dcl_linear_dma_fwd(N.ptr(x), C.c_int64(pitch(x)), N.ptr(Wt), C.c_int64(pitch(Wt)), N.ptr(bias), N.ptr(out),
-                                       C.c_int64(pitch(out)), int(M), int(n), int(K), int(bool(relu)), N.stream()), "linear_dma_fwd")
-    return out
+    return _linear_fp32(x, Wt, bias, relu, out, vendor=False)
 
 
 GEMM_SPLIT = True              # big launches of prepared layers run on the split-bf16 core (False: the fp32-MFMA core everywhere)
@@ -1026,6 +1033,23 @@ def prepared_linear(Wt, x):
 LINEAR_POOL_TILE = 128         # rows per partial of linear_pool (the GEMM's row tile)
 
 
+def _linear_pool(fn, what, x, wargs, K, n, bias, roww, relu, part, rows_per_crop, w_stride):
+    """linear_pool on either core: fn = the entry point (`what` names it in an error), wargs = its weight arguments"""
+    M = x.shape[0]
+    if rows_per_crop is None:
+        rows_per_crop, w_stride = M, 0
+        assert roww.is_contiguous() and roww.numel() == M
+    assert roww.dtype == torch.float32 and M % rows_per_crop == 0
+    tiles = (M + LINEAR_POOL_TILE - 1) // LINEAR_POOL_TILE
+    if part is None:
+        part = torch.empty((tiles, n), dtype=torch.float32, device=x.device)
+    assert part.shape == (tiles, n) and part.stride(1) == 1
+    N.check(fn(N.ptr(x), C.c_int64(_pitch(x)), *wargs, N.ptr(bias), N.ptr(roww), int(rows_per_crop),
+                                          C.c_int64(int(w_stride)), N.ptr(part), C.c_int64(_pitch(part)), int(M), int(n), int(K),
+                                          int(bool(relu)), N.stream()), what)
+    return part
+
+
 def linear_pool(x, Wt, bias, roww, relu=True, part=None, rows_per_crop=None, w_stride=0):
     """The last fuser layer with the confidence-weighted pooling as its epilogue (csrc/linear_dma.hip, EPI = 1):
     part[t] = sum over rows j of row tile t (128 rows) of w_j * act(x[j] @ Wt + bias) -- (ceil(M/128), N); the (M, N)
@@ -1037,20 +1061,22 @@ def linear_pool(x, Wt, bias, roww, relu=True, part=None, rows_per_crop=None, w_s
     if sw is not None:
         return linear_split_pool(x, sw, bias, roww, relu, part, rows_per_crop, w_stride)
     M, K = x.shape
-    n = Wt.shape[1]
-    if rows_per_crop is None:
-        rows_per_crop, w_stride = M, 0
-        assert roww.is_contiguous() and roww.numel() == M
-    assert roww.dtype == torch.float32 and M % rows_per_crop == 0
-    tiles = (M + LINEAR_POOL_TILE - 1) // LINEAR_POOL_TILE
-    if part is None:
-        part = torch.empty((tiles, n), dtype=torch.float32, device=x.device)
-    assert part.shape == (tiles, n) and part.stride(1) == 1
-    pitch = lambda t: int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))   # noqa: E731
-    N.check(N.lib().dcl_linear_pool_fwd(N.ptr(x), C.c_int64(pitch(x)), N.ptr(Wt), C.c_int64(pitch(Wt)), N.ptr(bias), N.ptr(roww),
-                                        int(rows_per_crop), C.c_int64(int(w_stride)), N.ptr(part), C.c_int64(pitch(part)), int(M),
-                                        int(n), int(K), int(bool(relu)), N.stream()), "linear_pool_fwd")
-    return part
+    return _linear_pool(N.lib().dcl_linear_pool_fwd, "linear_pool_fwd", x, (N.ptr(Wt), C.c_int64(_pitch(Wt))), K, Wt.shape[1], bias, roww, relu, part,
+                        rows_per_crop, w_stride)
+
+
+def _linear_rowdot(fn, what, x, wargs, K, n, bias, w3, b3, out):
+    """linear_rowdot on either core: fn = the entry point (`what` names it in an error), wargs = its weight arguments"""
+    M = x.shape[0]
+    assert n <= 128 and w3.shape == (n, 1) and b3.numel() == 1 and bias.numel() == n
+    if out is None:
+        out = torch.empty((M, 1), dtype=torch.float32, device=x.device)
+    assert out.is_contiguous() and out.numel() == M
+    if M == 0:                                              # (an empty tensor has no address to pass)
+        return out
+    N.check(fn(N.ptr(x), C.c_int64(_pitch(x)), *wargs, N.ptr(bias), N.ptr(w3), C.c_int64(int(w3.stride(0))),
+                                          N.ptr(b3), N.ptr(out), int(M), int(n), int(K), N.stream()), what)
+    return out
 
 
 def linear_rowdot(x, Wt, bias, w3, b3, out=None):
@@ -1062,18 +1088,8 @@ def linear_rowdot(x, Wt, bias, w3, b3, out=None):
     if sw is not None:
         return linear_split_rowdot(x, sw, bias, w3, b3, out)
     M, K = x.shape
-    n = Wt.shape[1]
-    assert n <= 128 and w3.shape == (n, 1) and b3.numel() == 1 and bias.numel() == n
-    if out is None:
-        out = torch.empty((M, 1), dtype=torch.float32, device=x.device)
-    assert out.is_contiguous() and out.numel() == M
-    if M == 0:                                              # (an empty tensor has no address to pass)
-        return out
-    pitch = lambda t: int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))   # noqa: E731
-    N.check(N.lib().dcl_linear_rowdot_fwd(N.ptr(x), C.c_int64(pitch(x)), N.ptr(Wt), C.c_int64(pitch(Wt)), N.ptr(bias), N.ptr(w3),
-                                          C.c_int64(int(w3.stride(0))), N.ptr(b3), N.ptr(out), int(M), int(n), int(K), N.stream()),
-            "linear_rowdot_fwd")
-    return out
+    return _linear_rowdot(N.lib().dcl_linear_rowdot_fwd, "linear_rowdot_fwd", x, (N.ptr(Wt), C.c_int64(_pitch(Wt))), K, Wt.shape[1],
+                          bias, w3, b3, out)
 
 
 class SplitWeight:
@@ -1090,8 +1106,7 @@ class SplitWeight:
         nbytes = int(lib.dcl_linear_split_weight_bytes(int(self.K), int(self.n)))
         assert nbytes > 0, "split-bf16 GEMM core: K must be a multiple of 16"
         self.planes = torch.empty(nbytes, dtype=torch.uint8, device=Wt.device)
-        pw = int(Wt.stride(0)) if self.K > 1 else self.n
-        N.check(lib.dcl_linear_split_weight(N.ptr(Wt), C.c_int64(pw), int(self.K), int(self.n), N.ptr(self.planes), N.stream()),
+        N.check(lib.dcl_linear_split_weight(N.ptr(Wt), C.c_int64(_pitch(Wt)), int(self.K), int(self.n), N.ptr(self.planes), N.stream()),
                 "linear_split_weight")
 
 
@@ -1105,15 +1120,9 @@ def linear_split(x, sw, bias=None, relu=False, out=None):
     """linear() on the split-bf16 GEMM core (csrc/linear_split.hip): act(x @ sw.Wt + bias) with fp32-sized errors at the bf16
     matrix pipe's rate (three bf16 pieces per operand, six piece products per product, fp32 accumulation).  sw: SplitWeight."""
     N.need_cuda(x)
-    assert x.dim() == 2 and x.shape[1] == sw.K and x.dtype == torch.float32 and (x.stride(1) == 1 or x.shape[1] == 1)
     M, K, n = x.shape[0], sw.K, sw.n
-    if out is None:
-        out = torch.empty((M, n), dtype=torch.float32, device=x.device)
-    assert out.shape == (M, n) and out.dtype == torch.float32 and out.is_cuda and (out.stride(1) == 1 or n == 1)
-    if bias is not None:
-        assert bias.is_cuda and bias.dtype == torch.float32 and bias.numel() == n and bias.is_contiguous()
-    pitch = lambda t: int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))   # noqa: E731
-    N.check(N.lib().dcl_linear_split_fwd(N.ptr(x), C.c_int64(pitch(x)), N.ptr(sw.planes), N.ptr(bias), N.ptr(out), C.c_int64(pitch(out)),
+    out = _layer_io(x, K, n, bias, out)
+    N.check(N.lib().dcl_linear_split_fwd(N.ptr(x), C.c_int64(_pitch(x)), N.ptr(sw.planes), N.ptr(bias), N.ptr(out), C.c_int64(_pitch(out)),
                                          int(M), int(n), int(K), int(bool(relu)), N.stream()), "linear_split_fwd")
     return out
 
@@ -1121,21 +1130,9 @@ def linear_split(x, sw, bias=None, relu=False, out=None):
 def linear_split_pool(x, sw, bias, roww, relu=True, part=None, rows_per_crop=None, w_stride=0):
     """linear_pool() on the split-bf16 core: same partials layout (one row of `part` per 128 rows of x)"""
     N.need_cuda(x, roww)
-    M, K, n = x.shape[0], sw.K, sw.n
-    assert x.shape[1] == K
-    if rows_per_crop is None:
-        rows_per_crop, w_stride = M, 0
-        assert roww.is_contiguous() and roww.numel() == M
-    assert roww.dtype == torch.float32 and M % rows_per_crop == 0
-    tiles = (M + LINEAR_POOL_TILE - 1) // LINEAR_POOL_TILE
-    if part is None:
-        part = torch.empty((tiles, n), dtype=torch.float32, device=x.device)
-    assert part.shape == (tiles, n) and part.stride(1) == 1
-    pitch = lambda t: int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))   # noqa: E731
-    N.check(N.lib().dcl_linear_split_pool_fwd(N.ptr(x), C.c_int64(pitch(x)), N.ptr(sw.planes), N.ptr(bias), N.ptr(roww), int(rows_per_crop),
-                                              C.c_int64(int(w_stride)), N.ptr(part), C.c_int64(pitch(part)), int(M), int(n), int(K),
-                                              int(bool(relu)), N.stream()), "linear_split_pool_fwd")
-    return part
+    assert x.shape[1] == sw.K
+    return _linear_pool(N.lib().dcl_linear_split_pool_fwd, "linear_split_pool_fwd", x, (N.ptr(sw.planes),), sw.K, sw.n, bias, roww,
+                        relu, part, rows_per_crop, w_stride)
 
 
 def linear_split_vpieces(x, sw, bias, vplanes, rows_per_crop, relu=True):
@@ -1145,8 +1142,7 @@ def linear_split_vpieces(x, sw, bias, vplanes, rows_per_crop, relu=True):
     N.need_cuda(x, vplanes)
     M, K, n = x.shape[0], sw.K, sw.n
     assert x.shape[1] == K and n <= 320 and n % 32 == 0 and rows_per_crop % 256 == 0 and M % rows_per_crop == 0
-    pitch = lambda t: int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))   # noqa: E731
-    N.check(N.lib().dcl_linear_split_vpieces_fwd(N.ptr(x), C.c_int64(pitch(x)), N.ptr(sw.planes), N.ptr(bias), N.ptr(vplanes),
+    N.check(N.lib().dcl_linear_split_vpieces_fwd(N.ptr(x), C.c_int64(_pitch(x)), N.ptr(sw.planes), N.ptr(bias), N.ptr(vplanes),
                                                  int(rows_per_crop), int(M), int(n), int(K), int(bool(relu)), N.stream()),
             "linear_split_vpieces_fwd")
     return vplanes
@@ -1155,18 +1151,8 @@ def linear_split_vpieces(x, sw, bias, vplanes, rows_per_crop, relu=True):
 def linear_split_rowdot(x, sw, bias, w3, b3, out=None):
     """linear_rowdot() on the split-bf16 core"""
     N.need_cuda(x, w3, b3)
-    M, K, n = x.shape[0], sw.K, sw.n
-    assert x.shape[1] == K and n <= 128 and w3.shape == (n, 1) and b3.numel() == 1 and bias.numel() == n
-    if out is None:
-        out = torch.empty((M, 1), dtype=torch.float32, device=x.device)
-    assert out.is_contiguous() and out.numel() == M
-    if M == 0:                                              # (an empty tensor has no address to pass)
-        return out
-    pitch = lambda t: int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))   # noqa: E731
-    N.check(N.lib().dcl_linear_split_rowdot_fwd(N.ptr(x), C.c_int64(pitch(x)), N.ptr(sw.planes), N.ptr(bias), N.ptr(w3),
-                                                C.c_int64(int(w3.stride(0))), N.ptr(b3), N.ptr(out), int(M), int(n), int(K), N.stream()),
-            "linear_split_rowdot_fwd")
-    return out
+    assert x.shape[1] == sw.K
+    return _linear_rowdot(N.lib().dcl_linear_split_rowdot_fwd, "linear_split_rowdot_fwd", x, (N.ptr(sw.planes),), sw.K, sw.n, bias, w3, b3, out)
 
 
 def conf_softmax(b, logit1, logit2):
@@ -1212,21 +1198,14 @@ def linear_group(jobs):
     assert 1 <= len(jobs) <= LINEAR_GROUP_MAX
     arr = (_LinearJob * len(jobs))()
     outs, keep = [], []
-    pitch = lambda t: int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))   # noqa: E731
     for q, (x, Wt, bias, relu, out) in zip(arr, jobs):
         N.need_cuda(x, Wt)
-        assert x.dim() == 2 and Wt.dim() == 2 and x.shape[1] == Wt.shape[0] and x.dtype == Wt.dtype == torch.float32
-        M, K = x.shape
-        n = Wt.shape[1]
-        if out is None:
-            out = torch.empty((M, n), dtype=torch.float32, device=x.device)
-        assert out.shape == (M, n) and out.dtype == torch.float32 and out.is_cuda
-        for t in (x, Wt, out):
-            assert t.stride(1) == 1 or t.shape[1] == 1, "rows must be dense"
-        if bias is not None:
-            assert bias.is_cuda and bias.dtype == torch.float32 and bias.numel() == n and bias.is_contiguous()
-        q.x, q.ldx, q.Wt, q.ldw, q.bias = x.data_ptr(), pitch(x), Wt.data_ptr(), pitch(Wt), (None if bias is None else bias.data_ptr())
-        q.y, q.ldy, q.M, q.N, q.K, q.relu = out.data_ptr(), pitch(out), int(M), int(n), int(K), int(bool(relu))
+        assert Wt.dim() == 2 and Wt.dtype == torch.float32
+        K, n = Wt.shape
+        out = _layer_io(x, K, n, bias, out, dense=(Wt,))
+        M = x.shape[0]
+        q.x, q.ldx, q.Wt, q.ldw, q.bias = x.data_ptr(), _pitch(x), Wt.data_ptr(), _pitch(Wt), (None if bias is None else bias.data_ptr())
+        q.y, q.ldy, q.M, q.N, q.K, q.relu = out.data_ptr(), _pitch(out), int(M), int(n), int(K), int(bool(relu))
         outs.append(out)
         keep.append((x, Wt, bias))
     N.check(N.lib().dcl_linear_group_fwd(arr, len(jobs), N.stream()), "linear_group_fwd")
@@ -1258,7 +1237,7 @@ def mlp128_to1(x, layers, out=None):
     if out is None:
         out = torch.empty((M, 1), dtype=torch.float32, device=x.device)
     assert out.is_contiguous() and out.numel() == M
-    N.check(N.lib().dcl_mlp128_to1(N.ptr(x), C.c_int64(int(x.stride(0)) if M > 1 else 128), int(M), N.ptr(W1t), N.ptr(b1), N.ptr(W2t),
+    N.check(N.lib().dcl_mlp128_to1(N.ptr(x), C.c_int64(_pitch(x)), int(M), N.ptr(W1t), N.ptr(b1), N.ptr(W2t),
                                    N.ptr(b2), N.ptr(W3t), C.c_int64(int(W3t.stride(0))), N.ptr(b3), N.ptr(out), N.stream()), "mlp128_to1")
     return out
 
