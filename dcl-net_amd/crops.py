@@ -21,6 +21,7 @@ YCBV_CAMERA = (312.9869, 241.3109, 1066.778, 1067.487, 10000.0, 1.0)  # cx, cy, 
 LM_CAMERA = (325.26110, 242.04899, 572.41140, 573.57043, 1.0, 1000.0)  # LM/dataloader_test_LM.py:104-107,153-160
 MIN_VALID = 32                                                        # :163
 LM_MIN_VALID = 128                                                    # LM/dataloader_test_LM.py:197
+LMO_MIN_VALID = 0                                                     # LM/dataloader_test_LMO.py:262 (`np.sum(choose_idx)>0`)
 
 
 def snap_box(rois, row, img_h=480, img_w=640):
@@ -298,24 +299,47 @@ class CropBuilder(object):
         _mark("end")
         return data
 
-    def build_lm(self, img, depth, mask_label, obj_bb, obj, eval_mode=False):
+    def build_lm(self, img, depth, mask_label, obj_bb=None, obj=None, eval_mode=False):
         """One LineMOD sample (`PoseDataset.__getitem__`, LM/dataloader_test_LM.py:116-214, test / eval modes): img (H,W,3+) u8,
         depth (H,W) u16 in millimetres, mask_label (H,W) bool object mask (the loader's `mask_label`), obj_bb [x,y,w,h],
-        obj = class id.  The builder must have been made with camera=LM_CAMERA.  Returns (feat_inp (N,7), voxel_inp (N,3) i64,
-        feat_tmp (M,7), voxel_tmp (M,3) i64, centroid (3,)) as CUDA tensors, or None where the loader returns its all-zero
-        dummy sample (empty mask; in test mode also when at most 128 points fall inside the voxel grid)."""
+        obj = class id.  obj_bb=None: the box is the loader's `mask_to_bbox(mask_label)` (:16-32,144, eval mode), computed
+        on the device from the uploaded mask (ops.mask_box) -- the box row never visits the host.  The builder must have
+        been made with camera=LM_CAMERA.  Returns (feat_inp (N,7), voxel_inp (N,3) i64, feat_tmp (M,7), voxel_tmp (M,3) i64,
+        centroid (3,)) as CUDA tensors, or None where the loader returns its all-zero dummy sample (empty mask; in test mode
+        also when at most 128 points fall inside the voxel grid)."""
+        if obj is None:
+            raise TypeError("build_lm: obj (the class id) is required")
+        return self._lm_sample(img, depth, mask_label, obj_bb, obj, LM_MIN_VALID, eval_mode, eval_mode)
+
+    def build_lmo(self, img, depth, mask_label, obj):
+        """One Occlusion-LineMOD sample (`Dataset.__getitem__`, LM/dataloader_test_LMO.py:197-284, eval / test modes): as
+        build_lm, but the box ALWAYS comes from the mask (`get_bbox(mask_to_bbox(mask_label, padding=0))`, :215 -- the mask
+        of an occluded object comes in pieces and the loader keeps the piece with the largest bounding rectangle), the
+        voxel-grid filter is always applied (:261-264) and the dummy sample is returned when no masked pixel with depth lies
+        inside the crop (:220-222) or no point lies inside the grid (:262,282-284) -> None.  camera=LM_CAMERA.  The pose
+        labels (the LineMOD -> Occlusion alignment included) are the caller's."""
+        return self._lm_sample(img, depth, mask_label, None, obj, LMO_MIN_VALID, True, False)
+
+    def _lm_sample(self, img, depth, mask_label, obj_bb, obj, min_valid, always_filter, keep_sparse):
+        """the common body of build_lm / build_lmo.  min_valid: the sample is the dummy unless more than min_valid points lie
+        inside the grid (keep_sparse: LineMOD's eval mode keeps it whatever the count)."""
         H, W = depth.shape
-        r0, r1, c0, c1 = lm_box(obj_bb, H, W)
         dev = self.dev
         d_t = torch.from_numpy(np.ascontiguousarray(depth).astype(np.uint16).view(np.int16)).to(dev)
         l_t = torch.from_numpy(np.ascontiguousarray(mask_label).astype(np.int32)).to(dev)
         i_t = torch.from_numpy(np.ascontiguousarray(img)).to(dev)
-        b_t = torch.tensor([[max(r0, 0), min(r1, H), max(c0, 0), min(c1, W)]], dtype=torch.int32, device=dev)
+        if obj_bb is None:
+            b_t = ops.mask_box(l_t, 1, 0)[:, 4:8].contiguous()               # device tensor: no host round trip
+            cap = H * W
+        else:
+            r0, r1, c0, c1 = lm_box(obj_bb, H, W)
+            b_t = torch.tensor([[max(r0, 0), min(r1, H), max(c0, 0), min(c1, W)]], dtype=torch.int32, device=dev)
+            cap = None
         o_t = torch.ones(1, dtype=torch.int32, device=dev)
         xyz, col, centroid, counts = ops.crop_points(d_t, l_t, i_t, b_t, o_t, self.camera, RGB_MEAN, self.extent * 0.5,
-                                                     LM_MIN_VALID, always_filter=eval_mode)
+                                                     min_valid, always_filter=always_filter, cap=cap)
         n_mask, n_valid, m = counts.cpu().numpy()[0]
-        if n_mask == 0 or not (n_valid > LM_MIN_VALID or eval_mode):
+        if n_mask == 0 or not (n_valid > min_valid or keep_sparse):
             return None
         pick = ops.legacy_choice_heads([int(m)], self.n_inp)[0] if m > self.n_inp else np.random.choice(m, self.n_inp)
         pick_t = torch.from_numpy(pick.astype(np.int64)).view(1, -1).to(dev)

@@ -1393,6 +1393,37 @@ def crop_sample(xyz, rgb, sample_idx, counts, half_extent0, unit, voxel_limit, n
     return feats, coords
 
 
+def mask_box(label, value=1, padding=0):
+    """`get_bbox(mask_to_bbox(label == value, padding))` of the LineMOD / Occlusion-LineMOD loaders on the device
+    (csrc/mask_box.hip).  label (H,W) or (n,H,W) i32 CUDA.  -> (n,10) i32 CUDA: box [x,y,w,h] of the 8-connected component
+    with the largest bounding rectangle, the box row ops.crop_points takes (columns 4:8), the number of components and the
+    winner's pixel count.  No host synchronisation; the workspace is a torch allocation."""
+    N.need_cuda(label)
+    assert label.dtype == torch.int32 and label.is_contiguous() and label.dim() in (2, 3)
+    n = 1 if label.dim() == 2 else label.shape[0]
+    H, W = label.shape[-2], label.shape[-1]
+    out = torch.empty((n, 10), dtype=torch.int32, device=label.device)
+    nb = C.c_int64(0)
+    N.check(N.lib().dcl_mask_box_ws_bytes(n, H, W, C.byref(nb)), "mask_box_ws_bytes")
+    ws = torch.empty(max(int(nb.value) // 4, 1), dtype=torch.int32, device=label.device)
+    N.check(N.lib().dcl_mask_box(N.ptr(label), n, H, W, int(value), int(padding), N.ptr(out), N.ptr(ws), C.c_int64(nb.value),
+                                 N.stream()), "mask_box")
+    return out
+
+
+def mask_box_host(label, value=1, padding=0):
+    """the host twin of mask_box (dcl_mask_box_host: same semantics, sequential, no GPU call): label (H,W) or (n,H,W)
+    integer numpy array -> (n,10) int32 numpy array."""
+    import numpy as np
+    lab = np.ascontiguousarray(np.asarray(label).astype(np.int32))
+    assert lab.ndim in (2, 3)
+    n = 1 if lab.ndim == 2 else lab.shape[0]
+    out = np.zeros((n, 10), np.int32)
+    N.check(N.lib().dcl_mask_box_host(lab.ctypes.data_as(C.c_void_p), n, lab.shape[-2], lab.shape[-1], int(value), int(padding),
+                                      out.ctypes.data_as(C.c_void_p)), "mask_box_host")
+    return out
+
+
 # ------------------------------------------------------------------------------------ training-side kernels
 def rulebook_transpose(nbr, n_out, cap_in):
     """inv[k][i] = o for nbr[k][o] = i (csrc/backward.hip); nbr (kvol, cap_out) i32 -> (kvol, cap_in) i32."""

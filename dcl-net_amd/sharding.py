@@ -92,6 +92,36 @@ class LmTable(object):
         return (float(suc.sum()) / float(num.sum()) if num.sum() else float("nan")), per
 
 
+class LmoTable(LmTable):
+    """Occlusion-LineMOD success table (tools/test_LMO.py:98-99,104-118,136-154,163-167): LmTable's counts and threshold,
+    except that a LOST detection counts as a failure instead of being dropped -- `num_count[idx] += 1` without a distance
+    ("Following HybridPose, count it on", :107-116).  The reference takes that branch for a frame whose only object is
+    lost; its collate then still carries the object's index (LM/dataloader_test_LMO.py:341-352).  Integer counts: the SUM
+    all-reduce stays exact."""
+    OBJLIST = (1, 5, 6, 8, 9, 10, 11, 12)                              # tools/test_LMO.py:68
+    SYM_IDX = (5, 6)                                                   # LM/dataloader_test_LMO.py:104: eggbox, glue
+
+    def add_lost(self, idx):
+        self.counts[idx, 0] += 1
+
+    def add_batch(self, obj_idx, dis, flags=None):
+        """one frame of the eval loop.  `flags` covers every object of the frame (-1 = lost).  A lost object is counted
+        (add_lost) when obj_idx names it too -- len(obj_idx) == len(flags), the lost-frame collate of the Occlusion-LineMOD
+        loader -- and skipped as in LmTable when obj_idx covers the detected objects only; `dis` always covers only the
+        detected ones, in order."""
+        flags = [0] * len(dis) if flags is None else [int(f) for f in flags]
+        with_lost = len(obj_idx) == len(flags)
+        k = 0
+        for j, f in enumerate(flags):
+            if f == -1:
+                if with_lost:
+                    self.add_lost(int(obj_idx[j]))
+                continue
+            self.add(int(obj_idx[j if with_lost else k]), float(dis[k]))
+            k += 1
+        assert k == len(dis)
+
+
 class AddsTable(object):
     """per-class sufficient statistics of the YCB-V ADD-S AUC / <2cm metric."""
 

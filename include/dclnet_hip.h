@@ -652,6 +652,25 @@ int dcl_crop_points(const uint16_t *depth, const int32_t *label, const uint8_t *
 int dcl_crop_sample(int n_inst, int npoint, int cap, const float *xyz, const float *rgb, const int64_t *sample_idx,
                     const int32_t *counts, int min_valid, float half_extent0, const float *unit_host, int voxel_limit,
                     float *feats, int64_t *coords, dclStream_t stream);
+/* The loaders' `get_bbox(mask_to_bbox(mask_label, padding))` (LM/dataloader_test_LMO.py:26-42,215,360-402; the LineMOD loader's
+ * eval mode, LM/dataloader_test_LM.py:144) for n label images (n,H,W) i32 (csrc/mask_box.hip; semantics: csrc/mask_box.h).
+ * A pixel is set where label == value; components are 8-connected; the winner is the component whose bounding rectangle
+ * has the largest w*h, among equal ones the one whose first pixel in raster order comes last.  out (n,10) i32:
+ *   [0:4]  box = [x - padding/2, y - padding/2, w + padding, h + padding] ([0,0,0,0] when no pixel is set)
+ *   [4:8]  the box row dcl_crop_points takes: crops.lm_box(box, H, W), then max(r0,0), min(r1,H), max(c0,0), min(c1,W)
+ *   [8]    number of components          [9]  pixel count of the winner
+ * The tie rule and "a pixel on the image border is a pixel" are ASSUMPTIONS about cv2.findContours that are not pinned
+ * against cv2 (absent where this project is built); neither matters for a mask with a unique largest rectangle away from
+ * the border.  Six launches over runs of set pixels, integer atomics only, the same bits on every call; no workgroup waits
+ * for another, nothing is read back, no allocation: capturable.  ws: dcl_mask_box_ws_bytes(n, H, W) bytes of device
+ * scratch, 4-byte aligned, sized for the worst mask (H * ceil(W/2) runs per image; 4.9 MB per 480 x 640 image), not
+ * zeroed by the caller.  dcl_mask_box_host: the same ten integers from host memory by a sequential route (the twin the
+ * tests compare the kernels with; no GPU call).  DCL_EINVAL before any device work for a null pointer of a non-empty call,
+ * H or W < 1, H*W >= 2^31 - 64, padding < 0 or a short workspace; n == 0 returns 0 and launches nothing.                  */
+int dcl_mask_box_ws_bytes(int n, int H, int W, int64_t *bytes_host);
+int dcl_mask_box(const int32_t *label, int n, int H, int W, int32_t value, int padding, int32_t *out, void *ws,
+                 int64_t ws_bytes, dclStream_t stream);
+int dcl_mask_box_host(const int32_t *label, int n, int H, int W, int32_t value, int padding, int32_t *out);
 
 /* ------------------------------------------------------------ eval metric ---
  * ADD-S per object (tools/test_YCBV_stage1.py:186-189): out[o] = mean_i min_j |R_pred x_i + t_pred - (R_gt x_j + t_gt)|
