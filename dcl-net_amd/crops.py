@@ -9,6 +9,8 @@ a seeded run consumes the global numpy RNG stream exactly like the original load
 needs the per-instance point counts on the host: the one read-back of the builder (plus the {V, maxActive} read-back of
 each voxelize_idx).  No CPU fallback: the arrays are uploaded and everything else happens on the device.
 """
+import math
+import random
 import time
 
 import numpy as np
@@ -22,6 +24,12 @@ LM_CAMERA = (325.26110, 242.04899, 572.41140, 573.57043, 1.0, 1000.0)  # LM/data
 MIN_VALID = 32                                                        # :163
 LM_MIN_VALID = 128                                                    # LM/dataloader_test_LM.py:197
 LMO_MIN_VALID = 0                                                     # LM/dataloader_test_LMO.py:262 (`np.sum(choose_idx)>0`)
+# the training loader (YCBV/dataloader_train_YCBV.py): its two cameras (cx, cy, fx, fy; :83-91 -- the second one for the real
+# sequences 0060 and later, :113-122), `minimum_num_pt` (:97) and the symmetric objects' indices obj - 1 (:98)
+YCBV_TRAIN_CAMERA_1 = (312.9869, 241.3109, 1066.778, 1067.487)
+YCBV_TRAIN_CAMERA_2 = (323.7872, 279.6921, 1077.836, 1078.189)
+TRAIN_MIN_PT = 50
+TRAIN_SYMMETRY_OBJ_IDX = (12, 15, 18, 19, 20)
 
 
 def snap_box(rois, row, img_h=480, img_w=640):
@@ -68,6 +76,59 @@ def lm_box(obj_bb, img_h=480, img_w=640):
     if c1 > img_w:
         c0, c1 = c0 - (c1 - img_w), img_w
     return r0, r1, c0, c1
+
+
+def extent_box(rmin, rmax, cmin, cmax, img_h=480, img_w=640):
+    """`get_bbox(mask_label)` of the training loader (dataloader_train_YCBV.py:280-318) from the mask's extent -- rmin, rmax, cmin,
+    cmax are the first and last set row / column, INCLUSIVE (np.where(rows)[0][[0, -1]]): sides grown to the next entry of the
+    border list (a side that equals an entry stays), the box centred on the extent and shifted back inside the loader's
+    img_h x img_w image.  Returns (rmin, rmax, cmin, cmax), the slice bounds."""
+    r0, r1, c0, c1 = int(rmin), int(rmax) + 1, int(cmin), int(cmax) + 1
+
+    def grow(v):                       # `r_b > border_list[tt] and r_b < border_list[tt + 1]` over -1, 40, 80, ... 680
+        return (v // 40 + 1) * 40 if -1 < v < 680 and (v % 40 != 0 or v == 0) else v
+    hr, hc = int(grow(r1 - r0) / 2), int(grow(c1 - c0) / 2)
+    mr, mc = int((r0 + r1) / 2), int((c0 + c1) / 2)
+    r0, r1, c0, c1 = mr - hr, mr + hr, mc - hc, mc + hc
+    if r0 < 0:
+        r0, r1 = 0, r1 - r0
+    if c0 < 0:
+        c0, c1 = 0, c1 - c0
+    if r1 > img_h:
+        r0, r1 = r0 - (r1 - img_h), img_h
+    if c1 > img_w:
+        c0, c1 = c0 - (c1 - img_w), img_w
+    return r0, r1, c0, c1
+
+
+def euler2mat(a1, a2, a3):
+    """`transforms3d.euler.euler2mat(a1, a2, a3)` with its default axes 'sxyz' (static x, y, z), taken as Rz(a3) Ry(a2) Rx(a1) in
+    float64.  transforms3d is not installed where this project is built: the convention is an ASSUMPTION that is not pinned
+    against the package.  The one place the augmentation rotation is written."""
+    c1, s1, c2, s2, c3, s3 = math.cos(a1), math.sin(a1), math.cos(a2), math.sin(a2), math.cos(a3), math.sin(a3)
+    rx = np.array([[1.0, 0.0, 0.0], [0.0, c1, -s1], [0.0, s1, c1]])
+    ry = np.array([[c2, 0.0, s2], [0.0, 1.0, 0.0], [-s2, 0.0, c2]])
+    rz = np.array([[c3, -s3, 0.0], [s3, c3, 0.0], [0.0, 0.0, 1.0]])
+    return rz @ ry @ rx
+
+
+class LoaderDraw(object):
+    """The random draws of the training loader, made on the loader's own generators with the loader's own calls
+    (dataloader_train_YCBV.py:127,162-164,172,195-198).  CropBuilder.build_train takes any object with these four methods, so
+    a test can replay recorded draws."""
+
+    def pick(self, k):
+        return int(np.random.randint(0, k))
+
+    def angles(self):
+        return [np.random.uniform(-math.pi / 36.0, math.pi / 36.0) for _ in range(3)]
+
+    def jitter(self):
+        return [random.uniform(-0.03, 0.03) for _ in range(3)]
+
+    def choice(self, m, n):
+        # choice(m, n, replace=False) through the library's walk on the same generator state (ops.legacy_choice_heads)
+        return ops.legacy_choice_heads([int(m)], n)[0] if m > n else np.random.choice(m, n)
 
 
 def _upload(a, dev):
@@ -117,6 +178,7 @@ class CropBuilder(object):
                                         int(self.limit[0]))
         self.tmp_feats = feats.view(len(self.cls_ids), self.n_tmp, 7)
         self.tmp_vox = coords.view(len(self.cls_ids), self.n_tmp, 4)[:, :, 1:].contiguous()
+        self._cad_mm, self._radius_tab = cad_points_mm, None      # build_train's per-class radius table, made on first use
         self.draw_seconds = 0.0                  # host time spent in the loader's np.random.choice draws (accumulated)
         # The template side of a batch is a function of the crops' CLASSES alone (:179-183,223): voxelise every class once
         # (device voxelize_idx, crop id 0) and keep the three maps on the host; a frame's maps are those tables put side by
@@ -269,27 +331,7 @@ class CropBuilder(object):
         data = dict(part["host"], all_flags=torch.IntTensor(flags), all_centroids=part["centroid"], labels=part["labels"],
                     counts=cnt[keep])
         _mark("sample + labels issued")
-        S = int(self.limit[0])
-        if (b <= ops.VI_CROPS_MAX_BATCH and self.n_inp <= ops.VI_CROPS_MAX_POINTS and S == ops.VI_CROPS_S and
-                self.mode in (3, 4)):
-            # the image's crops are voxelised in ONE launch (one workgroup per crop) into capacity-shaped tensors
-            occ, p2v, v2p, info = ops.voxelize_idx_crops(coords_inp, b, self.n_inp, S, self.mode, pitch=self.v2p_pitch)
-            if self.capacity:
-                # capacity form: nothing comes back to the host -- occupied_voxels / v2p_maps keep their b*n rows and `pitch`
-                # columns, the live row count stays on the device (v0_dev; Network.forward's graph path takes it as it is)
-                data["inp"] = {"feats": feats_inp, "coords": coords_inp, "occupied_voxels": occ, "p2v_maps": p2v, "v2p_maps": v2p,
-                               "v0_dev": info[0:1], "vi_info": info}
-            else:
-                V, ma, err = info.cpu().tolist()                                    # the builder's second host read-back
-                if err:      # a voxel with more points than the pitch holds (a tiny object sampled with replacement): general op
-                    occ, p2v, v2p = ops.voxelize_idx_gpu(coords_inp, b, S, self.mode)
-                    data["inp"] = {"feats": feats_inp, "coords": coords_inp, "occupied_voxels": occ, "p2v_maps": p2v, "v2p_maps": v2p}
-                else:
-                    data["inp"] = {"feats": feats_inp, "coords": coords_inp, "occupied_voxels": occ[:V], "p2v_maps": p2v,
-                                   "v2p_maps": v2p[:V, :max(ma, 1) + 1].contiguous()}
-        else:
-            occ, p2v, v2p = ops.voxelize_idx_gpu(coords_inp, b, S, self.mode)
-            data["inp"] = {"feats": feats_inp, "coords": coords_inp, "occupied_voxels": occ, "p2v_maps": p2v, "v2p_maps": v2p}
+        data["inp"] = self._inp_side(feats_inp, coords_inp, b)
         _mark("voxelisation issued")
         occ, p2v, v2p, coords_tmp = part["tmp_side"]                                # tables: no kernel, no read-back
         data["tmp"] = {"feats": feats_tmp, "coords": coords_tmp, "occupied_voxels": occ, "p2v_maps": p2v, "v2p_maps": v2p}
@@ -298,6 +340,190 @@ class CropBuilder(object):
         data["ready_event"].record(torch.cuda.current_stream(dev))
         _mark("end")
         return data
+
+    def _stack_frames(self, frames):
+        """frames -> (rgb (f,H,W,C) u8, depth (f,H,W) 16-bit storage, label (f,H,W) i32) on the device.  Frames of different
+        sizes are padded at the bottom and the right to the largest one with depth 0 and label -1 (a label outside every
+        class range takes no part anywhere; pixel coordinates do not move)."""
+        dev = self.dev
+        if torch.is_tensor(frames[0][1]):
+            Hm, Wm = max(f[1].shape[0] for f in frames), max(f[1].shape[1] for f in frames)
+
+            def pad(t, value, tail=0):
+                h, w = t.shape[0], t.shape[1]
+                if (h, w) == (Hm, Wm):
+                    return t
+                return torch.nn.functional.pad(t, (0, 0) * tail + (0, Wm - w, 0, Hm - h), value=value)
+            return (torch.stack([pad(f[0], 0, 1) for f in frames]), torch.stack([pad(f[1], 0) for f in frames]),
+                    torch.stack([pad(f[2], -1) for f in frames]))
+        Hm, Wm = max(f[1].shape[0] for f in frames), max(f[1].shape[1] for f in frames)
+        ch = frames[0][0].shape[2]
+        img = np.zeros((len(frames), Hm, Wm, ch), np.uint8)
+        dep = np.zeros((len(frames), Hm, Wm), np.uint16)
+        lab = np.full((len(frames), Hm, Wm), -1, np.int32)
+        for k, (i, d, l) in enumerate(frames):
+            h, w = d.shape
+            img[k, :h, :w], dep[k, :h, :w], lab[k, :h, :w] = i, d, l
+        return (torch.from_numpy(img).to(dev), torch.from_numpy(dep.view(np.int16)).to(dev), torch.from_numpy(lab).to(dev))
+
+    def _radius(self, cls):
+        """`radius_obj` (dataloader_train_YCBV.py:77-80): np.linalg.norm(cad / 1000, axis=1).max() per class, made on first use"""
+        if self._radius_tab is None:
+            self._radius_tab = {c: np.linalg.norm(np.asarray(p) / 1000.0, axis=1).max() for c, p in self._cad_mm.items()}
+        return self._radius_tab[cls]
+
+    def build_train(self, frames, metas, draw=None):
+        """One TRAINING batch (`Dataset.__getitem__` in 'train' mode + `collate`, YCBV/dataloader_train_YCBV.py:105-266): one
+        object per frame, the box from the mask's own extent, the cloud re-posed with the jittered ground-truth pose before the
+        unconditional grid filter, the jittered pose as the labels.
+
+        frames: a list of (img (H,W,3|4) u8, depth (H,W) u16, label (H,W) integer) numpy triples, or of resident() tensors.
+        metas:  per frame a mapping with `cls_indexes` (k class ids), `poses` (3,4,k), `factor_depth` and `camera`
+                (cx, cy, fx, fy: YCBV_TRAIN_CAMERA_1 / _2) -- the frame's meta.mat plus the loader's camera choice.
+        draw:   the source of every random number: pick(k), angles(), jitter(), choice(m, n).  Default LoaderDraw(): the loader's
+                calls on np.random and random.
+
+        ORDER OF THE DRAWS.  Frame by frame: pick() until the picked object has more than 50 valid pixels (:126-132), then --
+        unless the crop is the dummy of :139 -- angles() and jitter().  When every frame has had these, frame by frame again:
+        choice(m, input_size) for every frame that survived.  For one frame this is exactly `__getitem__`'s order on both
+        generators; for b > 1 the choice draws of all frames come after the pick / angle draws of all frames (np.random is shared
+        by pick, angles and choice, so a seeded batch differs from b seeded `__getitem__` calls in the choice draws; a test
+        that wants sample-for-sample equality replays recorded draws).  This order is what keeps a batch at two read-backs: the
+        picks need the label table, the choices need the point counts, nothing else comes back.
+
+        Host synchronisations per batch: (1) the label table, which feeds the pick loop and the boxes, (2) `counts`, which
+        feeds the choice draws; the exact-form builder adds build()'s {V, maxActive} read-back, the capacity-form one nothing.
+
+        A frame is dropped, as `collate` drops the dummy sample, when the box holds fewer than 50 masked pixels (:139) or at
+        most 50 points lie inside the grid after the re-pose (:191).  The box arithmetic is the loader's, with its 480 x 640
+        constants whatever the frame's size.
+
+        Returns collate's dict: inp / tmp {feats, occupied_voxels, p2v_maps, v2p_maps} (and coords) as build() returns them,
+        labels {rot_gt (b,3,3), trans_gt (b,3), obj_idx (b,1) i32}, flags (b) and radius (b,1) float32 -- CUDA tensors --
+        batch_offsets and voxel_num_limit (host, as build()), and beside collate's keys: kept (f) bool numpy, obj (f) the
+        picked class ids, boxes (f,4), counts and centroids of the kept crops."""
+        draw = LoaderDraw() if draw is None else draw
+        dev = self.dev
+        nf = len(frames)
+        if nf == 0 or len(metas) != nf:
+            raise ValueError("build_train: one meta per frame, at least one frame")
+        n_cls = max(self.cls_ids) + 1
+        i_t, d_t, l_t = self._stack_frames(frames)
+        Hm, Wm = d_t.shape[1], d_t.shape[2]
+        tab_t = ops.label_table(l_t, d_t, n_cls)
+        if Hm > 480 or Wm > 640:
+            # a frame larger than the loader's image: get_bbox pushes the box back inside 480 x 640, where it still covers the
+            # part of the mask that lies there -- so the masked pixels of the BOX (:138) are the mask's pixels in that window
+            win_t = ops.label_table(l_t[:, :480, :640].contiguous(), d_t[:, :480, :640].contiguous(), n_cls)
+            both = torch.stack([tab_t, win_t]).cpu().numpy()                         # host read-back 1 of 2
+            tab, win = both[0], both[1]
+        else:
+            tab = win = tab_t.cpu().numpy()                                           # host read-back 1 of 2
+        kept = np.zeros(nf, bool)
+        obj_of, boxes = np.zeros(nf, np.int32), np.zeros((nf, 4), np.int32)
+        src, cams, R0s, ts, jits, augs = [], [], [], [], [], []
+        for f, meta in enumerate(metas):
+            obj = np.asarray(meta["cls_indexes"]).flatten().astype(np.int32)
+            valid = [int(tab[f, c, 0]) if 0 <= c < n_cls else 0 for c in obj]
+            if not valid or max(valid) <= TRAIN_MIN_PT:
+                raise ValueError("build_train: no object of frame %d has more than %d valid pixels (the loader would draw "
+                                 "for ever)" % (f, TRAIN_MIN_PT))
+            while True:                                                               # :126-132
+                idx = draw.pick(len(obj))
+                if valid[idx] > TRAIN_MIN_PT:
+                    break
+            c = int(obj[idx])
+            obj_of[f] = c
+            r0, r1, c0, c1 = extent_box(*tab[f, c, 1:5])
+            boxes[f] = (r0, r1, c0, c1)
+            if win[f, c, 0] < TRAIN_MIN_PT:                                           # :139, before any further draw
+                continue
+            self.cls_row[c]                                                           # a class without a CAD cloud: KeyError, as :179
+            a1, a2, a3 = draw.angles()                                                # :162-164
+            jit = draw.jitter()                                                       # :172
+            P = np.asarray(meta["poses"], np.float64)[:, :, idx]
+            kept[f] = True
+            src.append((max(r0, 0), min(r1, Hm), max(c0, 0), min(c1, Wm), c, f))      # numpy slice clipping (:138)
+            cams.append(tuple(meta["camera"])[:4] + (float(np.asarray(meta["factor_depth"]).reshape(-1)[0]),))
+            R0s.append(P[:, 0:3])
+            ts.append(P[:, 3])
+            jits.append(jit)
+            augs.append(euler2mat(a1, a2, a3))
+        cand = np.nonzero(kept)[0]
+        out = {"batch_offsets": None, "voxel_num_limit": torch.tensor(self.limit), "kept": kept, "obj": obj_of, "boxes": boxes}
+        if cand.size == 0:
+            return dict(out, flags=torch.zeros(0, device=dev), batch_offsets=torch.zeros(1).int())
+        src_a = np.asarray(src, np.int32)
+        src_t, cam_t = _upload(src_a, dev), _upload(np.asarray(cams, np.float32), dev)
+        pose_t = _upload(ops.pose_rows(R0s, ts, jits, augs), dev)
+        cap = max(1, int(((src_a[:, 1] - src_a[:, 0]).clip(0) * (src_a[:, 3] - src_a[:, 2]).clip(0)).max()))
+        xyz, col, centroid, counts, rot_gt, trans_gt = ops.crop_points_posed(
+            d_t, l_t, i_t, src_a[:, 5], src_t, cam_t, pose_t, RGB_MEAN, self.extent * 0.5, TRAIN_MIN_PT, cap=cap)
+
+        def count_free_part(keep):
+            # what does not depend on the point counts, issued while the crop kernels run (as in build())
+            cls = [int(obj_of[cand[k]]) for k in keep]
+            rows = [self.cls_row[c] for c in cls]
+            cls_rows = _upload(np.asarray(rows, np.int64), dev)
+            small = np.array([[float(c - 1 in TRAIN_SYMMETRY_OBJ_IDX), self._radius(c), c - 1] for c in cls], np.float32)
+            small_t = _upload(small, dev)
+            return {"feats_tmp": self.tmp_feats[cls_rows].reshape(len(keep) * self.n_tmp, 7),
+                    "tmp_side": self._template_side(rows), "flags": small_t[:, 0].contiguous(),
+                    "radius": small_t[:, 1:2].contiguous(), "obj_idx": small_t[:, 2:3].int()}
+        part = count_free_part(list(range(cand.size)))
+        cnt = counts.cpu().numpy()                                                    # host read-back 2 of 2
+        keep = [k for k in range(cand.size) if cnt[k, 2] > 0]                         # :191: more than 50 points inside the grid
+        for k in range(cand.size):
+            kept[cand[k]] = cnt[k, 2] > 0
+        if not keep:
+            return dict(out, flags=torch.zeros(0, device=dev), batch_offsets=torch.zeros(1).int())
+        t_draw = time.perf_counter()
+        picks = [np.asarray(draw.choice(int(cnt[k, 2]), self.n_inp)) for k in keep]  # :195-198
+        self.draw_seconds += time.perf_counter() - t_draw
+        if len(keep) != cand.size:
+            kt = _upload(np.asarray(keep, np.int64), dev)
+            xyz, col, centroid = xyz[kt].contiguous(), col[kt].contiguous(), centroid[kt]
+            rot_gt, trans_gt = rot_gt[kt].contiguous(), trans_gt[kt].contiguous()
+            part = count_free_part(keep)
+        pick_t = _upload(np.stack(picks).astype(np.int64), dev)
+        # no clamp: the filter was applied, every point lies inside the grid (:203)
+        feats_inp, coords_inp = ops.crop_sample(xyz, col, pick_t, None, self.extent[0] * 0.5, self.unit, int(self.limit[0]))
+        b = len(keep)
+        out["inp"] = self._inp_side(feats_inp, coords_inp, b)
+        occ, p2v, v2p, coords_tmp = part["tmp_side"]
+        out["tmp"] = {"feats": part["feats_tmp"], "coords": coords_tmp, "occupied_voxels": occ, "p2v_maps": p2v, "v2p_maps": v2p}
+        out["labels"] = {"rot_gt": rot_gt, "trans_gt": trans_gt, "obj_idx": part["obj_idx"]}
+        out["batch_offsets"] = (torch.arange(b + 1) * self.n_inp).int()
+        out["flags"], out["radius"] = part["flags"], part["radius"]
+        out["counts"], out["centroids"] = cnt[keep], centroid
+        out["ready_event"] = torch.cuda.Event()
+        out["ready_event"].record(torch.cuda.current_stream(dev))
+        return out
+
+    def _inp_side(self, feats_inp, coords_inp, b):
+        """the observed side of a batch of b crops from its sampled feats rows and voxelize_idx input rows: capacity form
+        (no read-back) or exact form (the {V, maxActive} read-back), see __init__"""
+        S = int(self.limit[0])
+        if (b <= ops.VI_CROPS_MAX_BATCH and self.n_inp <= ops.VI_CROPS_MAX_POINTS and S == ops.VI_CROPS_S and
+                self.mode in (3, 4)):
+            # the image's crops are voxelised in ONE launch (one workgroup per crop) into capacity-shaped tensors
+            occ, p2v, v2p, info = ops.voxelize_idx_crops(coords_inp, b, self.n_inp, S, self.mode, pitch=self.v2p_pitch)
+            if self.capacity:
+                # capacity form: nothing comes back to the host -- occupied_voxels / v2p_maps keep their b*n rows and `pitch`
+                # columns, the live row count stays on the device (v0_dev; Network.forward's graph path takes it as it is)
+                return {"feats": feats_inp, "coords": coords_inp, "occupied_voxels": occ, "p2v_maps": p2v, "v2p_maps": v2p,
+                        "v0_dev": info[0:1], "vi_info": info}
+            else:
+                V, ma, err = info.cpu().tolist()                                    # the builder's second host read-back
+                if err:      # a voxel with more points than the pitch holds (a tiny object sampled with replacement): general op
+                    occ, p2v, v2p = ops.voxelize_idx_gpu(coords_inp, b, S, self.mode)
+                    return {"feats": feats_inp, "coords": coords_inp, "occupied_voxels": occ, "p2v_maps": p2v, "v2p_maps": v2p}
+                else:
+                    return {"feats": feats_inp, "coords": coords_inp, "occupied_voxels": occ[:V], "p2v_maps": p2v,
+                            "v2p_maps": v2p[:V, :max(ma, 1) + 1].contiguous()}
+        else:
+            occ, p2v, v2p = ops.voxelize_idx_gpu(coords_inp, b, S, self.mode)
+            return {"feats": feats_inp, "coords": coords_inp, "occupied_voxels": occ, "p2v_maps": p2v, "v2p_maps": v2p}
 
     def build_lm(self, img, depth, mask_label, obj_bb=None, obj=None, eval_mode=False):
         """One LineMOD sample (`PoseDataset.__getitem__`, LM/dataloader_test_LM.py:116-214, test / eval modes): img (H,W,3+) u8,

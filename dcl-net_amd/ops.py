@@ -1424,6 +1424,107 @@ def mask_box_host(label, value=1, padding=0):
     return out
 
 
+def label_table(label, depth, n_classes):
+    """Per-frame class table of the training loader (csrc/crops_train.hip: dcl_label_table).  label (n,H,W) i32 CUDA, depth
+    (n,H,W) 16-bit storage CUDA -> (n, n_classes, 5) i32 CUDA: [pixels with label == c and depth != 0, min row, max row,
+    min col, max col of label == c]; an absent class has count 0, min = 2^31 - 1 and max = -1.  No host synchronisation."""
+    N.need_cuda(label, depth)
+    assert label.dtype == torch.int32 and depth.dtype in (torch.int16, torch.uint16) and label.dim() == 3
+    assert label.is_contiguous() and depth.is_contiguous() and depth.shape == label.shape
+    n, H, W = label.shape
+    out = torch.empty((n, int(n_classes), 5), dtype=torch.int32, device=label.device)
+    N.check(N.lib().dcl_label_table(N.ptr(label), N.ptr(depth), n, H, W, int(n_classes), N.ptr(out), N.stream()), "label_table")
+    return out
+
+
+def label_table_host(label, depth, n_classes):
+    """the host twin of label_table (dcl_label_table_host, plain C++, no GPU call): (n,H,W) integer numpy arrays ->
+    (n, n_classes, 5) int32 numpy array."""
+    import numpy as np
+    lab = np.ascontiguousarray(np.asarray(label).astype(np.int32))
+    dep = np.ascontiguousarray(np.asarray(depth).astype(np.uint16))
+    assert lab.ndim == 3 and dep.shape == lab.shape
+    n, H, W = lab.shape
+    out = np.zeros((n, int(n_classes), 5), np.int32)
+    N.check(N.lib().dcl_label_table_host(lab.ctypes.data_as(C.c_void_p), dep.ctypes.data_as(C.c_void_p), n, H, W, int(n_classes),
+                                         out.ctypes.data_as(C.c_void_p)), "label_table_host")
+    return out
+
+
+def pose_rows(R0, t_gt, jitter, aug_r):
+    """The pose rows dcl_crop_points_posed takes (include/dclnet_hip.h: 112 bytes per crop): R0 (n,3,3) and aug_r (n,3,3)
+    rounded to float32, t_gt (n,3) kept float64, jitter (n,3) rounded to float32 -> (n,112) uint8 numpy array."""
+    import numpy as np
+    n = len(R0)
+    rows = np.zeros(n, POSE_ROW)
+    rows["t_gt"], rows["R0"] = np.asarray(t_gt, np.float64).reshape(n, 3), np.asarray(R0).astype(np.float32).reshape(n, 3, 3)
+    rows["j"], rows["A"] = np.asarray(jitter).astype(np.float32).reshape(n, 3), np.asarray(aug_r).astype(np.float32).reshape(n, 3, 3)
+    return rows.view(np.uint8).reshape(n, POSE_ROW_BYTES)
+
+
+POSE_ROW_BYTES = 112
+POSE_ROW = [("t_gt", "<f8", (3,)), ("R0", "<f4", (3, 3)), ("j", "<f4", (3,)), ("A", "<f4", (3, 3)), ("pad", "<f4")]
+
+
+def crop_points_posed(depth, label, rgb, frame_idx, src, cams, pose, rgb_mean, half_extent, min_valid=50, cap=None):
+    """The training loader's masked back-projection, centring, re-pose and grid filter (YCBV/dataloader_train_YCBV.py:138-193;
+    csrc/crops_train.hip).  depth / label (f,H,W), rgb (f,H,W,C) stacked frames; frame_idx: the crops' frames as a HOST
+    sequence (checked against f by the call); src (n,6) i32 [rmin,rmax,cmin,cmax,class,frame], cams (n,5) f32
+    [cx,cy,fx,fy,scale], pose (n,112) u8 (pose_rows) -- all CUDA.  -> xyz (n,cap,3) re-posed points inside the grid, rgb
+    (n,cap,3), centroid (n,3), counts (n,3) i32 [masked, inside the grid, rows: 0 unless more than min_valid are inside],
+    rot_gt (n,3,3), trans_gt (n,3).  No host synchronisation when cap is given."""
+    import numpy as np
+    N.need_cuda(depth, label, rgb, src, cams, pose)
+    assert depth.dtype in (torch.int16, torch.uint16) and label.dtype == torch.int32 and rgb.dtype == torch.uint8
+    assert depth.dim() == 3 and label.shape == depth.shape and rgb.dim() == 4 and rgb.shape[:3] == depth.shape
+    assert depth.is_contiguous() and label.is_contiguous() and rgb.is_contiguous()
+    n = src.shape[0]
+    assert src.dtype == torch.int32 and src.is_contiguous() and tuple(src.shape) == (n, 6)
+    assert cams.dtype == torch.float32 and cams.is_contiguous() and tuple(cams.shape) == (n, 5)
+    assert pose.dtype == torch.uint8 and pose.is_contiguous() and tuple(pose.shape) == (n, POSE_ROW_BYTES)
+    fidx = np.ascontiguousarray(np.asarray(frame_idx, np.int32).reshape(-1))
+    assert fidx.shape[0] == n
+    f, H, W = depth.shape
+    dev = depth.device
+    if cap is None:
+        bx = src.cpu()
+        cap = int(max(1, ((bx[:, 1] - bx[:, 0]).clamp(min=0) * (bx[:, 3] - bx[:, 2]).clamp(min=0)).max().item())) if n else 1
+    raw_xyz = torch.empty((n, cap, 3), dtype=torch.float32, device=dev)
+    raw_rgb = torch.empty((n, cap, 3), dtype=torch.float32, device=dev)
+    xyz = torch.empty((n, cap, 3), dtype=torch.float32, device=dev)
+    col = torch.empty((n, cap, 3), dtype=torch.float32, device=dev)
+    centroid = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    counts = torch.zeros((n, 3), dtype=torch.int32, device=dev)
+    rot_gt = torch.empty((n, 3, 3), dtype=torch.float32, device=dev)
+    trans_gt = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    ws_ints = C.c_int64(0)
+    N.check(N.lib().dcl_crop_points_ws_ints(n, int(cap), C.byref(ws_ints)), "crop_points_ws_ints")
+    ws = torch.empty(max(int(ws_ints.value), 1), dtype=torch.int32, device=dev)
+    mean_a = (C.c_double * 3)(*[float(v) for v in rgb_mean])
+    he_a = (C.c_float * 3)(*[float(v) for v in half_extent])
+    N.check(N.lib().dcl_crop_points_posed(N.ptr(depth), N.ptr(label), N.ptr(rgb), f, H, W, rgb.shape[3], n,
+                                          fidx.ctypes.data_as(C.c_void_p), N.ptr(src), N.ptr(cams), N.ptr(pose), mean_a, he_a,
+                                          int(min_valid), int(cap), N.ptr(raw_xyz), N.ptr(raw_rgb), N.ptr(xyz), N.ptr(col),
+                                          N.ptr(centroid), N.ptr(counts), N.ptr(rot_gt), N.ptr(trans_gt), N.ptr(ws), N.stream()),
+            "crop_points_posed")
+    return xyz, col, centroid, counts, rot_gt, trans_gt
+
+
+def crop_repose_host(points, pose_row, centroid):
+    """the host twin of the re-pose (dcl_crop_repose_host, plain C++ with the library's -ffp-contract=off): CENTRED points
+    (n,3) float32, one pose row (112 bytes, pose_rows), centroid (3) float32 -> (re-posed points (n,3), R1 (3,3), t1 (3))."""
+    import numpy as np
+    pts = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+    row = np.ascontiguousarray(np.asarray(pose_row, np.uint8).reshape(-1))
+    cen = np.ascontiguousarray(np.asarray(centroid, np.float32).reshape(3))
+    assert row.shape[0] == POSE_ROW_BYTES
+    out, R1, t1 = np.empty_like(pts), np.empty((3, 3), np.float32), np.empty(3, np.float32)
+    N.check(N.lib().dcl_crop_repose_host(pts.ctypes.data_as(C.c_void_p), row.ctypes.data_as(C.c_void_p),
+                                         cen.ctypes.data_as(C.c_void_p), pts.shape[0], out.ctypes.data_as(C.c_void_p),
+                                         R1.ctypes.data_as(C.c_void_p), t1.ctypes.data_as(C.c_void_p)), "crop_repose_host")
+    return out, R1, t1
+
+
 # ------------------------------------------------------------------------------------ training-side kernels
 def rulebook_transpose(nbr, n_out, cap_in):
     """inv[k][i] = o for nbr[k][o] = i (csrc/backward.hip); nbr (kvol, cap_out) i32 -> (kvol, cap_in) i32."""

@@ -672,6 +672,52 @@ int dcl_mask_box(const int32_t *label, int n, int H, int W, int32_t value, int p
                  int64_t ws_bytes, dclStream_t stream);
 int dcl_mask_box_host(const int32_t *label, int n, int H, int W, int32_t value, int padding, int32_t *out);
 
+/* ---- the TRAINING loader's front end (YCBV/dataloader_train_YCBV.py:105-210; csrc/crops_train.hip)
+ * Per-frame class table: for every frame of label (n,H,W) i32 / depth (n,H,W) u16 and every class id c in [0, n_classes),
+ * out[frame][c] = { pixels with label == c && depth != 0 (`len(mask.nonzero()[0])`, :128-131),
+ *                   min row, max row, min col, max col of label == c -- the LABEL alone, what get_bbox(mask_label) reduces
+ *                   (:134,280-285) }.
+ * An absent class: count 0, min = INT32_MAX, max = -1 (empty extent, min > max).  Labels outside [0, n_classes) take no
+ * part and are never an address.  Two launches (identity fill; one pass over the pixels with per-workgroup tables in LDS
+ * merged by integer atomics), integers only, no workgroup waits for another, nothing is read back: capturable, the same
+ * bits on every call.  DCL_EINVAL before any device work: n < 0, H or W < 1, H*W >= 2^31 - 64, n_classes outside
+ * [1, 256], a null pointer of a non-empty call; n == 0 returns 0.  dcl_label_table_host: the same integers from host
+ * memory in plain C++ (no GPU call).                                                                                     */
+int dcl_label_table(const int32_t *label, const uint16_t *depth, int n, int H, int W, int n_classes, int32_t *out,
+                    dclStream_t stream);
+int dcl_label_table_host(const int32_t *label, const uint16_t *depth, int n, int H, int W, int n_classes, int32_t *out);
+/* dcl_crop_points for the training loader: the same masked back-projection, row-order centroid and ordered compaction, with
+ *   per-crop source   crop i reads frame src[i][5] of the stacked depth / label (n_frames,H,W) and rgb (n_frames,H,W,C)
+ *                     tensors; src (n_inst,6) i32 DEVICE rows {rmin, rmax, cmin, cmax, class id, frame}.  frame_idx_host
+ *                     (n_inst) is the HOST copy of column 5: the call checks it against n_frames before any device work;
+ *                     a device row that disagrees and names no frame gives an empty crop, never an address.
+ *   per-crop camera   cams (n_inst,5) f32 DEVICE rows {cx, cy, fx, fy, depth scale} (:113-122,150)
+ *   per-crop pose row pose (n_inst) DEVICE rows of DCL_CROP_POSE_ROW_BYTES = 112 bytes, little endian:
+ *                       [  0: 24)  t_gt  3 x f64   meta['poses'][:, 3, idx]             (:136)
+ *                       [ 24: 60)  R0    9 x f32   meta['poses'][:, 0:3, idx], row major (:135,169)
+ *                       [ 60: 72)  j     3 x f32   the translation jitter                (:172)
+ *                       [ 72:108)  A     9 x f32   aug_r = euler2mat(a1, a2, a3)         (:162-166)
+ *                       [108:112)  padding
+ * After the centroid one lane per crop forms t0 = f32(t_gt - f64(centroid)) (:159,168), t1 = t0 + j (:172) and
+ * R1 = R0 A (:173); every centred point p goes through the loader's re-pose (:171-174) in float32, uncontracted, in this
+ * order:  d = p - t0;  q_j = (d0 R0[0][j] + d1 R0[1][j]) + d2 R0[2][j];  r_i = (q0 R1[i][0] + q1 R1[i][1]) + q2 R1[i][2];
+ * p' = r + t1  (R1[i][j] = (R0[i][0] A[0][j] + R0[i][1] A[1][j]) + R0[i][2] A[2][j]).  The grid filter |p'| < half_extent
+ * (strict, :189) is ALWAYS applied, in order.  counts (n_inst,3) = {masked pixels of the box, points inside the grid, rows
+ * written}; rows written = points inside the grid when there are more than min_valid (50, :191) of them, else 0 (the
+ * loader's dummy sample).  rot_gt (n_inst,3,3) = R1, trans_gt (n_inst,3) = t1 (zeros for an empty mask).  out_xyz holds p'.
+ * Other arguments, scratch and ws as dcl_crop_points (dcl_crop_points_ws_ints).  The pose never visits the host.
+ * dcl_crop_repose_host: the arithmetic above in plain C++ for n CENTRED points (n,3) of one crop: out_xyz (n,3) = p' of
+ * every point (unfiltered), out_R1 (9), out_t1 (3).                                                                      */
+#define DCL_CROP_POSE_ROW_BYTES 112
+int dcl_crop_points_posed(const uint16_t *depth, const int32_t *label, const uint8_t *rgb, int n_frames, int H, int W,
+                          int rgb_channels, int n_inst, const int32_t *frame_idx_host, const int32_t *src,
+                          const float *cams, const void *pose, const double *rgb_mean_host,
+                          const float *half_extent_host, int min_valid, int cap, float *raw_xyz, float *raw_rgb,
+                          float *out_xyz, float *out_rgb, float *centroid, int32_t *counts, float *rot_gt,
+                          float *trans_gt, int32_t *ws, dclStream_t stream);
+int dcl_crop_repose_host(const float *points, const void *pose_row, const float *centroid, int n, float *out_xyz,
+                         float *out_R1, float *out_t1);
+
 /* ------------------------------------------------------------ eval metric ---
  * ADD-S per object (tools/test_YCBV_stage1.py:186-189): out[o] = mean_i min_j |R_pred x_i + t_pred - (R_gt x_j + t_gt)|
  * over the P points of the object's class cloud.  cld (n_clouds, P, 3); cls i32[b] selects the cloud of object o
