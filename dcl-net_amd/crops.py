@@ -30,6 +30,12 @@ YCBV_TRAIN_CAMERA_1 = (312.9869, 241.3109, 1066.778, 1067.487)
 YCBV_TRAIN_CAMERA_2 = (323.7872, 279.6921, 1077.836, 1078.189)
 TRAIN_MIN_PT = 50
 TRAIN_SYMMETRY_OBJ_IDX = (12, 15, 18, 19, 20)
+# the LineMOD training loader (LM/dataloader_train_LM.py): its object list (:43), the symmetric objects' indices IN that list
+# (:120,195: objects 10 and 11), the in-grid point threshold (:201) and the mask sum below which an occlusion is undone (:343)
+LM_OBJLIST = (1, 2, 4, 5, 6, 8, 9, 10, 11, 12, 13, 14, 15)
+LM_TRAIN_SYMMETRY_OBJ_IDX = (7, 8)
+LM_TRAIN_MIN_PT = 128
+LM_OCCLUDE_MIN_SUM = 20
 
 
 def snap_box(rois, row, img_h=480, img_w=640):
@@ -112,10 +118,68 @@ def euler2mat(a1, a2, a3):
     return rz @ ry @ rx
 
 
+def lm_paste_plan(H, W, own_extent, other_extent, start_y, start_x, other_channels=3):
+    """The slicing of `occlude_with_another_object` (LM/dataloader_train_LM.py:307-334) on two mask extents and the two drawn
+    starts, bug for bug -> the plan row ops.occlude_paste takes (ops.PASTE_PLAN; `other` 0 and the crop box empty: the caller's),
+    or None where the loader ends in its `except:` and returns the originals.
+
+    own_extent / other_extent: (min row, max row, min col, max col) of channel 0 of this frame's and the occluder's mask, as
+    ops.mask_extent gives them; an empty mask (max < min) -> None (`np.min` of an empty array raises, before any draw).
+    The patch is the occluder's extent rectangle.  What the loader then does: a patch that starts above row 0 loses its first
+    rows, one that ends below row H its last ones (:315-324) -- and the same two trims are applied for x, but BOTH slice ROWS of
+    the patch again (columns are never trimmed) and the x-limit is H (`image.shape[0]`), not W (:325-334).  Negative slice
+    lengths mean what Python slicing means: the rows are tracked as a `range` sliced the way the loader slices its arrays.
+    The target rectangle is image[start_y:end_y, start_x:end_x] as numpy clips it.  The paste happens iff the patch broadcasts
+    to the target: per axis equal, or a patch axis of 1, which repeats (rep_y / rep_x).  Anything else raises in the loader
+    (:336); so does an occluder colour image with other than 3 channels (:338, after the draws)."""
+    ymin, ymax, xmin, xmax = (int(v) for v in own_extent)
+    oy0, oy1, ox0, ox1 = (int(v) for v in other_extent)
+    if ymax < ymin or xmax < xmin or oy1 < oy0 or ox1 < ox0:
+        return None
+    start_y, start_x = int(start_y), int(start_x)
+    oh, ow = oy1 - oy0 + 1, ox1 - ox0 + 1
+    rows = range(oh)                                   # the rows of the patch that are left
+    end_y, end_x = start_y + oh, start_x + ow
+    if start_y < 0:
+        rows, start_y = rows[-start_y:], 0
+    if end_y > H:
+        end_y = H
+        rows = rows[:end_y - start_y]
+    if start_x < 0:
+        rows, start_x = rows[-start_x:], 0             # :326-328 slice axis 0
+    if end_x > H:                                      # :330 compares with image.shape[0]
+        end_x = H
+        rows = rows[:end_x - start_x]                  # :332-334 slice axis 0
+    ty, tx = range(H)[start_y:end_y], range(W)[start_x:end_x]
+    ph, pw, th, tw = len(rows), ow, len(ty), len(tx)
+    if not ((ph == th or ph == 1) and (pw == tw or pw == 1)) or other_channels != 3:
+        return None
+    row = np.zeros(ops.PASTE_PLAN_INTS, np.int32)
+    row[0] = 1
+    row[2], row[3], row[4], row[5] = oy0 + (rows[0] if ph else 0), ox0, ph, pw
+    row[6], row[7], row[8], row[9] = (ty[0] if th else 0), (tx[0] if tw else 0), th, tw
+    row[10], row[11] = int(ph == 1 and th != 1), int(pw == 1 and tw != 1)
+    return row
+
+
+def lm_other_index(dict_index_objs, obj):
+    """`get_other_idx` (LM/dataloader_train_LM.py:286-291): a frame index outside the block [start, stop) of `obj`, drawn
+    with random.choice.  The loader builds the list of all other indices; indexing a `range` of the same length draws the same
+    number from Python's generator, and the position maps to the same index."""
+    start, stop = dict_index_objs[obj][0], dict_index_objs[obj][1]
+    length_all = dict_index_objs[15][1]
+    k = random.choice(range(start + max(length_all - stop, 0)))
+    return k if k < start else stop + (k - start)
+
+
 class LoaderDraw(object):
-    """The random draws of the training loader, made on the loader's own generators with the loader's own calls
-    (dataloader_train_YCBV.py:127,162-164,172,195-198).  CropBuilder.build_train takes any object with these four methods, so
-    a test can replay recorded draws."""
+    """The random draws of the training loaders, made on the loaders' own generators with the loaders' own calls
+    (dataloader_train_YCBV.py:127,162-164,172,195-198; LM/dataloader_train_LM.py:311,313,180-182,186,205-208).
+    CropBuilder.build_train / build_train_lm take any object with these methods, so a test can replay recorded draws."""
+
+    def paste(self, lo_y, hi_y, lo_x, hi_x):
+        start_y = int(np.random.randint(lo_y, hi_y))
+        return start_y, int(np.random.randint(lo_x, hi_x))
 
     def pick(self, k):
         return int(np.random.randint(0, k))
@@ -496,6 +560,167 @@ class CropBuilder(object):
         out["batch_offsets"] = (torch.arange(b + 1) * self.n_inp).int()
         out["flags"], out["radius"] = part["flags"], part["radius"]
         out["counts"], out["centroids"] = cnt[keep], centroid
+        out["ready_event"] = torch.cuda.Event()
+        out["ready_event"].record(torch.cuda.current_stream(dev))
+        return out
+
+    @staticmethod
+    def resident_lm(img, depth, mask, device="cuda"):
+        """upload one LineMOD training frame (or occluder frame) in the layout build_train_lm wants: u8 colour, depth as
+        16-bit storage, the (H,W,3) u8 mask"""
+        dev = torch.device(device)
+        return (torch.from_numpy(np.ascontiguousarray(img)).to(dev),
+                torch.from_numpy(np.ascontiguousarray(depth).astype(np.uint16).view(np.int16)).to(dev),
+                torch.from_numpy(np.ascontiguousarray(mask).astype(np.uint8)).to(dev))
+
+    def build_train_lm(self, samples, draw=None):
+        """One LineMOD TRAINING batch (`Dataset.__getitem__` in 'train' mode, `occlude_with_another_object` and `collate`,
+        LM/dataloader_train_LM.py:125-348): the object of another frame pasted over this frame's colour, depth and mask, the
+        box from `obj_bb`, the cloud re-posed in FLOAT64 with the jittered ground-truth pose before the unconditional grid
+        filter, the jittered pose as the labels.  The builder must have been made with camera=LM_CAMERA.
+
+        samples: per frame a mapping with `img` (H,W,3+) u8, `depth` (H,W) u16 millimetres, `mask` (H,W,3) u8 (numpy arrays, or
+                 the CUDA tensors of resident_lm), `obj` (class id), `obj_bb` [x, y, w, h], `cam_R_m2c` (9), `cam_t_m2c` (3,
+                 millimetres) and `other`: None or the occluder frame's (img, depth, mask).  Which meta entry and which other
+                 frame (lm_other_index) is dataset I/O: the caller's.  All frames have one size.
+        draw:    paste(lo_y, hi_y, lo_x, hi_x), angles(), jitter(), choice(m, n).  Default LoaderDraw().
+
+        ORDER OF THE DRAWS.  Frame by frame paste() -- where an occluder was given and neither mask is empty (:301-313) --;
+        then, frame by frame, angles() and jitter() for every frame whose box holds a valid pixel after the paste (:157-159);
+        then, frame by frame, choice(m, input_size) for every frame with more than 128 points inside the grid (:201-208).  For
+        one frame this is `__getitem__`'s own order on both generators (the caller draws the other index first); for b > 1
+        the three groups are batched per group: np.random is shared by all three, so a seeded batch differs from b seeded
+        `__getitem__` calls (a test that wants sample-for-sample equality replays recorded draws).
+
+        Host synchronisations per batch, and why three: (1) the mask extents and sums -- the paste draws' ranges are the
+        extents; (2) the pasted frames' valid-pixel counts -- the loader draws its pose jitter only for a non-empty crop, and
+        the count depends on the commit / roll-back the device decided; (3) `counts`, which feeds the choice draws.  The
+        exact-form builder adds build()'s {V, maxActive} read-back.
+
+        Returns collate's dict under its key names: inp / tmp {feats, occupied_voxels, p2v_maps, v2p_maps} (and coords), labels
+        {rot_gt (b,3,3), trans_gt (b,3)}, flags (b) the symmetry flags, obj_idx (b) i32 index in LM_OBJLIST, centriods (b,3)
+        (sic) -- CUDA tensors --, batch_offsets and voxel_num_limit (host); beside them kept (f) bool, occluded (f) bool (the
+        composite was kept), boxes (f,4), counts of the kept crops, ready_event.  An all-dummy batch: as build_train."""
+        draw = LoaderDraw() if draw is None else draw
+        dev = self.dev
+        nf = len(samples)
+        if nf == 0:
+            raise ValueError("build_train_lm: at least one frame")
+        if self.camera != tuple(LM_CAMERA):
+            raise ValueError("build_train_lm: the builder must be made with camera=LM_CAMERA")
+        # ---- 1. stack and upload; the extents of own and occluder masks in one call
+        with_other = [f for f, s in enumerate(samples) if s.get("other") is not None]
+        other_of = {f: k for k, f in enumerate(with_other)}
+        shape = tuple(samples[0]["depth"].shape)
+        H, W = shape
+        others = [samples[f]["other"] for f in with_other]
+        other_ch = [int(o[0].shape[2]) for o in others]
+        for s in samples:
+            if tuple(s["depth"].shape) != shape or tuple(s["mask"].shape) != shape + (3,):
+                raise ValueError("build_train_lm: every frame has the same size and an (H,W,3) mask")
+        if torch.is_tensor(samples[0]["depth"]):
+            i_t = torch.stack([s["img"] for s in samples])
+            d_t = torch.stack([s["depth"] for s in samples])
+            m_t = torch.stack([s["mask"] for s in samples] + [o[2] for o in others])
+            zero = torch.zeros((H, W, 3), dtype=torch.uint8, device=dev)
+            oi_t = torch.stack([o[0] if c == 3 else zero for o, c in zip(others, other_ch)]) if others else torch.zeros((0, H, W, 3), dtype=torch.uint8, device=dev)
+            od_t = torch.stack([o[1] for o in others]) if others else torch.zeros((0, H, W), dtype=d_t.dtype, device=dev)
+        else:
+            i_t = torch.from_numpy(np.stack([np.asarray(s["img"], np.uint8) for s in samples])).to(dev)
+            d_t = torch.from_numpy(np.stack([np.asarray(s["depth"]).astype(np.uint16) for s in samples]).view(np.int16)).to(dev)
+            m_t = torch.from_numpy(np.stack([np.asarray(s["mask"], np.uint8) for s in samples] +
+                                            [np.asarray(o[2], np.uint8) for o in others])).to(dev)
+            oi = np.zeros((len(others), H, W, 3), np.uint8)
+            od = np.zeros((len(others), H, W), np.uint16)
+            for k, (o, c) in enumerate(zip(others, other_ch)):
+                if c == 3:
+                    oi[k] = o[0]
+                od[k] = o[1]
+            oi_t, od_t = torch.from_numpy(oi).to(dev), torch.from_numpy(od.view(np.int16)).to(dev)
+        ext_t = ops.mask_extent(m_t)
+        ext = ext_t.cpu().numpy()                                                     # host read-back 1 of 3
+        # ---- 2. the paste draws and plans, the boxes
+        plans = np.zeros((nf, ops.PASTE_PLAN_INTS), np.int32)
+        boxes = np.zeros((nf, 4), np.int32)
+        for f, s in enumerate(samples):
+            r0, r1, c0, c1 = lm_box([int(v) for v in s["obj_bb"]])
+            boxes[f] = (r0, r1, c0, c1)
+            k = other_of.get(f)
+            if k is not None:
+                own, oth = ext[f, :4], ext[nf + k, :4]
+                if own[1] >= own[0] and oth[1] >= oth[0]:                             # both masks non-empty (:301-306)
+                    oh, ow = int(oth[1] - oth[0]) + 1, int(oth[3] - oth[2]) + 1
+                    sy, sx = draw.paste(int(own[0]) - oh + 1, int(own[1]) + 1, int(own[2]) - ow + 1, int(own[3]) + 1)   # :311,313
+                    row = lm_paste_plan(H, W, own, oth, sy, sx, other_ch[k])
+                    if row is not None:
+                        plans[f] = row
+                        plans[f, 1] = k
+            plans[f, 12:16] = (min(max(r0, 0), H), min(max(r1, 0), H), min(max(c0, 0), W), min(max(c1, 0), W))   # numpy slice clipping (:157)
+        plan_t = _upload(plans, dev)
+        w_rgb, w_dep, w_lab, info_t = ops.occlude_paste(i_t, d_t, m_t[:nf], oi_t, od_t, m_t[nf:], plans, plan_t, ext_t[:nf])
+        info = info_t.cpu().numpy()                                                   # host read-back 2 of 3
+        occluded = info[:, 0] != 0
+        # ---- 3. the pose draws of every frame with a valid pixel in its box (:157-159,180-187)
+        kept = np.zeros(nf, bool)
+        src, R0s, ts, jits, augs = [], [], [], [], []
+        for f, s in enumerate(samples):
+            if info[f, 2] == 0:
+                continue
+            self.cls_row[int(s["obj"])]                                               # a class without a CAD cloud: KeyError, as :191
+            a1, a2, a3 = draw.angles()                                                # :180-182
+            jit = draw.jitter()                                                       # :186
+            kept[f] = True
+            src.append(tuple(int(v) for v in plans[f, 12:16]) + (255, f))
+            R0s.append(np.resize(np.array(s["cam_R_m2c"]), (3, 3)))                   # :153
+            ts.append(np.array(s["cam_t_m2c"]) / 1000.0)                              # :154
+            jits.append(jit)
+            augs.append(euler2mat(a1, a2, a3))
+        cand = np.nonzero(kept)[0]
+        out = {"batch_offsets": None, "voxel_num_limit": torch.tensor(self.limit), "kept": kept, "occluded": occluded, "boxes": boxes}
+        if cand.size == 0:
+            return dict(out, flags=torch.zeros(0, device=dev), batch_offsets=torch.zeros(1).int())
+        src_a = np.asarray(src, np.int32)
+        src_t = _upload(src_a, dev)
+        cam_t = _upload(np.tile(np.asarray(self.camera, np.float32), (cand.size, 1)), dev)
+        pose_t = _upload(ops.pose_rows64(R0s, ts, jits, augs), dev)
+        cap = max(1, int(((src_a[:, 1] - src_a[:, 0]).clip(0) * (src_a[:, 3] - src_a[:, 2]).clip(0)).max()))
+        xyz, col, centroid, counts, rot_gt, trans_gt = ops.crop_points_posed64(
+            w_dep, w_lab, w_rgb, src_a[:, 5], src_t, cam_t, pose_t, RGB_MEAN, self.extent * 0.5, LM_TRAIN_MIN_PT, cap=cap)
+
+        def count_free_part(keep):
+            objs = [int(samples[cand[k]]["obj"]) for k in keep]
+            rows = [self.cls_row[c] for c in objs]
+            cls_rows = _upload(np.asarray(rows, np.int64), dev)
+            small = np.array([[float(LM_OBJLIST.index(c) in LM_TRAIN_SYMMETRY_OBJ_IDX), LM_OBJLIST.index(c)] for c in objs], np.float32)
+            small_t = _upload(small, dev)
+            return {"feats_tmp": self.tmp_feats[cls_rows].reshape(len(keep) * self.n_tmp, 7),
+                    "tmp_side": self._template_side(rows), "flags": small_t[:, 0].contiguous(), "obj_idx": small_t[:, 1].int()}
+        part = count_free_part(list(range(cand.size)))
+        cnt = counts.cpu().numpy()                                                    # host read-back 3 of 3
+        keep = [k for k in range(cand.size) if cnt[k, 2] > 0]                         # :201: more than 128 points inside the grid
+        for k in range(cand.size):
+            kept[cand[k]] = cnt[k, 2] > 0
+        if not keep:
+            return dict(out, flags=torch.zeros(0, device=dev), batch_offsets=torch.zeros(1).int())
+        t_draw = time.perf_counter()
+        picks = [np.asarray(draw.choice(int(cnt[k, 2]), self.n_inp)) for k in keep]  # :205-208
+        self.draw_seconds += time.perf_counter() - t_draw
+        if len(keep) != cand.size:
+            kt = _upload(np.asarray(keep, np.int64), dev)
+            xyz, col, centroid = xyz[kt].contiguous(), col[kt].contiguous(), centroid[kt]
+            rot_gt, trans_gt = rot_gt[kt].contiguous(), trans_gt[kt].contiguous()
+            part = count_free_part(keep)
+        pick_t = _upload(np.stack(picks).astype(np.int64), dev)
+        # no clamp: the filter was applied, every point lies inside the grid (:202)
+        feats_inp, coords_inp = ops.crop_sample(xyz, col, pick_t, None, self.extent[0] * 0.5, self.unit, int(self.limit[0]))
+        b = len(keep)
+        out["inp"] = self._inp_side(feats_inp, coords_inp, b)
+        occ, p2v, v2p, coords_tmp = part["tmp_side"]
+        out["tmp"] = {"feats": part["feats_tmp"], "coords": coords_tmp, "occupied_voxels": occ, "p2v_maps": p2v, "v2p_maps": v2p}
+        out["labels"] = {"rot_gt": rot_gt, "trans_gt": trans_gt}
+        out["batch_offsets"] = (torch.arange(b + 1) * self.n_inp).int()
+        out["flags"], out["obj_idx"] = part["flags"], part["obj_idx"]
+        out["counts"], out["centriods"] = cnt[keep], centroid
         out["ready_event"] = torch.cuda.Event()
         out["ready_event"].record(torch.cuda.current_stream(dev))
         return out

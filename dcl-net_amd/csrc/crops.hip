@@ -45,7 +45,7 @@ __global__ __launch_bounds__(kCropThreads) void k_crop_centroid(int cap, int nch
                                                                 int always_filter, const float *__restrict__ raw_xyz,
                                                                 float *__restrict__ centroid, int32_t *__restrict__ counts,
                                                                 int32_t *__restrict__ ws) {
-  crop_centroid_body<false>(blockIdx.x, cap, nch, hx, hy, hz, min_valid, always_filter, raw_xyz, centroid, counts, ws, nullptr,
+  crop_centroid_body<kPoseNone>(blockIdx.x, cap, nch, hx, hy, hz, min_valid, always_filter, raw_xyz, centroid, counts, ws, nullptr,
                             nullptr, nullptr);
 }
 
@@ -55,7 +55,7 @@ __global__ __launch_bounds__(kCropThreads) void k_crop_keep(int cap, int nch, fl
                                                             const float *__restrict__ centroid, float *__restrict__ out_xyz,
                                                             float *__restrict__ out_rgb, const int32_t *__restrict__ ws) {
   const int inst = blockIdx.x / nch, chunk = blockIdx.x - inst * nch;
-  crop_keep_body<false>(inst, chunk, cap, nch, hx, hy, hz, raw_xyz, raw_rgb, centroid, out_xyz, out_rgb, ws, nullptr);
+  crop_keep_body<kPoseNone>(inst, chunk, cap, nch, hx, hy, hz, raw_xyz, raw_rgb, centroid, out_xyz, out_rgb, ws, nullptr);
 }
 
 // feats row [1, r, g, b, x, y, z] and voxel coordinate row [batch, ix, iy, iz] of every sampled point (:170-176,186-190):

@@ -1,9 +1,12 @@
 // crops_body.h -- the bodies of the three crop kernels, shared by the evaluation entry (crops.hip: dcl_crop_points) and the
 // training entry (crops_train.hip: dcl_crop_points_posed).  Each kernel of either file is a thin wrapper that fetches its
-// crop's box, source frame and camera and calls the body; the training wrappers pass kPosed = true, which adds the loader's
-// re-pose (dataloader_train_YCBV.py:159-174) between the centroid and the grid filter.  With kPosed = false a body is, statement
+// crop's box, source frame and camera and calls the body; the training wrappers pass a kPose other than kPoseNone, which adds the loader's
+// re-pose (dataloader_train_YCBV.py:159-174) between the centroid and the grid filter.  With kPoseNone a body is, statement
 // for statement, what k_crop_mask / k_crop_centroid / k_crop_keep were before the split: the same float operations in the
 // same order (the library is built with -ffp-contract=off), so the same bits.
+// The posed path has two precisions (the template argument kPose): kPoseF32, the YCB-V training loader's float32 re-pose, and
+// kPoseF64, the LineMOD training loader's (LM/dataloader_train_LM.py:177-188,200-209), which holds the cloud in float64 from the
+// moment the float64 translation is subtracted until the FloatTensor of the sampled rows is made (crops_train_lm.hip).
 #pragma once
 #include "common.h"
 
@@ -79,6 +82,50 @@ __host__ __device__ inline void crop_repose(const CropPose &P, float &x, float &
   x = r0 + P.t1[0]; y = r1 + P.t1[1]; z = r2 + P.t1[2];
 }
 
+// ---- the float64 pose row of a LineMOD training crop (include/dclnet_hip.h: DCL_CROP_POSE_ROW64_BYTES): everything float64, as
+// the loader holds it (LM/dataloader_train_LM.py:153-154,183,186)
+struct CropPoseRow64 {
+  double t_gt[3];      // np.array(meta['cam_t_m2c']) / 1000.0 (:154)
+  double R0[9];        // np.resize(np.array(meta['cam_R_m2c']), (3, 3)), row major (:153)
+  double j[3];         // [random.uniform(-0.03, 0.03)] * 3 (:186)
+  double A[9];         // aug_r = euler2mat(a1, a2, a3) (:183)
+};
+static_assert(sizeof(CropPoseRow64) == DCL_CROP_POSE_ROW64_BYTES, "float64 pose row layout");
+
+struct CropPose64 { double R0[9], R1[9], t0[3], t1[3]; };
+
+// t0 = t_gt - f64(centroid) (:177), t1 = t0 + j (:186), R1 = R0 A (:187): crop_pose_form's order, nothing rounded
+__host__ __device__ inline void crop_pose_form(const CropPoseRow64 &row, const float *cen, CropPose64 &P) {
+  for (int k = 0; k < 3; ++k) {
+    P.t0[k] = row.t_gt[k] - (double)cen[k];
+    P.t1[k] = P.t0[k] + row.j[k];
+  }
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j)
+      P.R1[i * 3 + j] = (row.R0[i * 3] * row.A[j] + row.R0[i * 3 + 1] * row.A[3 + j]) + row.R0[i * 3 + 2] * row.A[6 + j];
+  for (int k = 0; k < 9; ++k) P.R0[k] = row.R0[k];
+}
+
+// the re-pose of one CENTRED float32 point in float64 (:185,188): crop_repose's order on widened operands
+__host__ __device__ inline void crop_repose(const CropPose64 &P, double &x, double &y, double &z) {
+  const double d0 = x - P.t0[0], d1 = y - P.t0[1], d2 = z - P.t0[2];
+  const double q0 = (d0 * P.R0[0] + d1 * P.R0[3]) + d2 * P.R0[6];
+  const double q1 = (d0 * P.R0[1] + d1 * P.R0[4]) + d2 * P.R0[7];
+  const double q2 = (d0 * P.R0[2] + d1 * P.R0[5]) + d2 * P.R0[8];
+  const double r0 = (q0 * P.R1[0] + q1 * P.R1[1]) + q2 * P.R1[2];
+  const double r1 = (q0 * P.R1[3] + q1 * P.R1[4]) + q2 * P.R1[5];
+  const double r2 = (q0 * P.R1[6] + q1 * P.R1[7]) + q2 * P.R1[8];
+  x = r0 + P.t1[0]; y = r1 + P.t1[1]; z = r2 + P.t1[2];
+}
+
+// what the precision of the posed path decides: the pose row, the formed pose, the type the re-posed point and the grid's
+// half extent are held in (kPoseNone: the evaluation kernels, nothing is re-posed)
+constexpr int kPoseNone = 0, kPoseF32 = 1, kPoseF64 = 2;
+template <int kPose> struct CropPrec { using real = float; using row_t = CropPoseRow; using pose_t = CropPose; };
+template <> struct CropPrec<kPoseF64> { using real = double; using row_t = CropPoseRow64; using pose_t = CropPose64; };
+__device__ __forceinline__ float crop_abs(float v) { return fabsf(v); }
+__device__ __forceinline__ double crop_abs(double v) { return fabs(v); }
+
 // ---- 1. masked pixels of the box in flat order (dataloader_test_YCBV.py:128-133), back-projection (:147-154)
 // depth / label / rgb: the crop's FRAME; status / rx / rc: the crop's own scratch
 __device__ __forceinline__ void crop_mask_body(const uint16_t *__restrict__ depth, const int32_t *__restrict__ label,
@@ -150,17 +197,23 @@ __device__ __forceinline__ void crop_mask_body(const uint16_t *__restrict__ dept
 // kPosed: one lane forms the crop's pose from its row and the centroid (rot_gt / trans_gt are written here), and the in-grid
 // test is made on the RE-POSED point; the filter is unconditional and a crop with at most min_valid points inside the grid
 // writes no row at all (dataloader_train_YCBV.py:189-191,208-210)
-template <bool kPosed>
-__device__ __forceinline__ void crop_centroid_body(int inst, int cap, int nch, float hx, float hy, float hz, int min_valid,
-                                                   int always_filter, const float *__restrict__ raw_xyz,
+// kPoseF64: the pose and the re-posed point are float64, the grid test is made on the float64 point against a float64 half
+// extent, and the labels are rounded to float32 once (LM/dataloader_train_LM.py:200,218)
+template <int kPose>
+__device__ __forceinline__ void crop_centroid_body(int inst, int cap, int nch, typename CropPrec<kPose>::real hx,
+                                                   typename CropPrec<kPose>::real hy, typename CropPrec<kPose>::real hz,
+                                                   int min_valid, int always_filter, const float *__restrict__ raw_xyz,
                                                    float *__restrict__ centroid, int32_t *__restrict__ counts,
-                                                   int32_t *__restrict__ ws, const CropPoseRow *__restrict__ pose,
+                                                   int32_t *__restrict__ ws,
+                                                   const typename CropPrec<kPose>::row_t *__restrict__ pose,
                                                    float *__restrict__ rot_gt, float *__restrict__ trans_gt) {
+  constexpr bool kPosed = kPose != kPoseNone;
+  using real = typename CropPrec<kPose>::real;
   __shared__ int s_wave[kCropThreads / 64];
   __shared__ float s_stage[2][kCropChunk * 3];
   __shared__ float s_cen[3];
   __shared__ int s_cnt[1024];                    // in-grid rows of every 4096-row chunk (cap <= 4 Mi pixels)
-  __shared__ CropPose s_pose;
+  __shared__ typename CropPrec<kPose>::pose_t s_pose;
   const int t = threadIdx.x;
   int32_t *w = ws + (size_t)inst * crop_ws_ints(cap);
   const float *rx = raw_xyz + (size_t)inst * cap * 3;
@@ -229,14 +282,14 @@ __device__ __forceinline__ void crop_centroid_body(int inst, int cap, int nch, f
   if (t < 3) { const float cen = acc / (float)n; s_cen[t] = cen; centroid[inst * 3 + t] = cen; }
   __syncthreads();
   const float cx = s_cen[0], cy = s_cen[1], cz = s_cen[2];
-  CropPose P;
+  typename CropPrec<kPose>::pose_t P;
   if constexpr (kPosed) {
     if (t == 0) {                               // the pose: one lane, read by every thread through LDS
       crop_pose_form(pose[inst], s_cen, s_pose);
 #pragma unroll
-      for (int k = 0; k < 9; ++k) rot_gt[inst * 9 + k] = s_pose.R1[k];
+      for (int k = 0; k < 9; ++k) rot_gt[inst * 9 + k] = (float)s_pose.R1[k];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) trans_gt[inst * 3 + k] = s_pose.t1[k];
+      for (int k = 0; k < 3; ++k) trans_gt[inst * 3 + k] = (float)s_pose.t1[k];
     }
     __syncthreads();
     P = s_pose;
@@ -249,9 +302,9 @@ __device__ __forceinline__ void crop_centroid_body(int inst, int cap, int nch, f
     for (int u = 0; u < 4; ++u) {
       const int i = ch * kCropChunk + 4 * t + u;
       if (i < n) {
-        float x = rx[(size_t)i * 3] - cx, y = rx[(size_t)i * 3 + 1] - cy, z = rx[(size_t)i * 3 + 2] - cz;
+        real x = rx[(size_t)i * 3] - cx, y = rx[(size_t)i * 3 + 1] - cy, z = rx[(size_t)i * 3 + 2] - cz;   // centred in float32
         if constexpr (kPosed) crop_repose(P, x, y, z);
-        v += fabsf(x) < hx && fabsf(y) < hy && fabsf(z) < hz;
+        v += crop_abs(x) < hx && crop_abs(y) < hy && crop_abs(z) < hz;
       }
     }
     int total;
@@ -278,12 +331,16 @@ __device__ __forceinline__ void crop_centroid_body(int inst, int cap, int nch, f
 }
 
 // ---- 3. keep the points inside the grid (in order), centred (:160-165); kPosed: centred, re-posed, then the grid test
-template <bool kPosed>
-__device__ __forceinline__ void crop_keep_body(int inst, int chunk, int cap, int nch, float hx, float hy, float hz,
+// kPoseF64: the grid test on the float64 point, the point rounded to float32 once when it is written
+template <int kPose>
+__device__ __forceinline__ void crop_keep_body(int inst, int chunk, int cap, int nch, typename CropPrec<kPose>::real hx,
+                                               typename CropPrec<kPose>::real hy, typename CropPrec<kPose>::real hz,
                                                const float *__restrict__ raw_xyz, const float *__restrict__ raw_rgb,
                                                const float *__restrict__ centroid, float *__restrict__ out_xyz,
                                                float *__restrict__ out_rgb, const int32_t *__restrict__ ws,
-                                               const CropPoseRow *__restrict__ pose) {
+                                               const typename CropPrec<kPose>::row_t *__restrict__ pose) {
+  constexpr bool kPosed = kPose != kPoseNone;
+  using real = typename CropPrec<kPose>::real;
   __shared__ int s_wave[kCropThreads / 64];
   const int t = threadIdx.x;
   const int32_t *w = ws + (size_t)inst * crop_ws_ints(cap);
@@ -291,7 +348,7 @@ __device__ __forceinline__ void crop_keep_body(int inst, int chunk, int cap, int
   if (chunk * kCropChunk >= n) return;
   const bool filter = w[2] != 0;
   const float cx = centroid[inst * 3], cy = centroid[inst * 3 + 1], cz = centroid[inst * 3 + 2];
-  CropPose P;
+  typename CropPrec<kPose>::pose_t P;
   if constexpr (kPosed) {                       // the same function of the same row and centroid as in the centroid kernel
     const float cen[3] = {cx, cy, cz};
     crop_pose_form(pose[inst], cen, P);
@@ -306,9 +363,10 @@ __device__ __forceinline__ void crop_keep_body(int inst, int chunk, int cap, int
     const int i = chunk * kCropChunk + 4 * t + u;
     keep[u] = false;
     if (i < n) {
-      p[u][0] = rx[(size_t)i * 3] - cx; p[u][1] = rx[(size_t)i * 3 + 1] - cy; p[u][2] = rx[(size_t)i * 3 + 2] - cz;
-      if constexpr (kPosed) crop_repose(P, p[u][0], p[u][1], p[u][2]);
-      keep[u] = !filter || (fabsf(p[u][0]) < hx && fabsf(p[u][1]) < hy && fabsf(p[u][2]) < hz);
+      real x = rx[(size_t)i * 3] - cx, y = rx[(size_t)i * 3 + 1] - cy, z = rx[(size_t)i * 3 + 2] - cz;
+      if constexpr (kPosed) crop_repose(P, x, y, z);
+      keep[u] = !filter || (crop_abs(x) < hx && crop_abs(y) < hy && crop_abs(z) < hz);
+      p[u][0] = (float)x; p[u][1] = (float)y; p[u][2] = (float)z;
     }
     cnt += keep[u];
   }

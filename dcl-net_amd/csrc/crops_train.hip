@@ -136,7 +136,7 @@ __global__ __launch_bounds__(kCropThreads) void k_crop_centroid_posed(int cap, i
                                                                       float *__restrict__ centroid, int32_t *__restrict__ counts,
                                                                       int32_t *__restrict__ ws, const CropPoseRow *__restrict__ pose,
                                                                       float *__restrict__ rot_gt, float *__restrict__ trans_gt) {
-  crop_centroid_body<true>(blockIdx.x, cap, nch, hx, hy, hz, min_valid, 1, raw_xyz, centroid, counts, ws, pose, rot_gt, trans_gt);
+  crop_centroid_body<kPoseF32>(blockIdx.x, cap, nch, hx, hy, hz, min_valid, 1, raw_xyz, centroid, counts, ws, pose, rot_gt, trans_gt);
 }
 
 __global__ __launch_bounds__(kCropThreads) void k_crop_keep_posed(int cap, int nch, float hx, float hy, float hz,
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(kCropThreads) void k_crop_keep_posed(int cap, int n
                                                                   float *__restrict__ out_rgb, const int32_t *__restrict__ ws,
                                                                   const CropPoseRow *__restrict__ pose) {
   const int inst = blockIdx.x / nch, chunk = blockIdx.x - inst * nch;
-  crop_keep_body<true>(inst, chunk, cap, nch, hx, hy, hz, raw_xyz, raw_rgb, centroid, out_xyz, out_rgb, ws, pose);
+  crop_keep_body<kPoseF32>(inst, chunk, cap, nch, hx, hy, hz, raw_xyz, raw_rgb, centroid, out_xyz, out_rgb, ws, pose);
 }
 
 }  // namespace

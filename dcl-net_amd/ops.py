@@ -1525,6 +1525,169 @@ def crop_repose_host(points, pose_row, centroid):
     return out, R1, t1
 
 
+# ---- the LineMOD training loader's front end (csrc/crops_train_lm.hip)
+PASTE_PLAN_INTS = 16
+# columns of a paste plan row (include/dclnet_hip.h: dcl_occlude_paste)
+PASTE_PLAN = ("enabled", "other", "py0", "px0", "ph", "pw", "ty0", "tx0", "th", "tw", "rep_y", "rep_x", "rmin", "rmax", "cmin", "cmax")
+POSE_ROW64_BYTES = 192
+POSE_ROW64 = [("t_gt", "<f8", (3,)), ("R0", "<f8", (3, 3)), ("j", "<f8", (3,)), ("A", "<f8", (3, 3))]
+
+
+def extent_sums(extent):
+    """the int64 mask sums behind columns 4:6 of mask_extent's rows: (n,6) int32 numpy array -> (n) int64"""
+    import numpy as np
+    return np.ascontiguousarray(np.asarray(extent, np.int32)[:, 4:6]).view(np.int64).reshape(-1)
+
+
+def mask_extent(mask):
+    """What `occlude_with_another_object` reduces of an object mask (LM/dataloader_train_LM.py:301-306,343; dcl_mask_extent).
+    mask (n,H,W,3) u8 CUDA -> (n,6) i32 CUDA: [min row, max row, min col, max col of mask[..., 0] != 0 (2^31 - 1 / -1 when
+    empty), and in columns 4:6 ONE int64: the sum of all bytes (extent_sums reads it)].  No host synchronisation."""
+    N.need_cuda(mask)
+    assert mask.dtype == torch.uint8 and mask.dim() == 4 and mask.shape[3] == 3 and mask.is_contiguous()
+    n, H, W = mask.shape[:3]
+    out = torch.empty((n, 6), dtype=torch.int32, device=mask.device)
+    N.check(N.lib().dcl_mask_extent(N.ptr(mask), n, H, W, N.ptr(out), N.stream()), "mask_extent")
+    return out
+
+
+def mask_extent_host(mask):
+    """the host twin of mask_extent (dcl_mask_extent_host, plain C++, no GPU call): (n,H,W,3) u8 numpy -> (n,6) int32 numpy"""
+    import numpy as np
+    m = np.ascontiguousarray(np.asarray(mask, np.uint8))
+    assert m.ndim == 4 and m.shape[3] == 3
+    out = np.zeros((m.shape[0], 6), np.int32)
+    N.check(N.lib().dcl_mask_extent_host(m.ctypes.data_as(C.c_void_p), m.shape[0], m.shape[1], m.shape[2],
+                                         out.ctypes.data_as(C.c_void_p)), "mask_extent_host")
+    return out
+
+
+def occlude_paste(rgb, depth, mask, other_rgb, other_depth, other_mask, plan_host, plan, extent):
+    """The occlusion compositing of the LineMOD training loader with its commit / roll-back decision on the device
+    (LM/dataloader_train_LM.py:335-346; dcl_occlude_paste).  rgb (n,H,W,C) u8, depth (n,H,W) 16-bit storage, mask (n,H,W,3) u8;
+    other_* the occluder frames (k,H,W,3) / (k,H,W) / (k,H,W,3) (k may be 0); plan (n,16) i32 CUDA rows (crops.lm_paste_plan,
+    columns PASTE_PLAN) and plan_host their host copy (checked by the call); extent: mask_extent(mask), CUDA.
+    -> working copies rgb' (n,H,W,C) u8, depth' (n,H,W), label' (n,H,W) i32 = channel 0 of the mask afterwards, and info (n,4)
+    i64 [committed, remaining mask sum, n_box_valid, removed].  The inputs are not modified; no host synchronisation."""
+    import numpy as np
+    N.need_cuda(rgb, depth, mask, other_rgb, other_depth, other_mask, plan, extent)
+    assert rgb.dtype == torch.uint8 and mask.dtype == torch.uint8 and depth.dtype in (torch.int16, torch.uint16)
+    assert rgb.dim() == 4 and depth.dim() == 3 and rgb.shape[:3] == depth.shape and tuple(mask.shape) == tuple(depth.shape) + (3,)
+    assert rgb.is_contiguous() and depth.is_contiguous() and mask.is_contiguous()
+    n, H, W = depth.shape
+    k = other_depth.shape[0]
+    assert other_rgb.dtype == torch.uint8 and other_mask.dtype == torch.uint8 and other_depth.dtype == depth.dtype
+    assert tuple(other_rgb.shape) == (k, H, W, 3) and tuple(other_mask.shape) == (k, H, W, 3) and tuple(other_depth.shape) == (k, H, W)
+    assert other_rgb.is_contiguous() and other_depth.is_contiguous() and other_mask.is_contiguous()
+    assert plan.dtype == torch.int32 and plan.is_contiguous() and tuple(plan.shape) == (n, PASTE_PLAN_INTS)
+    assert extent.dtype == torch.int32 and extent.is_contiguous() and tuple(extent.shape) == (n, 6)
+    ph = np.ascontiguousarray(np.asarray(plan_host, np.int32).reshape(n, PASTE_PLAN_INTS))
+    dev = rgb.device
+    out_rgb, out_depth = torch.empty_like(rgb), torch.empty_like(depth)
+    out_label = torch.empty((n, H, W), dtype=torch.int32, device=dev)
+    info = torch.empty((n, 4), dtype=torch.int64, device=dev)
+    N.check(N.lib().dcl_occlude_paste(N.ptr(rgb), N.ptr(depth), N.ptr(mask), n, H, W, rgb.shape[3], N.ptr(other_rgb),
+                                      N.ptr(other_depth), N.ptr(other_mask), k, ph.ctypes.data_as(C.c_void_p), N.ptr(plan),
+                                      N.ptr(extent), N.ptr(out_rgb), N.ptr(out_depth), N.ptr(out_label), N.ptr(info),
+                                      N.stream()), "occlude_paste")
+    return out_rgb, out_depth, out_label, info
+
+
+def occlude_paste_host(rgb, depth, mask, other_rgb, other_depth, other_mask, plan, extent=None):
+    """the host twin of occlude_paste (dcl_occlude_paste_host, plain C++, no GPU call) on numpy arrays; extent None:
+    mask_extent_host(mask).  -> (rgb', depth' u16, label' i32, info (n,4) i64)"""
+    import numpy as np
+    rgb, mask = np.ascontiguousarray(np.asarray(rgb, np.uint8)), np.ascontiguousarray(np.asarray(mask, np.uint8))
+    depth = np.ascontiguousarray(np.asarray(depth).astype(np.uint16))
+    n, H, W = depth.shape
+    o_rgb = np.ascontiguousarray(np.asarray(other_rgb, np.uint8).reshape(-1, H, W, 3))
+    o_mask = np.ascontiguousarray(np.asarray(other_mask, np.uint8).reshape(-1, H, W, 3))
+    o_depth = np.ascontiguousarray(np.asarray(other_depth).astype(np.uint16).reshape(-1, H, W))
+    k = o_depth.shape[0]
+    assert rgb.shape[:3] == (n, H, W) and mask.shape == (n, H, W, 3) and o_rgb.shape[0] == k == o_mask.shape[0]
+    plan = np.ascontiguousarray(np.asarray(plan, np.int32).reshape(n, PASTE_PLAN_INTS))
+    extent = mask_extent_host(mask) if extent is None else np.ascontiguousarray(np.asarray(extent, np.int32).reshape(n, 6))
+    out_rgb, out_depth = np.empty_like(rgb), np.empty_like(depth)
+    out_label, info = np.empty((n, H, W), np.int32), np.zeros((n, 4), np.int64)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    N.check(N.lib().dcl_occlude_paste_host(p(rgb), p(depth), p(mask), n, H, W, rgb.shape[3], p(o_rgb), p(o_depth), p(o_mask), k,
+                                           p(plan), p(extent), p(out_rgb), p(out_depth), p(out_label), p(info)),
+            "occlude_paste_host")
+    return out_rgb, out_depth, out_label, info
+
+
+def pose_rows64(R0, t_gt, jitter, aug_r):
+    """The pose rows dcl_crop_points_posed64 takes (include/dclnet_hip.h: 192 bytes per crop, everything float64 as the LineMOD
+    training loader holds it): R0 (n,3,3), t_gt (n,3), jitter (n,3), aug_r (n,3,3) -> (n,192) uint8 numpy array."""
+    import numpy as np
+    n = len(R0)
+    rows = np.zeros(n, POSE_ROW64)
+    rows["t_gt"], rows["R0"] = np.asarray(t_gt, np.float64).reshape(n, 3), np.asarray(R0, np.float64).reshape(n, 3, 3)
+    rows["j"], rows["A"] = np.asarray(jitter, np.float64).reshape(n, 3), np.asarray(aug_r, np.float64).reshape(n, 3, 3)
+    return rows.view(np.uint8).reshape(n, POSE_ROW64_BYTES)
+
+
+def crop_points_posed64(depth, label, rgb, frame_idx, src, cams, pose, rgb_mean, half_extent, min_valid=128, cap=None):
+    """crop_points_posed in the precision of the LineMOD training loader (LM/dataloader_train_LM.py:157-209;
+    csrc/crops_train_lm.hip): the re-pose and the grid test in float64, the results rounded to float32 once.  As
+    crop_points_posed, except cams (n,6) f32 [cx,cy,fx,fy,scale,post_div], pose (n,192) u8 (pose_rows64), half_extent three
+    float64.  -> xyz, rgb, centroid, counts, rot_gt, trans_gt.  No host synchronisation when cap is given."""
+    import numpy as np
+    N.need_cuda(depth, label, rgb, src, cams, pose)
+    assert depth.dtype in (torch.int16, torch.uint16) and label.dtype == torch.int32 and rgb.dtype == torch.uint8
+    assert depth.dim() == 3 and label.shape == depth.shape and rgb.dim() == 4 and rgb.shape[:3] == depth.shape
+    assert depth.is_contiguous() and label.is_contiguous() and rgb.is_contiguous()
+    n = src.shape[0]
+    assert src.dtype == torch.int32 and src.is_contiguous() and tuple(src.shape) == (n, 6)
+    assert cams.dtype == torch.float32 and cams.is_contiguous() and tuple(cams.shape) == (n, 6)
+    assert pose.dtype == torch.uint8 and pose.is_contiguous() and tuple(pose.shape) == (n, POSE_ROW64_BYTES)
+    fidx = np.ascontiguousarray(np.asarray(frame_idx, np.int32).reshape(-1))
+    assert fidx.shape[0] == n
+    f, H, W = depth.shape
+    dev = depth.device
+    if cap is None:
+        bx = src.cpu()
+        cap = int(max(1, ((bx[:, 1] - bx[:, 0]).clamp(min=0) * (bx[:, 3] - bx[:, 2]).clamp(min=0)).max().item())) if n else 1
+    raw_xyz = torch.empty((n, cap, 3), dtype=torch.float32, device=dev)
+    raw_rgb = torch.empty((n, cap, 3), dtype=torch.float32, device=dev)
+    xyz = torch.empty((n, cap, 3), dtype=torch.float32, device=dev)
+    col = torch.empty((n, cap, 3), dtype=torch.float32, device=dev)
+    centroid = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    counts = torch.zeros((n, 3), dtype=torch.int32, device=dev)
+    rot_gt = torch.empty((n, 3, 3), dtype=torch.float32, device=dev)
+    trans_gt = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    ws_ints = C.c_int64(0)
+    N.check(N.lib().dcl_crop_points_ws_ints(n, int(cap), C.byref(ws_ints)), "crop_points_ws_ints")
+    ws = torch.empty(max(int(ws_ints.value), 1), dtype=torch.int32, device=dev)
+    mean_a = (C.c_double * 3)(*[float(v) for v in rgb_mean])
+    he_a = (C.c_double * 3)(*[float(v) for v in half_extent])
+    N.check(N.lib().dcl_crop_points_posed64(N.ptr(depth), N.ptr(label), N.ptr(rgb), f, H, W, rgb.shape[3], n,
+                                            fidx.ctypes.data_as(C.c_void_p), N.ptr(src), N.ptr(cams), N.ptr(pose), mean_a, he_a,
+                                            int(min_valid), int(cap), N.ptr(raw_xyz), N.ptr(raw_rgb), N.ptr(xyz), N.ptr(col),
+                                            N.ptr(centroid), N.ptr(counts), N.ptr(rot_gt), N.ptr(trans_gt), N.ptr(ws), N.stream()),
+            "crop_points_posed64")
+    return xyz, col, centroid, counts, rot_gt, trans_gt
+
+
+def crop_repose64_host(points, pose_row, centroid, half_extent=None):
+    """the host twin of the float64 re-pose (dcl_crop_repose64_host, plain C++ with the library's -ffp-contract=off): CENTRED
+    points (n,3) float32, one pose row (192 bytes, pose_rows64), centroid (3) float32 -> (re-posed points (n,3) float32, R1
+    (3,3), t1 (3)), and with half_extent (3 float64) a fourth value: inside (n) bool, the grid test made on the float64 points."""
+    import numpy as np
+    pts = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+    row = np.ascontiguousarray(np.asarray(pose_row, np.uint8).reshape(-1))
+    cen = np.ascontiguousarray(np.asarray(centroid, np.float32).reshape(3))
+    assert row.shape[0] == POSE_ROW64_BYTES
+    out, R1, t1 = np.empty_like(pts), np.empty((3, 3), np.float32), np.empty(3, np.float32)
+    he = None if half_extent is None else (C.c_double * 3)(*[float(v) for v in half_extent])
+    inside = None if half_extent is None else np.zeros(pts.shape[0], np.uint8)
+    N.check(N.lib().dcl_crop_repose64_host(pts.ctypes.data_as(C.c_void_p), row.ctypes.data_as(C.c_void_p),
+                                           cen.ctypes.data_as(C.c_void_p), pts.shape[0], he, out.ctypes.data_as(C.c_void_p),
+                                           None if inside is None else inside.ctypes.data_as(C.c_void_p),
+                                           R1.ctypes.data_as(C.c_void_p), t1.ctypes.data_as(C.c_void_p)), "crop_repose64_host")
+    return (out, R1, t1) if inside is None else (out, R1, t1, inside.astype(bool))
+
+
 # ------------------------------------------------------------------------------------ training-side kernels
 def rulebook_transpose(nbr, n_out, cap_in):
     """inv[k][i] = o for nbr[k][o] = i (csrc/backward.hip); nbr (kvol, cap_out) i32 -> (kvol, cap_in) i32."""

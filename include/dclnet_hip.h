@@ -718,6 +718,82 @@ int dcl_crop_points_posed(const uint16_t *depth, const int32_t *label, const uin
 int dcl_crop_repose_host(const float *points, const void *pose_row, const float *centroid, int n, float *out_xyz,
                          float *out_R1, float *out_t1);
 
+/* ---- the LineMOD TRAINING loader's front end (LM/dataloader_train_LM.py:125-222,293-348; csrc/crops_train_lm.hip)
+ * dcl_mask_extent: what `occlude_with_another_object` needs of an object mask (:301-306,343), for n masks (n,H,W,3) u8.
+ * out (n,6) i32, a row = { min row, max row, min col, max col of mask[:, :, 0] != 0 (`np.nonzero(mask[:, :, 0])`; an empty
+ * mask: min = INT32_MAX, max = -1),  [4:6] = ONE int64 (little endian, 8-byte aligned: a row is 24 bytes): the sum of ALL
+ * bytes of the mask, `mask.sum()` }.  Two launches (identity fill; one pass, per-workgroup reduction, integer atomics),
+ * integers only, no workgroup waits for another, nothing is read back.  DCL_EINVAL: n < 0, H or W < 1,
+ * H*W >= 2^31 - 64, a null pointer of a non-empty call; n == 0 returns 0.  dcl_mask_extent_host: the same in plain C++.
+ *
+ * dcl_occlude_paste: the compositing of :335-346 for n frames, into WORKING COPIES (the inputs are not modified):
+ *   rgb (n,H,W,C) u8 with C >= 3, depth (n,H,W) u16, mask (n,H,W,3) u8            this frame
+ *   other_rgb (n_other,H,W,3) u8, other_depth (n_other,H,W) u16, other_mask (n_other,H,W,3) u8   the occluder frames
+ *   plan (n, DCL_PASTE_PLAN_INTS) i32 DEVICE rows, plan_host their HOST copy (crops.py::lm_paste_plan makes them):
+ *       [0] enabled   0: the frame is copied through and only counted
+ *       [1] other     the occluder frame of this frame, an index into other_*
+ *       [2] py0 [3] px0   origin of the patch inside the occluder frame: the occluder mask's first row / column plus the
+ *                         rows the loader's trims removed in front (the patch row window starts here)
+ *       [4] ph  [5] pw    shape of the patch (rows of the window, columns)
+ *       [6] ty0 [7] tx0   origin of the target rectangle inside this frame
+ *       [8] th  [9] tw    shape of the target rectangle (numpy's clipped slice)
+ *       [10] rep_y [11] rep_x   1: the patch has ONE row / column on this axis and numpy's broadcast repeats it
+ *       [12..15] rmin, rmax, cmin, cmax   the crop box, clipped to the frame (counted for every frame)
+ *   extent (n,6) i32    dcl_mask_extent's rows of `mask` (the original sums), DEVICE
+ *   out_rgb (n,H,W,C), out_depth (n,H,W) u16, out_label (n,H,W) i32 = channel 0 of the mask afterwards (what
+ *   dcl_crop_points_posed64 tests: label == 255 && depth != 0 is `mask_label * mask_depth`, :143-148)
+ *   info (n,4) i64 = { committed, remaining mask sum = original - removed (what the decision is taken on; it stays so after
+ *                      a roll-back), n_box_valid, what the paste removed }
+ * Inside the target rectangle, per channel, with om the occluder mask's value at the patch pixel:
+ *   rgb' = om == 0 ? rgb : other rgb;  mask' = om == 0 ? mask : 0;  depth' = om[channel 0] == 0 ? depth : other depth
+ * (the loader's multiply-then-add: the two terms never overlap), outside it the copy equals the original.  The first launch
+ * composites and adds what it removed from the mask to info[3] with integer atomics; the second one restores the rectangle
+ * from the originals where the remaining sum (original - removed) is below 20 (:343-346), writes committed / remaining, and
+ * counts n_box_valid = pixels of the box with label' == 255 && depth' != 0 (`len(choose)`, :157) -- no host decision, no
+ * read-back, no float atomics, no workgroup waits for another.  DCL_EINVAL before any device work: the shape limits of
+ * dcl_mask_extent, C < 3, null pointers, and a row of plan_host that names a pixel outside either frame, an occluder frame
+ * that is not there, a patch that does not broadcast to its target (an axis must be equal, or 1 with its repeat flag) or a
+ * box outside the frame.  A DEVICE row that disagrees is clamped: never an address.  dcl_occlude_paste_host: the same from
+ * host memory in plain C++ (plan = host rows).
+ *
+ * dcl_crop_points_posed64: dcl_crop_points_posed in the precision of the LineMOD training loader, which applies the
+ * jittered pose in FLOAT64 (`cloud - target_t` promotes the float32 cloud, :185; nothing is rounded until the FloatTensor
+ * of the sampled rows, :209).  Same arguments, except:
+ *   cams (n_inst,6) f32 rows {cx, cy, fx, fy, depth scale, post_div}: LineMOD's are (.., 1, 1000) -- the back-projection is
+ *        made in millimetres and divided by 1000 afterwards (:168-173), float32 as in dcl_crop_points
+ *   pose (n_inst) DEVICE rows of DCL_CROP_POSE_ROW64_BYTES = 192 bytes, little endian, all float64:
+ *                       [  0: 24)  t_gt  3 x f64   cam_t_m2c / 1000.0                    (:154)
+ *                       [ 24: 96)  R0    9 x f64   cam_R_m2c, row major                  (:153)
+ *                       [ 96:120)  j     3 x f64   the translation jitter                (:186)
+ *                       [120:192)  A     9 x f64   aug_r = euler2mat(a1, a2, a3)         (:183)
+ *        (the 112-byte row of dcl_crop_points_posed holds t_gt as f64 and R0, j, A as f32: see above)
+ *   half_extent_host: 3 DOUBLES, total_voxel_extent * 0.5 (:200)
+ * One lane forms t0 = t_gt - (double)centroid, t1 = t0 + j, R1 = R0 A; every centred float32 point is widened and goes
+ * through the re-pose of dcl_crop_points_posed, same order, double operands, uncontracted; |p'| < half_extent is tested on
+ * the doubles (strict, always); out_xyz, rot_gt = f32(R1), trans_gt = f32(t1) are rounded to float32 once.  min_valid:
+ * LineMOD's is 128 (:201).  dcl_crop_repose64_host: the arithmetic in plain C++ for n CENTRED points: out_xyz (n,3) = f32(p')
+ * of every point, inside (n) u8 = the grid test on the doubles (NULL with half_extent NULL: not wanted), out_R1, out_t1. */
+#define DCL_CROP_POSE_ROW64_BYTES 192
+#define DCL_PASTE_PLAN_INTS 16
+int dcl_mask_extent(const uint8_t *mask, int n, int H, int W, int32_t *out, dclStream_t stream);
+int dcl_mask_extent_host(const uint8_t *mask, int n, int H, int W, int32_t *out);
+int dcl_occlude_paste(const uint8_t *rgb, const uint16_t *depth, const uint8_t *mask, int n, int H, int W,
+                      int rgb_channels, const uint8_t *other_rgb, const uint16_t *other_depth, const uint8_t *other_mask,
+                      int n_other, const int32_t *plan_host, const int32_t *plan, const int32_t *extent, uint8_t *out_rgb,
+                      uint16_t *out_depth, int32_t *out_label, int64_t *info, dclStream_t stream);
+int dcl_occlude_paste_host(const uint8_t *rgb, const uint16_t *depth, const uint8_t *mask, int n, int H, int W,
+                           int rgb_channels, const uint8_t *other_rgb, const uint16_t *other_depth,
+                           const uint8_t *other_mask, int n_other, const int32_t *plan, const int32_t *extent,
+                           uint8_t *out_rgb, uint16_t *out_depth, int32_t *out_label, int64_t *info);
+int dcl_crop_points_posed64(const uint16_t *depth, const int32_t *label, const uint8_t *rgb, int n_frames, int H, int W,
+                            int rgb_channels, int n_inst, const int32_t *frame_idx_host, const int32_t *src,
+                            const float *cams, const void *pose, const double *rgb_mean_host,
+                            const double *half_extent_host, int min_valid, int cap, float *raw_xyz, float *raw_rgb,
+                            float *out_xyz, float *out_rgb, float *centroid, int32_t *counts, float *rot_gt,
+                            float *trans_gt, int32_t *ws, dclStream_t stream);
+int dcl_crop_repose64_host(const float *points, const void *pose_row, const float *centroid, int n,
+                           const double *half_extent, float *out_xyz, uint8_t *inside, float *out_R1, float *out_t1);
+
 /* ------------------------------------------------------------ eval metric ---
  * ADD-S per object (tools/test_YCBV_stage1.py:186-189): out[o] = mean_i min_j |R_pred x_i + t_pred - (R_gt x_j + t_gt)|
  * over the P points of the object's class cloud.  cld (n_clouds, P, 3); cls i32[b] selects the cloud of object o
