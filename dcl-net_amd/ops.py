@@ -723,6 +723,44 @@ def chamfer_backward(pred, target, idx_pt, idx_tp, g_pt, g_tp, active=None, need
     return grad_pred, grad_target
 
 
+OPTIM_CHUNK = 4096             # include/dclnet_hip.h: DCL_OPTIM_CHUNK
+OPTIM_TENSOR_BYTES = 48        # sizeof(dclOptimTensor): four pointers, int64 numel, float step_size, float bc2_sqrt
+
+
+def _optim_tables(table, chunk_tensor, chunk_begin):
+    N.need_cuda(table, chunk_tensor, chunk_begin)
+    assert table.dtype == torch.uint8 and table.dim() == 1 and table.is_contiguous() and table.numel() % OPTIM_TENSOR_BYTES == 0
+    assert chunk_tensor.dtype == torch.int32 and chunk_begin.dtype == torch.int64
+    assert chunk_tensor.dim() == 1 and chunk_tensor.shape == chunk_begin.shape
+    assert chunk_tensor.is_contiguous() and chunk_begin.is_contiguous()
+    assert table.data_ptr() % 8 == 0
+    return table.numel() // OPTIM_TENSOR_BYTES, chunk_tensor.numel()
+
+
+def grad_sqnorm(table, chunk_tensor, chunk_begin):
+    """The 2-norm of all listed gradients together, in float64 (csrc/optim.hip; include/dclnet_hip.h at dcl_grad_sqnorm):
+    table = the packed dclOptimTensor rows (uint8, OPTIM_TENSOR_BYTES each), chunk_tensor i32 / chunk_begin i64 = the chunk
+    table -> (sq_per_tensor (n_tensors,) f64, norm (1,) f64), both on the device.  Deterministic, no host read-back."""
+    n_tensors, n_chunks = _optim_tables(table, chunk_tensor, chunk_begin)
+    dev = table.device
+    sq = torch.zeros(n_tensors, dtype=torch.float64, device=dev)
+    norm = torch.zeros(1, dtype=torch.float64, device=dev)
+    partials = torch.empty(n_chunks, dtype=torch.float64, device=dev)
+    N.check(N.lib().dcl_grad_sqnorm(n_tensors, N.ptr(table), n_chunks, N.ptr(chunk_tensor), N.ptr(chunk_begin),
+                                    N.ptr(partials), N.ptr(sq), N.ptr(norm), N.stream()), "grad_sqnorm")
+    return sq, norm
+
+
+def adam_step(table, chunk_tensor, chunk_begin, grad_scale, beta1, beta2, eps):
+    """torch.optim.Adam's update of every listed tensor in one launch, the gradients multiplied by grad_scale on the way in
+    (dcl_adam_step; the header states the order of operations).  Updates param, exp_avg and exp_avg_sq in place THROUGH RAW
+    POINTERS: the caller moves the tensors' version counters (dcl.optim.Adam does)."""
+    n_tensors, n_chunks = _optim_tables(table, chunk_tensor, chunk_begin)
+    N.check(N.lib().dcl_adam_step(n_tensors, N.ptr(table), n_chunks, N.ptr(chunk_tensor), N.ptr(chunk_begin),
+                                  _c_float(grad_scale), _c_float(beta1), _c_float(beta2), _c_float(eps), N.stream()),
+            "adam_step")
+
+
 def three_interpolate(features, idx, weight):
     N.need_cuda(features, idx, weight)
     assert features.is_contiguous() and idx.is_contiguous() and weight.is_contiguous()

@@ -835,6 +835,55 @@ int dcl_chamfer_bwd(int b, int n, int m, const float *pred, const float *target,
                     const int32_t *idx_pt, const int32_t *idx_tp, const float *g_pt, const float *g_tp,
                     float *grad_pred, float *grad_target, dclStream_t stream);
 
+/* ------------------------------------------------------ optimizer step ---
+ * What follows loss.backward() in the reference's training scripts (tools/train_YCBV_stage1.py:119-125, 212-231): the global
+ * gradient norm that AutoClip measures, and the Adam update with the clip factor folded in (csrc/optim.hip).  Both calls walk
+ * ALL parameter tensors in one launch, driven by two device tables.
+ *   Tensor table, dclOptimTensor[n_tensors]: only the tensors that have a gradient this step.  The four arrays hold `numel`
+ *     (>= 1) contiguous fp32 each; they need no alignment.  step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t),
+ *     evaluated by the host in double from THIS tensor's step count t (1 at its first update) and rounded once to fp32, so a
+ *     tensor that had no gradient in some earlier step still gets its own corrections.  dcl_grad_sqnorm reads grad and numel only.
+ *   Chunk table, chunk_tensor[n_chunks] / chunk_begin[n_chunks]: chunk c covers the elements [chunk_begin[c],
+ *     min(chunk_begin[c] + DCL_OPTIM_CHUNK, numel)) of tensor chunk_tensor[c]; every element of every tensor lies in exactly
+ *     one chunk, the chunks of a tensor are consecutive and ascending and the first begins at 0.  One 256-thread workgroup
+ *     takes one chunk.  Where the chunk is full and its addresses are 16-byte aligned the lanes move 16-byte vectors (lane l
+ *     holds the vectors l, l + 256, l + 512, l + 768 of the chunk, all loads issued before the first use), elsewhere scalars
+ *     with the same element-to-lane map.                                                                                   */
+#define DCL_OPTIM_CHUNK 4096
+typedef struct dclOptimTensor {
+  float *param;
+  const float *grad;
+  float *exp_avg;
+  float *exp_avg_sq;
+  int64_t numel;
+  float step_size;
+  float bc2_sqrt;
+} dclOptimTensor;
+/* sq_per_tensor[t] = sum of grad_t[i]^2 in float64, norm[0] = sqrt of their sum: the 2-norm of all gradients together.
+ * Launch 1: workgroup c writes partials[c] = the sum of (double)g * (double)g (exact products) over its chunk: lane l adds its
+ * elements 4 (l + 256 k) + j in the order k, j ascending, the 64 lanes of a wave combine by an xor butterfly (distances 32, 16,
+ * .. 1) and the four wave sums are added as (w0 + w1) + (w2 + w3).  Launch 2, one workgroup: sq_per_tensor[t] = that tensor's
+ * partials added in ascending chunk order, total = sq_per_tensor added in ascending tensor order, norm[0] = sqrt(total).
+ * No atomics, no workgroup waits on another: the same inputs give the same bits in every call, and the result does not depend
+ * on the grid.  partials: n_chunks doubles, sq_per_tensor: n_tensors, norm: one; the caller owns all three.                */
+int dcl_grad_sqnorm(int n_tensors, const dclOptimTensor *table, int n_chunks, const int32_t *chunk_tensor,
+                    const int64_t *chunk_begin, double *partials, double *sq_per_tensor, double *norm, dclStream_t stream);
+/* torch.optim.Adam's update (no weight decay, no amsgrad) of every listed tensor in one launch, the gradient scaled by
+ * grad_scale (the clip factor) on the way in.  Per element, in fp32, every line one correctly rounded operation after the
+ * other in exactly this order (no contraction into fma; division and sqrtf are the correctly rounded ones):
+ *     g' = g * grad_scale                       (grad_scale == 1.0f leaves g's bits alone)
+ *     m  = m*beta1 + g'*omb1                    omb1 = (float)(1.0 - (double)beta1)
+ *     v  = v*beta2 + (g'*g')*omb2               omb2 = (float)(1.0 - (double)beta2)
+ *     d  = sqrtf(v)/bc2_sqrt + eps
+ *     p  = p - step_size*(m/d)
+ * This order is part of the contract (tests/test_gpu_optim.py compares bit for bit against it).  param, exp_avg and
+ * exp_avg_sq are updated in place; grad is read only.
+ * Both calls: a negative count, n_chunks < n_tensors, a NULL required pointer with n_tensors > 0, a non-finite grad_scale,
+ * beta1 or beta2 outside [0, 1) and eps <= 0 return DCL_EINVAL before any GPU call; n_tensors == 0 returns 0 without a
+ * launch.                                                                                                                  */
+int dcl_adam_step(int n_tensors, const dclOptimTensor *table, int n_chunks, const int32_t *chunk_tensor,
+                  const int64_t *chunk_begin, float grad_scale, float beta1, float beta2, float eps, dclStream_t stream);
+
 /* The loaders' point-sampling draws, bit for bit (host code, no GPU call): for each of k objects out[o*n .. o*n+n) =
  * np.random.permutation(m[o])[:n] = what np.random.choice(m[o], n, replace=False) returns (YCBV/dataloader_test_YCBV.py:166-169,
  * LM/dataloader_test_LM.py:176-181) -- numpy's legacy Fisher-Yates walk (mtrand.pyx: _shuffle_raw, random_interval: MT19937

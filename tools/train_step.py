@@ -1,17 +1,34 @@
 #!/usr/bin/env python3
-"""Training-step timing (forward in train mode + loss + backward + Adam) on synthetic crops: tools/train_step.py [b] [N]"""
-import importlib, os, sys, time
+"""Training-step timing (forward in train mode + loss + backward + Adam) on synthetic crops:
+tools/train_step.py [b] [N] [--optim torch|fused] [--autoclip]
+--optim fused: dcl.optim.Adam (csrc/optim.hip) instead of torch.optim.Adam; --autoclip: AutoClip(50) in front of the step, as
+the reference's training scripts run it -- the per-tensor .item() form with --optim torch, dcl.optim.AutoClip with fused."""
+import argparse, importlib, os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 dcl = importlib.import_module("dcl-net_amd")
-b = int(sys.argv[1]) if len(sys.argv) > 1 else 8
-n = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
+ap = argparse.ArgumentParser()
+ap.add_argument("b", type=int, nargs="?", default=8)
+ap.add_argument("n", type=int, nargs="?", default=1024)
+ap.add_argument("--optim", choices=("torch", "fused"), default="torch")
+ap.add_argument("--autoclip", action="store_true")
+args = ap.parse_args()
+b, n = args.b, args.n
 net = dcl.DCL_Net.Network(dcl.synth.default_cfg(n, n), mode="train")
 net.load_state_dict(dcl.synth.synth_state_dict(net, 1))
 net = net.cuda().train()
 crit = dcl.DCL_Net.losses(None)
-opt = torch.optim.Adam(net.parameters(), lr=1e-4)
+clip = None
+if args.optim == "fused":
+    opt = dcl.optim.Adam(net.parameters(), lr=1e-4)
+    if args.autoclip:
+        clip = dcl.optim.AutoClip(50, optimizer=opt)
+else:
+    opt = torch.optim.Adam(net.parameters(), lr=1e-4)
+    if args.autoclip:
+        from bench_optim import ItemAutoClip
+        clip = ItemAutoClip(50)
 data = dcl.synth.make_batch(b, n, n)
 data["flags"] = torch.zeros(b)
 def step():
@@ -19,10 +36,11 @@ def step():
     pred = net(data)
     loss = crit(pred, data["labels"])["loss_all"]
     loss.backward()
+    if clip is not None: clip(net)
     opt.step()
     return loss
 for _ in range(3): step()
 torch.cuda.synchronize(); t0 = time.perf_counter()
 for _ in range(10): l = step()
 torch.cuda.synchronize()
-print("train step b=%d N=M=%d: %.1f ms (loss %.4f), peak mem %.2f GB" % (b, n, (time.perf_counter() - t0) / 10 * 1e3, float(l.detach()), torch.cuda.max_memory_allocated() / 1e9))
+print("train step b=%d N=M=%d (optim %s%s): %.1f ms (loss %.4f), peak mem %.2f GB" % (b, n, args.optim, " + autoclip" if clip is not None else "", (time.perf_counter() - t0) / 10 * 1e3, float(l.detach()), torch.cuda.max_memory_allocated() / 1e9))
