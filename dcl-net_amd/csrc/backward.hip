@@ -12,7 +12,9 @@
 // gradient is a 27-term gather in the reference's ascending-offset order (bit-exact).  dW is a rows-contracted MFMA GEMM per
 // offset: both operands are read straight from global memory with the 32 lanes of a half-wave on 32 consecutive channels
 // (coalesced 128-B segments), split over row ranges into partial sums that a second kernel adds in split order
-// (deterministic; the reference's cuBLAS order is unspecified, so parity is by tolerance).  pointnet_sp's interpolation
+// (deterministic; the reference's cuBLAS order is unspecified, so parity is by tolerance -- and bit for bit on exactly
+// representable operands, whose partial sums are integers below 2^24 in any order: tests/test_gpu_conv_backward.py).
+// pointnet_sp's interpolation
 // gradient is an ordered gather of its own (readout_grad.hip: row-major (n, C) rows, flat over all crops, a workspace linear
 // in the problem); the reference's atomic scatter stays below as dcl_three_interpolate_grad_sp, the unspecified-order form
 // that tests and tools/bench_readout_grad.py compare it with, and nothing on the training path calls it.  pointnet_lib's three

@@ -1747,7 +1747,7 @@ def sparse_conv_backward(feat, W, dout, nbr, n_out, subm, need_dx=True):
     dout = dout.contiguous()
     dW = torch.zeros((kvol, cin, cout), dtype=torch.float32, device=dev)
     dx = None
-    if n_out > 0:
+    if n_out > 0 and n_in > 0:                                     # (no input rows: no pair, dW = 0 -- and no feat pointer)
         splits = C.c_int32(0)
         N.check(N.lib().dcl_sparse_conv_wgrad_splits(int(n_out), C.byref(splits)), "wgrad_splits")
         partial = torch.empty(splits.value * kvol * cin * cout, dtype=torch.float32, device=dev)

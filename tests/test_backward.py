@@ -1,5 +1,7 @@
 """Training-side kernels (csrc/backward.hip, dcl-net_amd/autograd.py) vs the numpy restatement of the reference's
-backward code (oracle/backward.py)."""
+backward code (oracle/backward.py), at a few hundred rows.  The sparse-conv and pool gradients at training row counts -- every
+kernel family and decomposition of the dX route, several wgrad splits -- are in tests/test_gpu_conv_backward.py, against the
+float64 / exact-integer reference of tests/conv_grad_cases.py."""
 import numpy as np
 import pytest
 import torch
