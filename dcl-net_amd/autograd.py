@@ -207,3 +207,76 @@ class Ortho9dFn(Function):
     def backward(ctx, grad_R):
         o9, = ctx.saved_tensors
         return _ops.ortho9d_backward(o9, _ops.N.f32c(grad_R))
+
+
+class RigidPointsFn(Function):
+    """Rigid transform of b clouds with its gradient on the device: pts (b,n,3), R (b,3,3), t (b,3), inverse -> (b,n,3);
+    inverse False: R p + t, True: R^T (p - t).  Forward = ops.rigid_points, backward = ops.rigid_points_backward: g_R and g_t
+    are sums over a crop's points in the pinned order (deterministic), the gradient of pts is formed only when it is asked
+    for.  No vendor GEMM in either pass.  CUDA tensors only."""
+
+    @staticmethod
+    def forward(ctx, pts, R, t, inverse=False):
+        if not (pts.is_cuda and R.is_cuda and t.is_cuda):
+            raise RuntimeError("RigidPointsFn (objective='fused') runs on the GPU only: got %s / %s / %s tensors; the "
+                               "'module' objective serves CPU tensors" % (pts.device, R.device, t.device))
+        pts, R, t = _ops.N.f32c(pts), _ops.N.f32c(R), _ops.N.f32c(t)
+        ctx.save_for_backward(pts, R, t)
+        ctx.inverse = bool(inverse)
+        return _ops.rigid_points(pts, R, t, ctx.inverse)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        pts, R, t = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if not (need[0] or need[1] or need[2]):
+            return None, None, None, None
+        g_R, g_t, g_pts = _ops.rigid_points_backward(pts, R, t, ctx.inverse, _ops.N.f32c(g_out), need_pts=need[0])
+        return g_pts, (g_R if need[1] else None), (g_t if need[2] else None), None
+
+
+class PoseObjectiveFn(Function):
+    """The per-point terms of the training objective and their ordered sums as ONE packed tensor (ops.pose_objective):
+    apply(posed, posed_gt, sym, cd_pose_pt, cd_pose_tp[, Yc, cano_pred, cano_gt, Xo, conf, cd_Xo_pt, cd_Xo_tp, cd_Yc_pt,
+    cd_Yc_tp]) -> packed (5,) = [loss_pose, loss_Xo, loss_Yc, loss_conf, loss_all].  Gradients go to posed, Xo, Yc, conf and
+    the six Chamfer halves (one launch, ops.pose_objective_backward; the upstream gradient stays on the device); posed_gt,
+    cano_pred, cano_gt and sym take none and ride on ctx.  Saved for the backward: the inputs it reads and the per-point rows
+    L -- not packed, not the per-crop sums."""
+
+    @staticmethod
+    def forward(ctx, posed, posed_gt, sym, cd_pose_pt, cd_pose_tp, Yc=None, cano_pred=None, cano_gt=None, Xo=None, conf=None,
+                cd_Xo_pt=None, cd_Xo_tp=None, cd_Yc_pt=None, cd_Yc_tp=None):
+        c = _ops.N.f32c
+        full = Xo is not None
+        posed, posed_gt, sym = c(posed), c(posed_gt), c(sym)
+        cd_pose = (c(cd_pose_pt), c(cd_pose_tp))
+        if full:
+            Yc, cano_pred, cano_gt, Xo, conf = c(Yc), c(cano_pred), c(cano_gt), c(Xo), c(conf)
+            cd_Xo, cd_Yc = (c(cd_Xo_pt), c(cd_Xo_tp)), (c(cd_Yc_pt), c(cd_Yc_tp))
+        else:
+            cd_Xo = cd_Yc = None
+        packed, L = _ops.pose_objective(posed, posed_gt, sym, cd_pose, Yc, cano_pred, cano_gt, Xo, conf, cd_Xo, cd_Yc)
+        # the backward reads the clouds, conf and L; the Chamfer halves enter it only through sym (their gradients are
+        # per-crop constants), so they are not kept
+        ctx.save_for_backward(*((posed, Yc, Xo, conf, L) if full else (posed,)))
+        ctx.fixed = (posed_gt, sym, cano_pred, cano_gt)
+        ctx.full = full
+        return packed
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_packed):
+        posed_gt, sym, cano_pred, cano_gt = ctx.fixed
+        g_packed = _ops.N.f32c(g_packed)
+        if ctx.full:
+            posed, Yc, Xo, conf, L = ctx.saved_tensors
+        else:
+            posed, = ctx.saved_tensors
+            Yc = Xo = conf = L = None
+        g_posed, g_Xo, g_Yc, g_conf, g_cdp, g_cdx, g_cdy = _ops.pose_objective_backward(
+            g_packed, posed, posed_gt, sym, Yc, cano_pred, cano_gt, Xo, conf, L)
+        if not ctx.full:
+            return g_posed, None, None, g_cdp[0], g_cdp[1]
+        return (g_posed, None, None, g_cdp[0], g_cdp[1], g_Yc, None, None, g_Xo, g_conf, g_cdx[0], g_cdx[1], g_cdy[0],
+                g_cdy[1])

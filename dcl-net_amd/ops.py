@@ -723,6 +723,176 @@ def chamfer_backward(pred, target, idx_pt, idx_tp, g_pt, g_tp, active=None, need
     return grad_pred, grad_target
 
 
+def _f32_like(t, shape, what):
+    assert t.dtype == torch.float32 and tuple(t.shape) == tuple(shape) and t.is_contiguous(), \
+        "%s: fp32 contiguous %s wanted, got %s %s" % (what, tuple(shape), t.dtype, tuple(t.shape))
+
+
+def _same_side(host, what, *ts):
+    """host twins take CPU tensors, the kernels the GPU's"""
+    for t in ts:
+        if t is not None and t.is_cuda == host:
+            raise RuntimeError("%s takes %s tensors (got a %s one)%s" % (
+                what, "CPU" if host else "GPU", t.device, "" if host else "; no CPU fallback"))
+
+
+def _rigid_args(pts, R, t, inverse, host, what):
+    _same_side(host, what, pts, R, t)
+    assert pts.dim() == 3 and pts.shape[2] == 3, tuple(pts.shape)
+    b, n = pts.shape[0], pts.shape[1]
+    _f32_like(pts, (b, n, 3), "pts")
+    _f32_like(R, (b, 3, 3), "R")
+    _f32_like(t, (b, 3), "t")
+    return b, n, int(bool(inverse))
+
+
+def _rigid_points(pts, R, t, inverse, host):
+    b, n, inv = _rigid_args(pts, R, t, inverse, host, "rigid_points_host" if host else "rigid_points")
+    out = torch.empty_like(pts)
+    if host:
+        N.check(N.lib().dcl_rigid_points_host(b, n, N.ptr(pts), N.ptr(R), N.ptr(t), inv, N.ptr(out)), "rigid_points_host")
+    else:
+        N.check(N.lib().dcl_rigid_points(b, n, N.ptr(pts), N.ptr(R), N.ptr(t), inv, N.ptr(out), N.stream()), "rigid_points")
+    return out
+
+
+def _rigid_points_backward(pts, R, t, inverse, g_out, need_pts, host):
+    what = "rigid_points_backward_host" if host else "rigid_points_backward"
+    b, n, inv = _rigid_args(pts, R, t, inverse, host, what)
+    _same_side(host, what, g_out)
+    _f32_like(g_out, (b, n, 3), "g_out")
+    g_R, g_t = torch.empty_like(R), torch.empty_like(t)
+    g_pts = torch.empty_like(pts) if need_pts else None
+    if host:
+        N.check(N.lib().dcl_rigid_points_bwd_host(b, n, N.ptr(pts), N.ptr(R), N.ptr(t), inv, N.ptr(g_out), N.ptr(g_R),
+                                                  N.ptr(g_t), N.ptr(g_pts)), what)
+    else:
+        N.check(N.lib().dcl_rigid_points_bwd(b, n, N.ptr(pts), N.ptr(R), N.ptr(t), inv, N.ptr(g_out), N.ptr(g_R), N.ptr(g_t),
+                                             N.ptr(g_pts), N.stream()), what)
+    return g_R, g_t, g_pts
+
+
+def rigid_points(pts, R, t, inverse=False):
+    """Rigid transform of b clouds in one launch (dcl_rigid_points): pts (b,n,3), R (b,3,3), t (b,3), fp32 contiguous ->
+    (b,n,3).  inverse=False: R p + t (= bmm(p, R^T) + t); inverse=True: R^T (p - t) (= bmm(p - t, R)).  No vendor GEMM."""
+    return _rigid_points(pts, R, t, inverse, False)
+
+
+def rigid_points_backward(pts, R, t, inverse, g_out, need_pts=False):
+    """Gradients of rigid_points (dcl_rigid_points_bwd): g_out (b,n,3) -> (g_R (b,3,3), g_t (b,3), g_pts (b,n,3) or None).
+    The sums over a crop's points run in the order include/dclnet_hip.h pins: the same inputs give the same bits."""
+    return _rigid_points_backward(pts, R, t, inverse, g_out, need_pts, False)
+
+
+def rigid_points_host(pts, R, t, inverse=False):
+    """rigid_points on CPU tensors (the kernel's routine compiled for the host).  For checking the arithmetic where there is
+    no GPU; no model path calls it."""
+    return _rigid_points(pts, R, t, inverse, True)
+
+
+def rigid_points_backward_host(pts, R, t, inverse, g_out, need_pts=False):
+    """rigid_points_backward on CPU tensors, in the kernel's summation order; no model path calls it."""
+    return _rigid_points_backward(pts, R, t, inverse, g_out, need_pts, True)
+
+
+_OBJ_OPTIONAL = ("Yc", "cano_pred", "cano_gt", "Xo", "conf", "cd_Xo", "cd_Yc")
+
+
+def _objective_args(posed, posed_gt, sym, cd_pose, Yc, cano_pred, cano_gt, Xo, conf, cd_Xo, cd_Yc, host, what, cd=True):
+    """-> (b, n, full, the pointers of the C argument list after b, n: 8 inputs and, with cd, the 6 Chamfer halves)"""
+    opt = (Yc, cano_pred, cano_gt, Xo, conf) + ((cd_Xo, cd_Yc) if cd else ())
+    full = opt[0] is not None
+    if any((o is not None) != full for o in opt):
+        raise ValueError("%s: %s go together: all of them, or none for the pose-only form" % (what, ", ".join(_OBJ_OPTIONAL)))
+    assert posed.dim() == 3 and posed.shape[2] == 3, tuple(posed.shape)
+    b, n = posed.shape[0], posed.shape[1]
+    clouds = (posed, posed_gt) + ((Yc, cano_pred, cano_gt, Xo) if full else ())
+    halves = (tuple(cd_pose) + ((tuple(cd_Xo) + tuple(cd_Yc)) if full else ())) if cd else ()
+    assert len(halves) == ((6 if full else 2) if cd else 0), "every cd_* is the pair (dist_pt, dist_tp) of one chamfer call"
+    _same_side(host, what, sym, *(clouds + halves + ((conf,) if full else ())))
+    for c in clouds:
+        _f32_like(c, (b, n, 3), "cloud")
+    for h in halves:
+        _f32_like(h, (b, n), "chamfer half")
+    _f32_like(sym, (b,), "sym")
+    if full:
+        _f32_like(conf, (b, 2 * n), "conf")
+    p = N.ptr
+    ptrs = (p(posed), p(posed_gt), p(Yc), p(cano_pred), p(cano_gt), p(Xo), p(conf), p(sym))
+    if cd:
+        cdx, cdy = (cd_Xo, cd_Yc) if full else ((None, None), (None, None))
+        ptrs += (p(cd_pose[0]), p(cd_pose[1]), p(cdx[0]), p(cdx[1]), p(cdy[0]), p(cdy[1]))
+    return b, n, full, ptrs
+
+
+def _pose_objective(posed, posed_gt, sym, cd_pose, Yc, cano_pred, cano_gt, Xo, conf, cd_Xo, cd_Yc, host):
+    what = "pose_objective_host" if host else "pose_objective"
+    b, n, full, ptrs = _objective_args(posed, posed_gt, sym, cd_pose, Yc, cano_pred, cano_gt, Xo, conf, cd_Xo, cd_Yc, host, what)
+    dev = posed.device
+    L = torch.empty((b, 2 * n), dtype=torch.float32, device=dev) if full else None
+    crop_sums = torch.empty((max(b, 1), 5), dtype=torch.float32, device=dev)
+    packed = torch.zeros((5,), dtype=torch.float32, device=dev) if b == 0 else torch.empty((5,), dtype=torch.float32, device=dev)
+    if host:
+        N.check(N.lib().dcl_pose_objective_fwd_host(b, n, *ptrs, N.ptr(L), N.ptr(crop_sums), N.ptr(packed)), what)
+    else:
+        N.check(N.lib().dcl_pose_objective_fwd(b, n, *ptrs, N.ptr(L), N.ptr(crop_sums), N.ptr(packed), N.stream()), what)
+    return packed, L
+
+
+def _pose_objective_backward(g_packed, posed, posed_gt, sym, Yc, cano_pred, cano_gt, Xo, conf, L, host):
+    what = "pose_objective_backward_host" if host else "pose_objective_backward"
+    b, n, full, ptrs = _objective_args(posed, posed_gt, sym, None, Yc, cano_pred, cano_gt, Xo, conf, None, None, host, what,
+                                       cd=False)
+    _same_side(host, what, g_packed, L)
+    _f32_like(g_packed, (5,), "g_packed")
+    assert (L is not None) == full, "L goes with the full form"
+    if full:
+        _f32_like(L, (b, 2 * n), "L")
+    dev = posed.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)                  # noqa: E731
+    g_posed = new(b, n, 3)
+    g_cd = [new(b, n) for _ in range(6 if full else 2)] + ([] if full else [None] * 4)
+    g_Xo, g_Yc, g_conf = (new(b, n, 3), new(b, n, 3), new(b, 2 * n)) if full else (None, None, None)
+    outs = (N.ptr(g_packed), N.ptr(g_posed), N.ptr(g_Xo), N.ptr(g_Yc), N.ptr(g_conf)) + tuple(N.ptr(g) for g in g_cd)
+    if host:
+        N.check(N.lib().dcl_pose_objective_bwd_host(b, n, *ptrs, N.ptr(L), *outs), what)
+    else:
+        N.check(N.lib().dcl_pose_objective_bwd(b, n, *ptrs, N.ptr(L), *outs, N.stream()), what)
+    return g_posed, g_Xo, g_Yc, g_conf, (g_cd[0], g_cd[1]), (g_cd[2], g_cd[3]), (g_cd[4], g_cd[5])
+
+
+def pose_objective(posed, posed_gt, sym, cd_pose, Yc=None, cano_pred=None, cano_gt=None, Xo=None, conf=None, cd_Xo=None,
+                   cd_Yc=None):
+    """The per-point terms of `losses.forward` and their ordered sums (dcl_pose_objective_fwd; include/dclnet_hip.h has the
+    formulas and the pinned summation order).  posed, posed_gt, Yc, cano_pred, cano_gt, Xo (b,n,3); conf (b,2n); sym (b,)
+    float; cd_pose, cd_Xo, cd_Yc: the (dist_pt, dist_tp) pairs `chamfer` returned for (posed, posed_gt), (Xo, template),
+    (Yc, posed_gt), each (b,n).  -> (packed (5,) = [loss_pose, loss_Xo, loss_Yc, loss_conf, loss_all], L (b,2n) = the
+    per-point [loss_Xo | loss_Yc] rows the backward reads).  With the optional arguments all None only the pose term is
+    formed (`losses_refiner`): packed = [loss_pose, 0, 0, 0, loss_pose], L = None.  No host synchronisation."""
+    return _pose_objective(posed, posed_gt, sym, cd_pose, Yc, cano_pred, cano_gt, Xo, conf, cd_Xo, cd_Yc, False)
+
+
+def pose_objective_backward(g_packed, posed, posed_gt, sym, Yc=None, cano_pred=None, cano_gt=None, Xo=None, conf=None, L=None):
+    """Every gradient of pose_objective in one launch (dcl_pose_objective_bwd): g_packed (5,) the upstream gradient of
+    packed, on the device; the clouds, conf, sym as the forward took them and the L it returned (the Chamfer halves are not
+    read: their gradients depend on sym alone) -> (g_posed, g_Xo, g_Yc, g_conf, g_cd_pose, g_cd_Xo, g_cd_Yc), the last
+    three (pt, tp) pairs; the pose-only form returns None for what it does not have.  Deterministic."""
+    return _pose_objective_backward(g_packed, posed, posed_gt, sym, Yc, cano_pred, cano_gt, Xo, conf, L, False)
+
+
+def pose_objective_host(posed, posed_gt, sym, cd_pose, Yc=None, cano_pred=None, cano_gt=None, Xo=None, conf=None,
+                        cd_Xo=None, cd_Yc=None):
+    """pose_objective on CPU tensors: the kernels' routines compiled for the host, in their summation order.  For checking the
+    arithmetic where there is no GPU; no model path calls it."""
+    return _pose_objective(posed, posed_gt, sym, cd_pose, Yc, cano_pred, cano_gt, Xo, conf, cd_Xo, cd_Yc, True)
+
+
+def pose_objective_backward_host(g_packed, posed, posed_gt, sym, Yc=None, cano_pred=None, cano_gt=None, Xo=None, conf=None,
+                                 L=None):
+    """pose_objective_backward on CPU tensors; no model path calls it."""
+    return _pose_objective_backward(g_packed, posed, posed_gt, sym, Yc, cano_pred, cano_gt, Xo, conf, L, True)
+
+
 OPTIM_CHUNK = 4096             # include/dclnet_hip.h: DCL_OPTIM_CHUNK
 OPTIM_TENSOR_BYTES = 48        # sizeof(dclOptimTensor): four pointers, int64 numel, float step_size, float bc2_sqrt
 

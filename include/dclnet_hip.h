@@ -835,6 +835,78 @@ int dcl_chamfer_bwd(int b, int n, int m, const float *pred, const float *target,
                     const int32_t *idx_pt, const int32_t *idx_tp, const float *g_pt, const float *g_tp,
                     float *grad_pred, float *grad_target, dclStream_t stream);
 
+/* The rest of the objective (models/DCL_Net.py:264-304, models/refiner.py:101-125; csrc/objective.hip, csrc/objective.h).
+ * All arrays fp32 contiguous.  fma(a,b,c) is one rounding; everything else is rounded operation by operation as written.
+ *
+ * PINNED ORDER of every per-crop sum below: one workgroup of 256 lanes per crop; lane l adds the terms of points l, l+256,
+ * l+512, ... ascending into its own accumulator (from 0); the 256 accumulators are folded by a tree with strides 128, 64,
+ * ..., 1 (slot l += slot l+stride for l < stride).  Crops are added afterwards in ascending order (from 0).  No float atomics:
+ * the same inputs give the same bits.  The *_host entry points run the same routines on HOST pointers and make no GPU call.
+ *
+ * dcl_rigid_points: pts (b,n,3), R (b,3,3), t (b,3) -> out (b,n,3), one launch.
+ *   inverse == 0: out_i = R p_i + t   (bmm(p, R^T) + t), row r = fma(R_r2,p_2, fma(R_r1,p_1, R_r0*p_0)) + t_r
+ *   inverse == 1: out_i = R^T (p_i - t)   (bmm(p - t, R)), q = p_i - t, column c = fma(R_2c,q_2, fma(R_1c,q_1, R_0c*q_0))
+ * dcl_rigid_points_bwd: g_out (b,n,3) -> g_R (b,3,3), g_t (b,3), g_pts (b,n,3; may be NULL: skipped), all OVERWRITTEN, one
+ * launch.  Per point, accumulated in the pinned order:
+ *   inverse == 0: g_R[r][c] = fma(g_r, p_c, g_R[r][c]); g_t[r] += g_r;        g_pts_i = R^T g_i
+ *   inverse == 1: g_R[r][c] = fma(q_r, g_c, g_R[r][c]); g_t[r] -= (R g_i)_r;  g_pts_i = R g_i
+ * b < 0, n < 1, inverse not 0 / 1, a NULL required pointer with b > 0 return DCL_EINVAL before any GPU call; b == 0 returns 0. */
+int dcl_rigid_points(int b, int n, const float *pts, const float *R, const float *t, int inverse, float *out,
+                     dclStream_t stream);
+int dcl_rigid_points_bwd(int b, int n, const float *pts, const float *R, const float *t, int inverse, const float *g_out,
+                         float *g_R, float *g_t, float *g_pts, dclStream_t stream);
+int dcl_rigid_points_host(int b, int n, const float *pts, const float *R, const float *t, int inverse, float *out);
+int dcl_rigid_points_bwd_host(int b, int n, const float *pts, const float *R, const float *t, int inverse,
+                              const float *g_out, float *g_R, float *g_t, float *g_pts);
+/* dcl_pose_objective_fwd: the per-point terms and their sums.  posed, posed_gt, Yc, cano_pred, cano_gt, Xo (b,n,3); conf
+ * (b,2n); sym (b,) the float multiplier of the formula; cd_*_pt / cd_*_tp (b,n) the two halves dcl_chamfer_fwd returned for
+ * (posed, posed_gt), (Xo, template) and (Yc, posed_gt).  With s = sym[crop], |a - b| = sqrt(fma(dz,dz, fma(dy,dy, dx*dx))):
+ *   pose_i = (1-s) * |posed_i - posed_gt_i| + s * (0.5 * (cd_pose_pt_i + cd_pose_tp_i))
+ *   LXo_i  = (1-s) * |Xo_i - cano_gt_i|  + (0.5*s) * (0.5 * (cd_Xo_pt_i + cd_Xo_tp_i) + |Xo_i - cano_pred_i|)
+ *   LYc_i  = (1-s) * |Yc_i - posed_gt_i| + (0.5*s) * (0.5 * (cd_Yc_pt_i + cd_Yc_tp_i) + |Yc_i - posed_i|)
+ *   conf terms  LXo_i * conf[i] - 0.01 * log(conf[i])  and  LYc_i * conf[n+i] - 0.01 * log(conf[n+i])
+ * Outputs: L (b,2n) = [LXo | LYc] per crop (kept for the backward); crop_sums (b,5) = per crop, in the pinned order, the sums
+ * of pose, LXo, LYc, the conf terms of the Xo half and those of the Yc half; packed (5,) = [loss_pose, loss_Xo, loss_Yc,
+ * loss_conf, loss_all] with T_k = column k of crop_sums added over the crops ascending:
+ *   loss_pose = T_0 / (b n), loss_Xo = T_1 / (b n), loss_Yc = T_2 / (b n), loss_conf = (T_3 + T_4) / (2 b n),
+ *   loss_all = ((loss_pose + 5 * loss_Xo) + loss_Yc) + loss_conf.
+ * Two launches (per-crop sums; one wave adds the crops).  conf <= 0 is not guarded: it gives what log gives.
+ * Pose-only form (the refiner's loss): Yc, cano_pred, cano_gt, Xo, conf, cd_Xo_*, cd_Yc_* and L all NULL -> packed =
+ * [loss_pose, 0, 0, 0, loss_pose]; only column 0 of crop_sums is meaningful.
+ *
+ * dcl_pose_objective_bwd: one launch, no reduction.  It takes the forward's clouds, conf, sym and L, not the Chamfer halves
+ * (their gradients depend on sym alone).  g_packed (5,) is the DEVICE upstream gradient of packed; the weights
+ *   W_pose = (g0 + g4) / (b n), W_Xo = fma(5, g4, g1) / (b n), W_Yc = (g2 + g4) / (b n), W_conf = (g3 + g4) / (2 b n)
+ * are formed on the device.  With u_k(a, b) = (k / |a - b|) (a - b), 0 where |a - b| == 0 (torch.norm's subgradient):
+ *   g_posed_i = u_{W_pose (1-s)}(posed_i, posed_gt_i)                   (posed is detached inside LYc)
+ *   g_Xo_i    = u_{W_Xo (1-s)}(Xo_i, cano_gt_i)  + u_{W_Xo 0.5 s}(Xo_i, cano_pred_i)
+ *   g_Yc_i    = u_{W_Yc (1-s)}(Yc_i, posed_gt_i) + u_{W_Yc 0.5 s}(Yc_i, posed_i)
+ *   g_conf_j  = W_conf * (L_j - 0.01 / conf_j)                          (L is detached inside loss_conf)
+ *   g_cd_pose_{pt,tp}_i = (W_pose s) * 0.5,  g_cd_Xo_{pt,tp}_i = (W_Xo 0.5 s) * 0.5,  g_cd_Yc_{pt,tp}_i = (W_Yc 0.5 s) * 0.5
+ * All outputs OVERWRITTEN.  Pose-only form: the optional inputs, L and g_Xo, g_Yc, g_conf, g_cd_Xo_*, g_cd_Yc_* all NULL.
+ * Both calls: b < 0, n < 1, a NULL required pointer or a PARTIAL set of the optional ones (with b > 0) return DCL_EINVAL
+ * before any GPU call; b == 0 returns 0.                                                                                 */
+int dcl_pose_objective_fwd(int b, int n, const float *posed, const float *posed_gt, const float *Yc, const float *cano_pred,
+                           const float *cano_gt, const float *Xo, const float *conf, const float *sym,
+                           const float *cd_pose_pt, const float *cd_pose_tp, const float *cd_Xo_pt, const float *cd_Xo_tp,
+                           const float *cd_Yc_pt, const float *cd_Yc_tp, float *L, float *crop_sums, float *packed,
+                           dclStream_t stream);
+int dcl_pose_objective_bwd(int b, int n, const float *posed, const float *posed_gt, const float *Yc, const float *cano_pred,
+                           const float *cano_gt, const float *Xo, const float *conf, const float *sym, const float *L,
+                           const float *g_packed,
+                           float *g_posed, float *g_Xo, float *g_Yc, float *g_conf, float *g_cd_pose_pt, float *g_cd_pose_tp,
+                           float *g_cd_Xo_pt, float *g_cd_Xo_tp, float *g_cd_Yc_pt, float *g_cd_Yc_tp, dclStream_t stream);
+int dcl_pose_objective_fwd_host(int b, int n, const float *posed, const float *posed_gt, const float *Yc,
+                                const float *cano_pred, const float *cano_gt, const float *Xo, const float *conf,
+                                const float *sym, const float *cd_pose_pt, const float *cd_pose_tp, const float *cd_Xo_pt,
+                                const float *cd_Xo_tp, const float *cd_Yc_pt, const float *cd_Yc_tp, float *L,
+                                float *crop_sums, float *packed);
+int dcl_pose_objective_bwd_host(int b, int n, const float *posed, const float *posed_gt, const float *Yc,
+                                const float *cano_pred, const float *cano_gt, const float *Xo, const float *conf,
+                                const float *sym, const float *L, const float *g_packed, float *g_posed, float *g_Xo, float *g_Yc, float *g_conf,
+                                float *g_cd_pose_pt, float *g_cd_pose_tp, float *g_cd_Xo_pt, float *g_cd_Xo_tp,
+                                float *g_cd_Yc_pt, float *g_cd_Yc_tp);
+
 /* ------------------------------------------------------ optimizer step ---
  * What follows loss.backward() in the reference's training scripts (tools/train_YCBV_stage1.py:119-125, 212-231): the global
  * gradient norm that AutoClip measures, and the Adam update with the clip factor folded in (csrc/optim.hip).  Both calls walk
