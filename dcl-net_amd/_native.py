@@ -35,6 +35,13 @@ def _open(path):
     if got != ABI_VERSION:
         raise RuntimeError("%s speaks C-ABI version %d, this package calls version %d (include/dclnet_hip.h): rebuild the "
                            "library (make -C dcl-net_amd/csrc)" % (path, got, ABI_VERSION))
+    # csrc/linear_bwd.hip: int64 pitches between int sizes -- declared, so that a plain Python int converts correctly
+    i, i64 = C.c_int, C.c_int64
+    L.dcl_linear_wgrad_splits.argtypes = [i, C.POINTER(C.c_int32)]
+    L.dcl_linear_wgrad.argtypes = [vp, i64, vp, i64, i, i, i, vp, vp, i64, vp]
+    L.dcl_relu_bwd.argtypes = [vp, i64, vp, i64, vp, vp, i64, i, i, i, vp, i64, vp, vp, vp]
+    for fn in (L.dcl_linear_wgrad_splits, L.dcl_linear_wgrad, L.dcl_relu_bwd):
+        fn.restype = i
     return L
 
 

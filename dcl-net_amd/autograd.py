@@ -4,7 +4,8 @@ libs/pointnet_lib/pointnet2_utils.py:40-76,144-238, libs/pointgroup_ops/function
 forward = the inference kernels, backward = csrc/backward.hip; and of the correspondence attention (CrossAttentionFn:
 forward = dcl_cross_attention, backward = csrc/attention_bwd.hip), which the reference forms from bmm and softmax;
 and of the losses' Chamfer distance (ChamferFn: csrc/chamfer.hip in both passes); and of the rotation head's projection
-(Ortho9dFn: forward = dcl_ortho9d_to_matrix, backward = csrc/rotation_grad.hip).
+(Ortho9dFn: forward = dcl_ortho9d_to_matrix, backward = csrc/rotation_grad.hip); and of the stage-2 refiner's shared MLP
+(RefinerShareFn: forward = the own GEMM core, backward = csrc/linear_bwd.hip + the same core).
 Used by the module mirrors (spconv/, libs/) so that `Network(cfg, mode='train')` is trainable on the GPU."""
 import torch
 from torch.autograd import Function
@@ -280,3 +281,66 @@ class PoseObjectiveFn(Function):
             return g_posed, None, None, g_cdp[0], g_cdp[1]
         return (g_posed, None, None, g_cdp[0], g_cdp[1], g_Yc, None, None, g_Xo, g_conf, g_cdx[0], g_cdx[1], g_cdy[0],
                 g_cdy[1])
+
+
+class RefinerShareFn(Function):
+    """The stage-2 refiner's MLP_share (Conv1d 259 -> 512 -> 512 -> 1024, ReLU after each) with the confidence-weighted sum over
+    the points, trained on the library's own GEMM kernels: apply(xyz_pm (M,3), F_pm (M,256), conf_w (b,n), W0, b0, W1, b1, W2,
+    b2) -> shared (b,1024), M = b n, n a multiple of ops.LINEAR_POOL_TILE, the W* the Conv1d weights as registered (out, in, 1).
+    Forward = the calls of Refiner.forward_pm up to `shared` on the fp32-MFMA core (ops.linear_dma, ops.affine3_relu,
+    ops.linear_pool_dma + the tile sum); the split-bf16 core takes no part, the weights change every step.  Saved: the inputs,
+    h1 and h2 -- not the (M,1024) activation, which the backward recomputes into scratch.  Backward: ops.relu_bwd (mask + bias
+    gradient), ops.linear_wgrad (weight gradient) and ops.linear_dma with the registered weight as its (K,N) matrix (input
+    gradient) per layer; layer 0 writes its two weight-gradient blocks (xyz | features) into one (512,259) tensor.  Every
+    reduction has a pinned order: the same inputs give the same gradients bit for bit.  xyz_pm, F_pm and conf_w take no
+    gradient (the training script detaches them): asking for one raises."""
+
+    @staticmethod
+    def forward(ctx, xyz_pm, F_pm, conf_w, W0, b0, W1, b1, W2, b2):
+        if any(ctx.needs_input_grad[:3]):
+            raise ValueError("RefinerShareFn: xyz_pm, F_pm and conf_w take no gradient (detach them)")
+        for t in (xyz_pm, F_pm, conf_w, W0, b0, W1, b1, W2, b2):
+            if not (t.is_cuda and t.dtype == torch.float32):
+                raise RuntimeError("RefinerShareFn runs on float32 CUDA tensors only (got %s on %s)" % (t.dtype, t.device))
+        b, n = conf_w.shape
+        M = b * n
+        if n % _ops.LINEAR_POOL_TILE:
+            raise ValueError("RefinerShareFn: n %% %d == 0 required (the pooling tile), got n = %d" % (_ops.LINEAR_POOL_TILE, n))
+        assert tuple(xyz_pm.shape) == (M, 3) and tuple(F_pm.shape) == (M, F_pm.shape[1]) and W0.shape[1] == 3 + F_pm.shape[1]
+        xyz_pm, F_pm, conf_w = xyz_pm.contiguous(), F_pm.contiguous(), conf_w.contiguous()
+        W0, W1, W2 = W0.contiguous(), W1.contiguous(), W2.contiguous()
+        b0, b1, b2 = b0.contiguous(), b1.contiguous(), b2.contiguous()
+        Wt0 = W0[:, :, 0].t()
+        Wt0x, Wt0f = Wt0[:3].contiguous(), Wt0[3:].contiguous()
+        Wt1, Wt2 = W1[:, :, 0].t().contiguous(), W2[:, :, 0].t().contiguous()
+        feat_term = _ops.linear_dma(F_pm, Wt0f, b0)
+        h1 = _ops.affine3_relu(xyz_pm, Wt0x, feat_term)
+        h2 = _ops.linear_dma(h1, Wt1, b1, True)
+        part = _ops.linear_pool_dma(h2, Wt2, b2, conf_w.reshape(-1), relu=True)
+        ctx.save_for_backward(xyz_pm, F_pm, conf_w, W1, W2, b2, Wt2, h1, h2)
+        return part.view(b, n // _ops.LINEAR_POOL_TILE, -1).sum(dim=1)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_shared):
+        if any(ctx.needs_input_grad[:3]):
+            raise ValueError("RefinerShareFn: xyz_pm, F_pm and conf_w take no gradient (detach them)")
+        xyz_pm, F_pm, conf_w, W1, W2, b2, Wt2, h1, h2 = ctx.saved_tensors
+        b, n = conf_w.shape
+        g_shared = _ops.N.f32c(g_shared)
+        # layer 2: the pooled activation again (scratch), masked and weighted in place
+        h3 = _ops.linear_dma(h2, Wt2, b2, True)
+        dz, db2 = _ops.relu_bwd(h3, roww=conf_w.reshape(-1), gpool=g_shared, rows_per_crop=n, out=h3)
+        dW2 = _ops.linear_wgrad(dz, h2)
+        dh = _ops.linear_dma(dz, W2[:, :, 0])
+        del h3, dz
+        # layer 1
+        dz, db1 = _ops.relu_bwd(h2, dh, out=dh)
+        dW1 = _ops.linear_wgrad(dz, h1)
+        dh = _ops.linear_dma(dz, W1[:, :, 0])
+        # layer 0: no input gradient; the weight's two column blocks
+        dz, db0 = _ops.relu_bwd(h1, dh, out=dh)
+        dW0 = torch.empty((h1.shape[1], 3 + F_pm.shape[1]), dtype=torch.float32, device=dz.device)
+        _ops.linear_wgrad(dz, xyz_pm, out=dW0[:, :3])
+        _ops.linear_wgrad(dz, F_pm, out=dW0[:, 3:])
+        return None, None, None, dW0.unsqueeze(2), db0, dW1.unsqueeze(2), db1, dW2.unsqueeze(2), db2

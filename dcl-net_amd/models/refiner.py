@@ -35,12 +35,21 @@ def _param_version(mod):
 class Refiner(nn.Module):
     POSE_HEADS_MAX = 128      # crops up to which the two heads run as dcl_pose_heads (two launches; Network.POSE_HEADS_MAX)
 
-    def __init__(self, cfg=None, train_rotation="host"):
+    TRAIN_MLP_MODES = ("modules", "kernels")
+
+    def __init__(self, cfg=None, train_rotation="host", train_mlp="modules"):
         """train_rotation: "host" (default) or "device" -- how a call that needs a gradient differentiates the rotation
-        head's projection; see DCL_Net.Network."""
+        head's projection; see DCL_Net.Network.
+        train_mlp: how train() mode runs MLP_share and the pooling.  "modules" (default): the registered nn.Conv1d / nn.ReLU
+        modules (vendor GEMMs in both passes).  "kernels": autograd.RefinerShareFn -- the library's own GEMM core forward, its
+        own weight-gradient GEMM and ReLU / bias kernels backward, every reduction in a pinned order (DESIGN.md section 9);
+        needs n % 128 == 0 and inputs that do not require grad (ValueError otherwise).  eval() mode is the same either way."""
         super().__init__()
         from .DCL_Net import check_train_rotation
         self.train_rotation = check_train_rotation(train_rotation)
+        if train_mlp not in self.TRAIN_MLP_MODES:
+            raise ValueError('train_mlp must be "modules" or "kernels", got %r' % (train_mlp,))
+        self.train_mlp = train_mlp
         self.MLP_share = Head_MultiLayerPerceptron([256 + 3, 512, 512, 1024], ["relu"] * 3, [False] * 3, [0.0] * 3)
         self.regressor_rot2 = Head_MultiLayerPerceptron([1024, 512, 128, 9], ["relu", "relu", "none"], [False] * 3,
                                                         [0.0] * 3)
@@ -135,15 +144,44 @@ class Refiner(nn.Module):
         delta_t = self.regressor_trans2(shared).squeeze(-1)
         return {"trans_pred": delta_t, "rot_pred": ortho9d2matrix(o9[:, :3], o9[:, 3:6], o9[:, 6:], self.train_rotation)}
 
+    def _forward_kernels(self, x, conf):
+        """training path with train_mlp="kernels": the shared MLP and the pooling as autograd.RefinerShareFn on point-major
+        copies of the input (made once; the training script detaches input_features and conf, so no gradient leaves through
+        them), then the two heads as the registered modules on the (b, 1024) pooled feature.  No cached weights: the function
+        reads the registered parameters, so an optimizer step is seen whoever takes it."""
+        from ..autograd import RefinerShareFn
+        b, _, n = x.shape
+        if n % ops.LINEAR_POOL_TILE:
+            raise ValueError('train_mlp="kernels" needs n %% %d == 0 (the pooling tile), got n = %d'
+                             % (ops.LINEAR_POOL_TILE, n))
+        if x.requires_grad or conf.requires_grad:
+            raise ValueError('train_mlp="kernels" takes input_features and conf that do not require grad (the training '
+                             'script detaches them); train_mlp="modules" differentiates through them')
+        conf_w = torch.softmax(conf.unsqueeze(1), dim=2)[:, 0, :1024].contiguous()           # refiner.py:81
+        if tuple(conf_w.shape) != (b, n):
+            raise ValueError('train_mlp="kernels" needs one confidence per point: conf[:, :1024] is %s for n = %d'
+                             % (tuple(conf_w.shape), n))
+        pm = x.float().transpose(1, 2)
+        xyz_pm = pm[:, :, :3].reshape(b * n, 3)
+        F_pm = pm[:, :, 3:].reshape(b * n, -1)
+        L = self.MLP_share.layers
+        shared = RefinerShareFn.apply(xyz_pm, F_pm, conf_w, L[0].weight, L[0].bias, L[2].weight, L[2].bias, L[4].weight,
+                                      L[4].bias).unsqueeze(2)
+        o9 = self.regressor_rot2(shared).squeeze(-1)
+        delta_t = self.regressor_trans2(shared).squeeze(-1)
+        return {"trans_pred": delta_t, "rot_pred": ortho9d2matrix(o9[:, :3], o9[:, 3:6], o9[:, 6:], self.train_rotation)}
+
     def forward(self, input_dict):
         """reference contract: {"input_features" (b,259,n), "conf" (b,n+m), "obj_idx"} ->
-        {"trans_pred" (b,3), "rot_pred" (b,3,3)}.  train() mode: differentiable module path; eval(): fused inference
-        path (folded weights, no autograd graph)."""
+        {"trans_pred" (b,3), "rot_pred" (b,3,3)}.  train() mode: differentiable module path (train_mlp="kernels": its shared
+        MLP on the library's own kernels); eval(): fused inference path (folded weights, no autograd graph)."""
         x = input_dict["input_features"]
         conf = input_dict["conf"]
         if not x.is_cuda:
             raise RuntimeError("dcl-net_amd.Refiner runs on the GPU only (no CPU fallback)")
         if self.training:
+            if self.train_mlp == "kernels":
+                return self._forward_kernels(x, conf)
             return self._forward_modules(x, conf)
         with torch.no_grad():
             f = self._fold()

@@ -2044,3 +2044,84 @@ def voxelize_bp(d_out, map_rule, n_points, mode=4):
     N.check(N.lib().dcl_voxelize_bp(N.ptr(d_out.contiguous()), N.ptr(map_rule), N.ptr(d_feats), M, map_rule.shape[1] - 1, c,
                                     int(mode == 4), N.stream()), "voxelize_bp")
     return d_feats
+
+
+# ------------------------------------------------------------------------------------ Linear + ReLU stacks: training side
+WGRAD_ROWS = 512               # include/dclnet_hip.h: DCL_WGRAD_ROWS, the rows of one split of linear_wgrad / relu_bwd
+
+
+def linear_wgrad_splits(M):
+    """how many row splits linear_wgrad / relu_bwd cut M rows into: max(1, ceil(M / WGRAD_ROWS)), a function of M alone
+    (needs no GPU)"""
+    splits = C.c_int32(0)
+    N.check(N.lib().dcl_linear_wgrad_splits(int(M), C.byref(splits)), "linear_wgrad_splits")
+    return int(splits.value)
+
+
+def _rows2d(t, what):
+    assert t.dim() == 2 and t.dtype == torch.float32 and t.is_cuda, "%s: a 2-D float32 CUDA tensor" % what
+    assert t.stride(1) == 1 or t.shape[1] == 1, "%s: rows must be dense" % what
+    return t
+
+
+def linear_wgrad(a, b, out=None):
+    """The weight gradient of a per-point linear layer (csrc/linear_bwd.hip): dW (P,Q) = a^T b = sum_j a[j,:]^T b[j,:] with
+    a = dZ (M,P) and b = the layer's input (M,Q) -- the Conv1d weight's own (out, in) layout.  linear()'s conventions: 2-D
+    tensors whose rows may be strided, `out=dW0[:, 3:]` writes a column block of a wider gradient in place.  Own fp32 MFMA
+    kernel with a pinned order (rows ascending inside splits of WGRAD_ROWS rows, splits ascending): no atomics, the same bits
+    on every call and for every pitch and alignment.  No vendor library."""
+    N.need_cuda(a, b)
+    _rows2d(a, "a")
+    _rows2d(b, "b")
+    M, P = a.shape
+    assert b.shape[0] == M, "a and b must have the same rows"
+    Q = b.shape[1]
+    if out is None:
+        out = torch.empty((P, Q), dtype=torch.float32, device=a.device)
+    _rows2d(out, "out")
+    assert tuple(out.shape) == (P, Q)
+    partial = torch.empty(linear_wgrad_splits(M) * P * Q, dtype=torch.float32, device=a.device)
+    N.check(N.lib().dcl_linear_wgrad(N.ptr(a), C.c_int64(_pitch(a)), N.ptr(b), C.c_int64(_pitch(b)), int(M), int(P), int(Q),
+                                     N.ptr(partial), N.ptr(out), C.c_int64(_pitch(out)), N.stream()), "linear_wgrad")
+    return out
+
+
+def relu_bwd(h, g=None, roww=None, gpool=None, rows_per_crop=None, out=None):
+    """ReLU mask + bias gradient of a Linear + ReLU layer whose OUTPUT is h (M,P) (csrc/linear_bwd.hip) -> (dz (M,P), db (P,)).
+    relu_bwd(h, g): dz = where(h > 0, g, 0); `out=g` masks the arriving gradient in place.
+    relu_bwd(h, roww=w, gpool=G, rows_per_crop=n): the pooled last layer, whose output went into shared[crop] = sum_j w[j] h[j]:
+    dz[j] = where(h[j] > 0, w[j] * G[j // n], 0) with w (M,) and G (crops,P) the gradient of `shared`; `out=h` overwrites h.
+    db = dz.sum(0) in linear_wgrad's order (rows ascending inside a split, splits ascending): the same bits on every call."""
+    N.need_cuda(h, g, roww, gpool)
+    _rows2d(h, "h")
+    M, P = h.shape
+    if out is None:
+        out = torch.empty((M, P), dtype=torch.float32, device=h.device)
+    _rows2d(out, "out")
+    assert tuple(out.shape) == (M, P)
+    if g is not None:
+        assert roww is None and gpool is None, "either g or (roww, gpool, rows_per_crop)"
+        _rows2d(g, "g")
+        assert tuple(g.shape) == (M, P)
+        form = (N.ptr(g), C.c_int64(_pitch(g)), None, None, C.c_int64(0), 0)
+    else:
+        assert roww is not None and gpool is not None and rows_per_crop, "either g or (roww, gpool, rows_per_crop)"
+        _rows2d(gpool, "gpool")
+        rows_per_crop = int(rows_per_crop)
+        assert roww.dtype == torch.float32 and roww.is_contiguous() and roww.numel() == M
+        assert gpool.shape[1] == P and gpool.shape[0] * rows_per_crop >= M
+        form = (None, C.c_int64(0), N.ptr(roww), N.ptr(gpool), C.c_int64(_pitch(gpool)), rows_per_crop)
+    partial = torch.empty(linear_wgrad_splits(M) * P, dtype=torch.float32, device=h.device)
+    db = torch.empty(P, dtype=torch.float32, device=h.device)
+    N.check(N.lib().dcl_relu_bwd(N.ptr(h), C.c_int64(_pitch(h)), *form, int(M), int(P), N.ptr(out), C.c_int64(_pitch(out)),
+                                 N.ptr(partial), N.ptr(db), N.stream()), "relu_bwd")
+    return out, db
+
+
+def linear_pool_dma(x, Wt, bias, roww, relu=True, part=None, rows_per_crop=None, w_stride=0):
+    """linear_pool on the fp32-MFMA core whatever the launch size and whether or not the weight has been prepared: what a
+    training forward calls, whose weights change every step (no bf16 pieces to keep in step)."""
+    N.need_cuda(x, Wt, roww)
+    M, K = x.shape
+    return _linear_pool(N.lib().dcl_linear_pool_fwd, "linear_pool_fwd", x, (N.ptr(Wt), C.c_int64(_pitch(Wt))), K, Wt.shape[1],
+                        bias, roww, relu, part, rows_per_crop, w_stride)

@@ -622,6 +622,38 @@ int dcl_three_interpolate_grad_sp_ordered(int c, int n, int m, const float *grad
 int dcl_voxelize_bp(const float *d_out, const int32_t *rules, float *d_feats_zeroed, int n_rows, int max_active, int c,
                     int average, dclStream_t stream);
 
+/* ---- a per-point Linear + ReLU stack's training side (the stage-2 refiner's MLP_share; csrc/linear_bwd.hip).  The input
+ * gradient of such a layer is dcl_linear_dma_fwd with the registered (out, in) weight as its (K x N) matrix; these are the rest.
+ *
+ * Weight gradient: dW[p][q] = sum_{j < M} a[j][p] * b[j][q].  a = dZ (M x P, pitch lda >= P), b = the layer input (M x Q,
+ * pitch ldb >= Q), dW (P x Q, pitch lddw >= Q: the Conv1d weight's own (out, in) layout; a column block of a wider gradient
+ * is written in place and nothing beside it is touched).  fp32 MFMA (v_mfma_f32_32x32x2_f32), exact products.
+ * PINNED ORDER: the M rows are cut into splits of DCL_WGRAD_ROWS rows, splits = dcl_linear_wgrad_splits(M) =
+ * max(1, ceil(M / DCL_WGRAD_ROWS)) -- a function of M alone, never of P, Q, the device or its CU count.  Inside a split an
+ * output element is ONE accumulator, started at +0 and fed by the split's rows in ascending order (the waves of a workgroup
+ * tile (P, Q), never the rows); a second kernel adds the splits' results in ascending split order, one rounded add each.  No
+ * float atomics and no workgroup waits on another: the same values give the same bits on every call, whatever the pitches and
+ * the alignment.  Against exact arithmetic an element is therefore off by at most (DCL_WGRAD_ROWS + splits + 2) * 2^-24 *
+ * sum_j |a_jp| |b_jq|.  partial: caller scratch of splits * P * Q floats.  Any P, Q >= 1, any M >= 0 (M == 0 zero-fills dW),
+ * any pitches, any 4-byte aligned bases (16-byte aligned bases with pitches that are multiples of 4 floats load faster).
+ * DCL_EINVAL before any GPU work for a NULL or misaligned pointer, a negative size, P or Q < 1, or a pitch below the width. */
+#define DCL_WGRAD_ROWS 512
+int dcl_linear_wgrad_splits(int M, int32_t *splits_host);
+int dcl_linear_wgrad(const float *a, int64_t lda, const float *b, int64_t ldb, int M, int P, int Q, float *partial,
+                     float *dW, int64_t lddw, dclStream_t stream);
+/* ReLU mask + bias gradient of such a layer: h (M x P) is the layer's OUTPUT (after the ReLU),
+ *   g != NULL:  dz[j][p] = h[j][p] > 0 ? g[j][p] : 0                       (g (M x P): the gradient that arrives; dz may be g),
+ *   g == NULL:  dz[j][p] = h[j][p] > 0 ? roww[j] * gpool[j / rows_per_crop][p] : 0   (the pooled last layer: its output went
+ *               into out[crop] = sum_j roww[j] h[j]; roww (M), gpool (crops x P, pitch ldgp) = the pooled gradient; the product
+ *               is one rounded multiply; dz may be h),
+ * and db[p] = sum_j dz[j][p] in the order of dcl_linear_wgrad: rows ascending inside a split of DCL_WGRAD_ROWS rows from +0,
+ * then the splits ascending (off by at most (DCL_WGRAD_ROWS + splits) * 2^-24 * sum_j |dz_jp|); bit-identical call after call
+ * and in place or not.  h == 0 and NaN give 0.  partial: scratch of dcl_linear_wgrad_splits(M) * P floats; db (P).  Lanes run
+ * over columns.  M == 0 zero-fills db.  DCL_EINVAL as above (the unused form's arguments are ignored). */
+int dcl_relu_bwd(const float *h, int64_t ldh, const float *g, int64_t ldg, const float *roww, const float *gpool,
+                 int64_t ldgp, int rows_per_crop, int M, int P, float *dz, int64_t lddz, float *partial, float *db,
+                 dclStream_t stream);
+
 /* ------------------------------------------------------------ crop builder ---
  * The per-object crop construction of the data loaders (YCBV/dataloader_test_YCBV.py:124-183), on the device, in the
  * reference's pixel order and float32/float64 arithmetic (results bit-identical to the numpy/torch code).
