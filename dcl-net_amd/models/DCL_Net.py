@@ -85,7 +85,7 @@ def _fuser():
 class Network(nn.Module):
     def __init__(self, cfg, mode="train", fused=True, graph_max_batch=8, async_inputs=False, graph_max_points=98304,
                  single_stream=False, pipeline_chunks=1, capture_graph=True, pair_features=None,
-                 train_attention="materialised", train_rotation="host"):
+                 train_attention="materialised", train_rotation="host", train_conv_wgrad="rows"):
         """graph_max_batch > 0 (default 8): eval-mode calls with at most that many crops go through forward_graphed (one
         whole-forward hipGraph per batch size, captured on first use) -- the one-image-at-a-time eval loops of the
         reference (tools/test_LM.py:104-112: one object per call) are launch-bound otherwise: 0.53 instead of 1.1 ms
@@ -116,8 +116,13 @@ class Network(nn.Module):
         torch ops around a batched SVD on the host, two blocking copies per step; "device" = autograd.Ortho9dFn, the eval
         kernel forward and csrc/rotation_grad.hip backward, no host synchronisation, and a gradient that stays accurate for
         near-orthonormal axes.  Calls that need no gradient do not read it.
+        train_conv_wgrad: the form of the sparse convolutions' weight gradient on the same path, set on every convolution of both
+        backbones (spconv.SparseConvolution.wgrad).  "rows" (default) = csrc/backward.hip, which walks every output row of every
+        kernel offset; "pairs" = csrc/conv_wgrad_pairs.hip, an ordered list of the pairs that exist and a staged fp32-MFMA kernel
+        over it.  The forward pass and the input gradients are the same either way.
         These are constructor arguments on purpose: nothing on the call path reads the environment."""
         super().__init__()
+        self.train_conv_wgrad = ops.check_conv_wgrad(train_conv_wgrad, "train_conv_wgrad")
         self.train_rotation = check_train_rotation(train_rotation)
         if train_attention not in ("materialised", "fused"):
             raise ValueError('train_attention must be "materialised" or "fused", got %r' % (train_attention,))
@@ -139,6 +144,10 @@ class Network(nn.Module):
         self.backbone_stride_layers = [1, 3, 5]
         self.backbone_inp = Backbone_SPCONV(self.backbone_dims, self.backbone_stride_layers, cfg.backbone)
         self.backbone_tmp = Backbone_SPCONV(self.backbone_dims, self.backbone_stride_layers, cfg.backbone)
+        for bb in (self.backbone_inp, self.backbone_tmp):
+            for m in bb.modules():
+                if isinstance(m, spconv.SparseConvolution):
+                    m.wgrad = self.train_conv_wgrad
         self.stage1_get_point_feats = Ops_GetPointFeat_spconv(SCALE_LISTS, self.unit_voxel_extent, VOXEL_NUM_LIMIT)
         block = partial(BasicBlock_3DCONV, size=1, bias=False, stride=1, padding=0, norm=True, act="relu", drop=0.0)
         for grp in ("1", "2"):                       # registration order = the reference's (state_dict order)

@@ -1907,22 +1907,125 @@ def rulebook_transpose(nbr, n_out, cap_in):
     return inv
 
 
-def sparse_conv_backward(feat, W, dout, nbr, n_out, subm, need_dx=True):
-    """indice_conv_backward_fp32 (spconv_ops.h:351-438): -> (d_feat (V_in,Cin) or None, dW (kvol,Cin,Cout))."""
+CONV_PAIRS_SPLIT = 512         # include/dclnet_hip.h: DCL_CONV_PAIRS_SPLIT, the pairs of one split of sparse_conv_wgrad_pairs
+CONV_PAIRS_HEAD = 96           # DCL_CONV_PAIRS_HEAD
+CONV_WGRAD_FORMS = ("rows", "pairs")
+
+
+def check_conv_wgrad(value, what="wgrad"):
+    if value not in CONV_WGRAD_FORMS:
+        raise ValueError('%s must be "rows" or "pairs", got %r' % (what, value))
+    return value
+
+
+class ConvPairs(object):
+    """the ordered pair list of a rulebook (conv_pairs): head (CONV_PAIRS_HEAD,) i32 -- count at [k], start at [32 + k], nsplit
+    at [60], overflow at [61], an offset's first split at [64 + k]; pair_in / pair_out (max_pairs,) i32; split_tab (max_splits, 4)
+    i32 rows (offset, first pair, length, 0).  All on the device; nothing here was read back."""
+    __slots__ = ("head", "pair_in", "pair_out", "split_tab", "kvol", "n_out", "n_in", "max_pairs", "max_splits")
+
+    def counts(self):
+        """(count (kvol), start (kvol + 1), nsplit, overflow) -- a host read-back, for tests and tools"""
+        h = self.head.cpu()
+        return h[:self.kvol], h[32:33 + self.kvol], int(h[60]), int(h[61])
+
+
+def conv_pairs(nbr, n_out, n_in, check=False):
+    """The rulebook's pairs in a pinned order (csrc/conv_wgrad_pairs.hip): (k, o) is a pair iff o < n_out and 0 <= nbr[k][o] <
+    n_in; offset k's pairs lie at start[k] .. start[k] + count[k] in ascending o, cut into splits of CONV_PAIRS_SPLIT pairs.
+    Sized for kvol * min(n_in, n_out) pairs, which holds them all whenever an input row meets an offset at most once (the
+    precondition of rulebook_transpose); pairs beyond it are counted, not stored, and check=True reads that count back and
+    raises.  No read-back otherwise.  -> ConvPairs"""
+    N.need_cuda(nbr)
+    assert nbr.dtype == torch.int32 and nbr.dim() == 2 and nbr.is_contiguous()
+    kvol, cap = nbr.shape
+    n_out, n_in = int(n_out), int(n_in)
+    assert 0 <= n_out <= cap and n_in >= 0
+    dev = nbr.device
+    P = ConvPairs()
+    P.kvol, P.n_out, P.n_in = kvol, n_out, n_in
+    P.max_pairs = kvol * min(n_in, n_out)
+    ms, wb = C.c_int32(0), C.c_int64(0)
+    N.check(N.lib().dcl_conv_pairs_max_splits(P.max_pairs, kvol, C.byref(ms)), "conv_pairs_max_splits")
+    N.check(N.lib().dcl_conv_pairs_ws_bytes(kvol, n_out, C.byref(wb)), "conv_pairs_ws_bytes")
+    P.max_splits = int(ms.value)
+    P.head = torch.empty(CONV_PAIRS_HEAD, dtype=torch.int32, device=dev)
+    lists = torch.empty((2, max(P.max_pairs, 1)), dtype=torch.int32, device=dev)
+    P.pair_in, P.pair_out = lists[0], lists[1]
+    P.split_tab = torch.empty((P.max_splits, 4), dtype=torch.int32, device=dev)
+    ws = torch.empty(max(int(wb.value) // 4, 1), dtype=torch.int32, device=dev)
+    N.check(N.lib().dcl_conv_pairs(N.ptr(nbr), cap, kvol, n_out, n_in, P.max_pairs, N.ptr(P.head), N.ptr(P.pair_in),
+                                   N.ptr(P.pair_out), N.ptr(P.split_tab), N.ptr(ws), C.c_int64(ws.numel() * 4), N.stream()),
+            "conv_pairs")
+    if check:
+        over = int(P.head[61])
+        if over:
+            raise RuntimeError("conv_pairs: %d pairs beyond the %d that kvol * min(n_in, n_out) holds: an input row meets an "
+                               "offset more than once" % (over, P.max_pairs))
+    return P
+
+
+def conv_pairs_host(nbr, n_out, n_in, max_pairs=None):
+    """the host twin of conv_pairs (dcl_conv_pairs_host, plain C++, no GPU): nbr (kvol, cap) int32 numpy ->
+    dict(head, pair_in, pair_out, split_tab, max_pairs, max_splits) of numpy arrays; entries past the stored pairs and past
+    nsplit are left -1"""
+    import numpy as np
+    nbr = np.ascontiguousarray(nbr, np.int32)
+    kvol, cap = nbr.shape
+    if max_pairs is None:
+        max_pairs = kvol * min(int(n_in), int(n_out))
+    ms = C.c_int32(0)
+    N.check(N.lib().dcl_conv_pairs_max_splits(int(max_pairs), kvol, C.byref(ms)), "conv_pairs_max_splits")
+    head = np.full(CONV_PAIRS_HEAD, -1, np.int32)
+    pin, pout = np.full(max(max_pairs, 1), -1, np.int32), np.full(max(max_pairs, 1), -1, np.int32)
+    tab = np.full((ms.value, 4), -1, np.int32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    N.check(N.lib().dcl_conv_pairs_host(vp(nbr), cap, kvol, int(n_out), int(n_in), int(max_pairs), vp(head), vp(pin), vp(pout),
+                                        vp(tab)), "conv_pairs_host")
+    return dict(head=head, pair_in=pin, pair_out=pout, split_tab=tab, max_pairs=int(max_pairs), max_splits=int(ms.value))
+
+
+def sparse_conv_wgrad_pairs(feat, dout, pairs, cin, cout):
+    """dW (kvol, cin, cout) = sum over the listed pairs of feat[pair_in]^T dout[pair_out] on the fp32 MFMA, in the pinned order
+    of csrc/conv_wgrad_pairs.hip: inside a split one accumulator per element fed by the pairs ascending, then an offset's splits
+    ascending.  A function of the list and the rows it names alone; the same bits on every call.  Every element is written."""
+    N.need_cuda(feat, dout)
+    cin, cout = int(cin), int(cout)
+    feat, dout = N.f32c(feat), N.f32c(dout)
+    assert tuple(feat.shape) == (feat.shape[0], cin) and feat.shape[0] >= pairs.n_in
+    assert tuple(dout.shape) == (dout.shape[0], cout) and dout.shape[0] >= pairs.n_out
+    dev = feat.device
+    dW = torch.empty((pairs.kvol, cin, cout), dtype=torch.float32, device=dev)
+    partial = torch.empty(pairs.max_splits * cin * cout, dtype=torch.float32, device=dev)
+    N.check(N.lib().dcl_sparse_conv_wgrad_pairs(N.ptr(feat), pairs.n_in, N.ptr(dout), pairs.n_out, cin, cout, pairs.kvol,
+                                                N.ptr(pairs.head), N.ptr(pairs.pair_in), N.ptr(pairs.pair_out),
+                                                N.ptr(pairs.split_tab), pairs.max_splits, N.ptr(partial), N.ptr(dW),
+                                                N.stream()), "sparse_conv_wgrad_pairs")
+    return dW
+
+
+def sparse_conv_backward(feat, W, dout, nbr, n_out, subm, need_dx=True, wgrad="rows"):
+    """indice_conv_backward_fp32 (spconv_ops.h:351-438): -> (d_feat (V_in,Cin) or None, dW (kvol,Cin,Cout)).  wgrad: the form
+    of the weight gradient -- "rows" (default; csrc/backward.hip walks every output row of every offset) or "pairs" (conv_pairs +
+    sparse_conv_wgrad_pairs: only the pairs that exist, in a pinned order).  The input gradient is the same either way."""
+    check_conv_wgrad(wgrad)
     N.need_cuda(feat, W, dout, nbr)
     kvol, cap = nbr.shape
     cin, cout = W.shape[-2], W.shape[-1]
     n_in = feat.shape[0]
     dev = feat.device
     dout = dout.contiguous()
-    dW = torch.zeros((kvol, cin, cout), dtype=torch.float32, device=dev)
     dx = None
-    if n_out > 0 and n_in > 0:                                     # (no input rows: no pair, dW = 0 -- and no feat pointer)
-        splits = C.c_int32(0)
-        N.check(N.lib().dcl_sparse_conv_wgrad_splits(int(n_out), C.byref(splits)), "wgrad_splits")
-        partial = torch.empty(splits.value * kvol * cin * cout, dtype=torch.float32, device=dev)
-        N.check(N.lib().dcl_sparse_conv_wgrad(N.ptr(feat), N.ptr(nbr), cap, int(n_out), N.ptr(dout), cin, cout, kvol,
-                                              N.ptr(partial), N.ptr(dW), N.stream()), "sparse_conv_wgrad")
+    if wgrad == "pairs":                                           # (the list lives for this call only)
+        dW = sparse_conv_wgrad_pairs(feat, dout, conv_pairs(nbr, n_out, n_in), cin, cout)
+    else:
+        dW = torch.zeros((kvol, cin, cout), dtype=torch.float32, device=dev)
+        if n_out > 0 and n_in > 0:                                 # (no input rows: no pair, dW = 0 -- and no feat pointer)
+            splits = C.c_int32(0)
+            N.check(N.lib().dcl_sparse_conv_wgrad_splits(int(n_out), C.byref(splits)), "wgrad_splits")
+            partial = torch.empty(splits.value * kvol * cin * cout, dtype=torch.float32, device=dev)
+            N.check(N.lib().dcl_sparse_conv_wgrad(N.ptr(feat), N.ptr(nbr), cap, int(n_out), N.ptr(dout), cin, cout, kvol,
+                                                  N.ptr(partial), N.ptr(dW), N.stream()), "sparse_conv_wgrad")
     if need_dx:
         if n_in == 0 or n_out == 0:
             dx = torch.zeros((n_in, cin), dtype=torch.float32, device=dev)

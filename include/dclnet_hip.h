@@ -598,6 +598,46 @@ int dcl_rulebook_transpose(const int32_t *nbr, int cap_out, const int32_t *n_out
 int dcl_sparse_conv_wgrad_splits(int n_out, int32_t *splits_host);
 int dcl_sparse_conv_wgrad(const float *feat, const int32_t *nbr, int cap, int n_out, const float *dout, int cin, int cout,
                           int kvol, float *partial, float *dW, dclStream_t stream);
+/* ---- the same filter gradient over the rulebook's PAIRS, in a pinned order (csrc/conv_wgrad_pairs.hip).
+ *
+ * Ordered pair list of a gather table nbr (kvol x cap, i32): (k, o) is a pair iff o < n_out and 0 <= nbr[k][o] < n_in.  Any
+ * other entry takes no part and is never an address; rows o >= n_out are never read.  head (DCL_CONV_PAIRS_HEAD i32):
+ *   head[k]                        count[k], the pairs of offset k                                   (k < kvol)
+ *   head[32 + k]                   start[k], the exclusive prefix of count                           (k <= kvol)
+ *   head[60]                       nsplit, the rows of the split table in use
+ *   head[61]                       overflow = max(0, start[kvol] - max_pairs), the pairs that were not stored
+ *   head[64 + k]                   the first split of offset k (head[64 + kvol] = nsplit)            (k <= kvol)
+ * pair_in / pair_out [start[k] + p] (max_pairs i32 each) = the p-th pair of offset k in ASCENDING o: its input row nbr[k][o]
+ * and its output row o -- a stable compaction from prefix sums; no atomic takes part and no workgroup waits on another.  A
+ * pair whose position is max_pairs or more is not stored; count and start stay the true figures and overflow says how many
+ * pairs are missing (a caller that sized max_pairs as kvol * min(n_in, n_out) sees 0 whenever an input row meets an offset at
+ * most once -- the precondition of dcl_rulebook_transpose).  split_tab (dcl_conv_pairs_max_splits(max_pairs, kvol) rows of 4
+ * i32: offset, first pair, length, 0): the STORED pairs of offset k cut into splits of DCL_CONV_PAIRS_SPLIT consecutive pairs
+ * (the last one shorter), offsets ascending; nsplit <= max_pairs / DCL_CONV_PAIRS_SPLIT + kvol.  ws: scratch of at least
+ * dcl_conv_pairs_ws_bytes bytes.  Three launches, no read-back: capturable.  The two queries and dcl_conv_pairs_host (the same
+ * contract in plain C++ on host pointers) make no GPU call.  DCL_EINVAL before any GPU work for kvol outside 1..27, a
+ * negative size, cap < n_out, max_pairs >= 2^30, a NULL buffer or a short workspace. */
+#define DCL_CONV_PAIRS_SPLIT 512
+#define DCL_CONV_PAIRS_HEAD 96
+int dcl_conv_pairs_ws_bytes(int kvol, int n_out, int64_t *bytes_host);
+int dcl_conv_pairs_max_splits(int max_pairs, int kvol, int32_t *splits_host);
+int dcl_conv_pairs(const int32_t *nbr, int cap, int kvol, int n_out, int n_in, int max_pairs, int32_t *head,
+                   int32_t *pair_in, int32_t *pair_out, int32_t *split_tab, void *ws, int64_t ws_bytes, dclStream_t stream);
+int dcl_conv_pairs_host(const int32_t *nbr, int cap, int kvol, int n_out, int n_in, int max_pairs, int32_t *head,
+                        int32_t *pair_in, int32_t *pair_out, int32_t *split_tab);
+/* dW[k][ci][co] = sum over the pairs of offset k of feat[pair_in][ci] * dout[pair_out][co] (feat n_in x cin, dout n_out x
+ * cout, dW kvol x cin x cout, all dense row-major) on v_mfma_f32_32x32x2_f32: exact products, one rounding per step.
+ * PINNED ORDER: an element of a split's result is ONE accumulator, started at +0 and fed by the split's pairs ascending (the
+ * waves of a workgroup tile (cin, cout) or take different splits, never the pairs of one split); a second launch adds each
+ * offset's splits ascending from the first one's value, and writes +0 for an offset without pairs: every element of dW is
+ * written.  The result is a function of the ordered pair list and the rows it names alone -- not of cap, of rows that hold no
+ * pair, or of the launch.  No float atomics, no waiting on counters.  Against exact arithmetic an element is off by at most
+ * (DCL_CONV_PAIRS_SPLIT + splits_k + 2) * 2^-24 * sum |x| |g|.  Any cin, cout >= 1 (zero-filled lanes; 16-byte loads are only
+ * the fast path of aligned rows).  Listed rows outside [0, n_in) / [0, n_out) read as zero rows and are never addresses.
+ * max_splits: the rows of split_tab; partial: scratch of max_splits * cin * cout floats.  DCL_EINVAL as above.          */
+int dcl_sparse_conv_wgrad_pairs(const float *feat, int n_in, const float *dout, int n_out, int cin, int cout, int kvol,
+                                const int32_t *head, const int32_t *pair_in, const int32_t *pair_out,
+                                const int32_t *split_tab, int max_splits, float *partial, float *dW, dclStream_t stream);
 /* indice_avgpool backward (avgpool.cu:178-206): din[i] = sum_k asc dout[inv[k][i]] / (float)rf[inv[k][i]].  C % 4 == 0. */
 int dcl_sparse_avgpool_bwd(const float *dout, const int32_t *inv, int cap_in, int n_in, const int32_t *rf, int c, int kvol,
                            float *din, dclStream_t stream);
