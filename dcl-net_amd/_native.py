@@ -40,7 +40,11 @@ def _open(path):
     L.dcl_linear_wgrad_splits.argtypes = [i, C.POINTER(C.c_int32)]
     L.dcl_linear_wgrad.argtypes = [vp, i64, vp, i64, i, i, i, vp, vp, i64, vp]
     L.dcl_relu_bwd.argtypes = [vp, i64, vp, i64, vp, vp, i64, i, i, i, vp, i64, vp, vp, vp]
-    for fn in (L.dcl_linear_wgrad_splits, L.dcl_linear_wgrad, L.dcl_relu_bwd):
+    # csrc/conv_dgrad.hip
+    L.dcl_sparse_conv_dgrad.argtypes = [vp, i, vp, i, i, vp, i, i, i, vp, vp]
+    L.dcl_sparse_conv_dgrad_host.argtypes = [vp, i, vp, i, i, vp, i, i, i, vp]
+    for fn in (L.dcl_linear_wgrad_splits, L.dcl_linear_wgrad, L.dcl_relu_bwd, L.dcl_sparse_conv_dgrad,
+               L.dcl_sparse_conv_dgrad_host):
         fn.restype = i
     return L
 

@@ -16,20 +16,22 @@ from . import ops as _ops
 
 class SparseConvFn(Function):
     """SparseConvFunction / SubMConvFunction (functional.py:20-88).  wgrad: the form of the weight gradient, "rows" (default) or
-    "pairs" (ops.sparse_conv_backward); the pair list is built in the backward call and dies with it."""
+    "pairs" (ops.sparse_conv_backward); the pair list is built in the backward call and dies with it.  dgrad: the form of the
+    input gradient, "conv" (default) or "direct" (ops.sparse_conv_dgrad)."""
 
     @staticmethod
-    def forward(ctx, features, W, nbr, n_out, subm, wgrad="rows"):
+    def forward(ctx, features, W, nbr, n_out, subm, wgrad="rows", dgrad="conv"):
         ctx.save_for_backward(features, W, nbr)
         ctx.n_out, ctx.subm, ctx.wgrad = int(n_out), bool(subm), _ops.check_conv_wgrad(wgrad)
+        ctx.dgrad = _ops.check_conv_dgrad(dgrad)
         return _ops.sparse_conv(features, nbr, n_out, W, subm)
 
     @staticmethod
     def backward(ctx, grad_output):
         features, W, nbr = ctx.saved_tensors
         dx, dW = _ops.sparse_conv_backward(features, W, grad_output, nbr, ctx.n_out, ctx.subm,
-                                           need_dx=ctx.needs_input_grad[0], wgrad=ctx.wgrad)
-        return dx, dW.view_as(W), None, None, None, None
+                                           need_dx=ctx.needs_input_grad[0], wgrad=ctx.wgrad, dgrad=ctx.dgrad)
+        return dx, dW.view_as(W), None, None, None, None, None
 
 
 class SparseAvgPoolFn(Function):

@@ -85,7 +85,8 @@ def _fuser():
 class Network(nn.Module):
     def __init__(self, cfg, mode="train", fused=True, graph_max_batch=8, async_inputs=False, graph_max_points=98304,
                  single_stream=False, pipeline_chunks=1, capture_graph=True, pair_features=None,
-                 train_attention="materialised", train_rotation="host", train_conv_wgrad="rows"):
+                 train_attention="materialised", train_rotation="host", train_conv_wgrad="rows",
+                 train_conv_dgrad="conv"):
         """graph_max_batch > 0 (default 8): eval-mode calls with at most that many crops go through forward_graphed (one
         whole-forward hipGraph per batch size, captured on first use) -- the one-image-at-a-time eval loops of the
         reference (tools/test_LM.py:104-112: one object per call) are launch-bound otherwise: 0.53 instead of 1.1 ms
@@ -120,8 +121,13 @@ class Network(nn.Module):
         backbones (spconv.SparseConvolution.wgrad).  "rows" (default) = csrc/backward.hip, which walks every output row of every
         kernel offset; "pairs" = csrc/conv_wgrad_pairs.hip, an ordered list of the pairs that exist and a staged fp32-MFMA kernel
         over it.  The forward pass and the input gradients are the same either way.
+        train_conv_dgrad: the form of their input gradient (spconv.SparseConvolution.dgrad).  "conv" (default) = the forward
+        dispatcher on the transposed rulebook and a transposed copy of W; "direct" = csrc/conv_dgrad.hip, which reads W as
+        registered, on the convolutions whose (cin, cout) is in ops.CONV_DGRAD_DIRECT_WIDTHS -- the widths on which it was measured
+        faster (profiles/conv_dgrad.txt) -- and "conv" on the others: a rule by widths alone.  Forward and dW are the same either way.
         These are constructor arguments on purpose: nothing on the call path reads the environment."""
         super().__init__()
+        self.train_conv_dgrad = ops.check_conv_dgrad(train_conv_dgrad, "train_conv_dgrad")
         self.train_conv_wgrad = ops.check_conv_wgrad(train_conv_wgrad, "train_conv_wgrad")
         self.train_rotation = check_train_rotation(train_rotation)
         if train_attention not in ("materialised", "fused"):
@@ -148,6 +154,7 @@ class Network(nn.Module):
             for m in bb.modules():
                 if isinstance(m, spconv.SparseConvolution):
                     m.wgrad = self.train_conv_wgrad
+                    m.dgrad = ops.conv_dgrad_form(m.in_channels, m.out_channels, self.train_conv_dgrad)
         self.stage1_get_point_feats = Ops_GetPointFeat_spconv(SCALE_LISTS, self.unit_voxel_extent, VOXEL_NUM_LIMIT)
         block = partial(BasicBlock_3DCONV, size=1, bias=False, stride=1, padding=0, norm=True, act="relu", drop=0.0)
         for grp in ("1", "2"):                       # registration order = the reference's (state_dict order)

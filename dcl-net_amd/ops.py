@@ -2004,11 +2004,70 @@ def sparse_conv_wgrad_pairs(feat, dout, pairs, cin, cout):
     return dW
 
 
-def sparse_conv_backward(feat, W, dout, nbr, n_out, subm, need_dx=True, wgrad="rows"):
+CONV_DGRAD_FORMS = ("conv", "direct")
+# the (cin, cout) of the backbone layers on which tools/bench_conv_dgrad.py measured "direct" faster than "conv" with disjoint
+# block ranges on the layers of BOTH backbones (profiles/conv_dgrad.txt); Network(train_conv_dgrad="direct") goes by this table
+CONV_DGRAD_DIRECT_WIDTHS = frozenset(((16, 32), (128, 256)))
+
+
+def check_conv_dgrad(value, what="dgrad"):
+    if value not in CONV_DGRAD_FORMS:
+        raise ValueError('%s must be "conv" or "direct", got %r' % (what, value))
+    return value
+
+
+def conv_dgrad_form(cin, cout, train_conv_dgrad="direct"):
+    """the dgrad of a convolution of these widths under Network(train_conv_dgrad=): by widths alone, never by the data"""
+    direct = check_conv_dgrad(train_conv_dgrad, "train_conv_dgrad") == "direct"
+    return "direct" if direct and (int(cin), int(cout)) in CONV_DGRAD_DIRECT_WIDTHS else "conv"
+
+
+def sparse_conv_dgrad(dout, inv, n_in, W):
+    """dX (n_in, cin) = sum_k sum_co dout[inv[k][i]][co] W[k][ci][co] on csrc/conv_dgrad.hip: inv (kvol, cap_in) from
+    rulebook_transpose, W (kvol, cin, cout) as registered -- no transposed copy.  An entry of inv is a neighbour iff it names one
+    of dout's rows.  Pinned order: one accumulator per element from +0, offsets ascending, channels ascending inside an offset;
+    the same bits on every call, whatever n_in, cap_in or the other rows.  Every element is written."""
+    N.need_cuda(dout, inv, W)
+    assert inv.dtype == torch.int32 and inv.dim() == 2 and inv.is_contiguous()
+    kvol, cap_in = inv.shape
+    cin, cout = int(W.shape[-2]), int(W.shape[-1])
+    n_in = int(n_in)
+    dout = N.f32c(dout)
+    W = N.f32c(W.reshape(kvol, cin, cout))
+    assert dout.dim() == 2 and dout.shape[1] == cout and 0 <= n_in <= cap_in
+    dx = torch.empty((n_in, cin), dtype=torch.float32, device=dout.device)
+    N.check(N.lib().dcl_sparse_conv_dgrad(N.ptr(dout), int(dout.shape[0]), N.ptr(inv), cap_in, n_in, N.ptr(W), cin, cout, kvol,
+                                          N.ptr(dx), N.stream()), "sparse_conv_dgrad")
+    return dx
+
+
+def sparse_conv_dgrad_host(dout, inv, n_in, W, n_out=None):
+    """the host twin of sparse_conv_dgrad (dcl_sparse_conv_dgrad_host, plain C++, no GPU) on numpy arrays: the same chain,
+    literally.  n_out: the rows of dout that count (default: all of them)."""
+    import numpy as np
+    inv = np.ascontiguousarray(inv, np.int32)
+    kvol, cap_in = inv.shape
+    cin, cout = int(W.shape[-2]), int(W.shape[-1])
+    dout = np.ascontiguousarray(dout, np.float32)
+    W = np.ascontiguousarray(np.asarray(W, np.float32).reshape(kvol, cin, cout))
+    n_out = dout.shape[0] if n_out is None else int(n_out)
+    assert dout.ndim == 2 and dout.shape[1] == cout and n_out <= dout.shape[0]
+    dx = np.full((int(n_in), cin), np.nan, np.float32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    N.check(N.lib().dcl_sparse_conv_dgrad_host(vp(dout), n_out, vp(inv), cap_in, int(n_in), vp(W), cin, cout, kvol, vp(dx)),
+            "sparse_conv_dgrad_host")
+    return dx
+
+
+def sparse_conv_backward(feat, W, dout, nbr, n_out, subm, need_dx=True, wgrad="rows", dgrad="conv"):
     """indice_conv_backward_fp32 (spconv_ops.h:351-438): -> (d_feat (V_in,Cin) or None, dW (kvol,Cin,Cout)).  wgrad: the form
     of the weight gradient -- "rows" (default; csrc/backward.hip walks every output row of every offset) or "pairs" (conv_pairs +
-    sparse_conv_wgrad_pairs: only the pairs that exist, in a pinned order).  The input gradient is the same either way."""
+    sparse_conv_wgrad_pairs: only the pairs that exist, in a pinned order).  dgrad: the form of the input gradient -- "conv"
+    (default: the forward dispatcher on the transposed rulebook and a transposed copy of W) or "direct" (sparse_conv_dgrad on
+    the transposed rulebook and W as it is; always the new kernel, whatever the widths).  Neither switch touches the other's
+    result."""
     check_conv_wgrad(wgrad)
+    check_conv_dgrad(dgrad)
     N.need_cuda(feat, W, dout, nbr)
     kvol, cap = nbr.shape
     cin, cout = W.shape[-2], W.shape[-1]
@@ -2029,6 +2088,8 @@ def sparse_conv_backward(feat, W, dout, nbr, n_out, subm, need_dx=True, wgrad="r
     if need_dx:
         if n_in == 0 or n_out == 0:
             dx = torch.zeros((n_in, cin), dtype=torch.float32, device=dev)
+        elif dgrad == "direct":
+            dx = sparse_conv_dgrad(dout[:n_out], rulebook_transpose(nbr, n_out, n_in), n_in, W)
         else:
             inv = rulebook_transpose(nbr, n_out, n_in)
             Wt = W.reshape(kvol, cin, cout).transpose(1, 2).contiguous()          # per-offset W^T: (kvol, Cout, Cin)

@@ -33,6 +33,7 @@ class SparseConvolution(SparseModule):
         self.subm = subm
         self.indice_key = indice_key
         self.wgrad = "rows"            # the weight gradient's form in training: "rows" or "pairs" (ops.sparse_conv_backward)
+        self.dgrad = "conv"            # the input gradient's form in training: "conv" or "direct" (ops.sparse_conv_backward)
         self.weight = Parameter(torch.Tensor(*self.kernel_size, in_channels, out_channels))
         if bias:
             self.bias = Parameter(torch.Tensor(out_channels))
@@ -73,7 +74,7 @@ class SparseConvolution(SparseModule):
             input.indice_dict[self.indice_key] = (out_set, indices, nbr, None, input.spatial_shape)
         n_out = indices.shape[0] if self.subm else out_set.n
         W = self.weight.view(-1, self.in_channels, self.out_channels)
-        out_features = SparseConvFn.apply(features.contiguous(), W.contiguous(), nbr, n_out, self.subm, self.wgrad)
+        out_features = SparseConvFn.apply(features.contiguous(), W.contiguous(), nbr, n_out, self.subm, self.wgrad, self.dgrad)
         if self.bias is not None:
             out_features += self.bias
         out_tensor = SparseConvTensor(out_features, indices if self.subm else out_set.indices, out_shape,

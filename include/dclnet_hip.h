@@ -590,7 +590,8 @@ int dcl_ortho9d_bwd_host(int b, const float *o9, const float *grad_R, float *gra
 
 /* ------------------------------------------------------------ training-side kernels (csrc/backward.hip) ---
  * Transposed rulebook: inv[k][i] = o for every nbr[k][o] = i >= 0, -1 elsewhere (inv: i32[kvol][cap_in]).  With it the
- * input gradient of indice_conv (spconv_ops.h:351-438) is dcl_sparse_conv_fwd(dOut, inv, W^T per offset).            */
+ * input gradient of indice_conv (spconv_ops.h:351-438) is either dcl_sparse_conv_fwd(dOut, inv, W^T per offset), the default
+ * route, or dcl_sparse_conv_dgrad(dOut, inv, W) below, which reads W as registered.                                   */
 int dcl_rulebook_transpose(const int32_t *nbr, int cap_out, const int32_t *n_out_dev, int n_out_host, int kvol,
                            int32_t *inv, int cap_in, dclStream_t stream);
 /* Filter gradient of indice_conv: dW[k] = sum_o feat[nbr[k][o]]^T dout[o] (spconv_ops.h:413-417).  partial: scratch of
@@ -638,6 +639,26 @@ int dcl_conv_pairs_host(const int32_t *nbr, int cap, int kvol, int n_out, int n_
 int dcl_sparse_conv_wgrad_pairs(const float *feat, int n_in, const float *dout, int n_out, int cin, int cout, int kvol,
                                 const int32_t *head, const int32_t *pair_in, const int32_t *pair_out,
                                 const int32_t *split_tab, int max_splits, float *partial, float *dW, dclStream_t stream);
+/* ---- the input gradient of indice_conv on a kernel of its own, in a pinned order (csrc/conv_dgrad.hip, conv_dgrad.h).
+ *
+ *   dx[i][ci] = sum_k sum_co dout[inv[k][i]][co] * W[k][ci][co]          i < n_in, ci < cin
+ *
+ * dout n_out x cout, dx n_in x cin, W kvol x cin x cout AS REGISTERED (no transposed copy), all dense row-major; inv kvol x
+ * cap_in from dcl_rulebook_transpose.  An entry is a neighbour iff 0 <= inv[k][i] < n_out; any other entry takes no part and
+ * is never an address, so rows of dout at or past n_out are never read.  fp32 MFMA (v_mfma_f32_32x32x2_f32): exact products,
+ * one rounding per step.  PINNED ORDER: an element of dx is ONE accumulator, started at +0; offsets k ascending, an offset
+ * that is no neighbour skipped, the channels co ascending inside an offset -- one fmaf chain, never split, which the host
+ * twin runs literally.  The element is a function of its row's neighbours, of the dout rows they name and of W alone: not of
+ * n_in, cap_in, other rows or the launch.  Every element of the n_in rows of dx is written, +0 for a row without neighbours;
+ * nothing at or past row n_in is.  Any cin, cout >= 1 and kvol <= 27 through one body (zero-filled lanes; 16-byte loads are
+ * only the fast path of aligned rows); W and the named rows of dout are taken to be finite.  No float atomics, no waiting on
+ * counters, no scratch; one launch, capturable.  dcl_sparse_conv_dgrad_host is the same routine in plain C++ on HOST pointers
+ * and makes no GPU call.  DCL_EINVAL before any GPU work for kvol outside 1..27, a negative size, cin or cout < 1, cap_in <
+ * n_in, a NULL or misaligned buffer that a non-empty side needs; n_in == 0 or n_out == 0 is not an error.               */
+int dcl_sparse_conv_dgrad(const float *dout, int n_out, const int32_t *inv, int cap_in, int n_in, const float *W, int cin,
+                          int cout, int kvol, float *dx, dclStream_t stream);
+int dcl_sparse_conv_dgrad_host(const float *dout, int n_out, const int32_t *inv, int cap_in, int n_in, const float *W, int cin,
+                               int cout, int kvol, float *dx);
 /* indice_avgpool backward (avgpool.cu:178-206): din[i] = sum_k asc dout[inv[k][i]] / (float)rf[inv[k][i]].  C % 4 == 0. */
 int dcl_sparse_avgpool_bwd(const float *dout, const int32_t *inv, int cap_in, int n_in, const int32_t *rf, int c, int kvol,
                            float *din, dclStream_t stream);

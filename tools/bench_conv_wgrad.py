@@ -65,9 +65,9 @@ def main():
 
     class Recorder(object):
         @staticmethod
-        def apply(features, W, nbr, n_out, subm, wgrad="rows"):
+        def apply(features, W, nbr, n_out, subm, *forms):
             calls.append((features.detach(), W.detach(), nbr, int(n_out), bool(subm)))
-            return real.apply(features, W, nbr, n_out, subm, wgrad)
+            return real.apply(features, W, nbr, n_out, subm, *forms)
 
     b, n = args.b, args.n
     net = dcl.DCL_Net.Network(dcl.synth.default_cfg(n, n), mode="train")
