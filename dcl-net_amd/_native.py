@@ -43,8 +43,15 @@ def _open(path):
     # csrc/conv_dgrad.hip
     L.dcl_sparse_conv_dgrad.argtypes = [vp, i, vp, i, i, vp, i, i, i, vp, vp]
     L.dcl_sparse_conv_dgrad_host.argtypes = [vp, i, vp, i, i, vp, i, i, i, vp]
+    # csrc/conf_pool_grad.hip: an int64 scratch size among the pointers
+    L.dcl_conf_pool_cm_fwd.argtypes = [i] * 4 + [vp] * 5
+    L.dcl_conf_pool_cm_fwd_host.argtypes = [i] * 4 + [vp] * 4
+    L.dcl_conf_pool_cm_bwd_ws_bytes.argtypes = [i] * 4 + [C.POINTER(C.c_int64)]
+    L.dcl_conf_pool_cm_bwd.argtypes = [i] * 4 + [vp] * 11 + [i64, vp]
+    L.dcl_conf_pool_cm_bwd_host.argtypes = [i] * 4 + [vp] * 10
     for fn in (L.dcl_linear_wgrad_splits, L.dcl_linear_wgrad, L.dcl_relu_bwd, L.dcl_sparse_conv_dgrad,
-               L.dcl_sparse_conv_dgrad_host):
+               L.dcl_sparse_conv_dgrad_host, L.dcl_conf_pool_cm_fwd, L.dcl_conf_pool_cm_fwd_host,
+               L.dcl_conf_pool_cm_bwd_ws_bytes, L.dcl_conf_pool_cm_bwd, L.dcl_conf_pool_cm_bwd_host):
         fn.restype = i
     return L
 

@@ -347,3 +347,43 @@ class RefinerShareFn(Function):
         _ops.linear_wgrad(dz, xyz_pm, out=dW0[:, :3])
         _ops.linear_wgrad(dz, F_pm, out=dW0[:, 3:])
         return None, None, None, dW0.unsqueeze(2), db0, dW1.unsqueeze(2), db1, dW2.unsqueeze(2), db2
+
+
+class ConfPoolFn(Function):
+    """The confidence-weighted pooling that ends stage 1's dense half (models/DCL_Net.py: conf_1 ... F_p_wei) on the library's
+    own kernels: apply(logit1 (b,1,n1) or (b,n1), logit2 (b,1,n2) or (b,n2), F1 (b,C,n1), F2 (b,C,n2)) -> (conf (b, n1+n2) =
+    sigmoid(cat[logit1, logit2]), pooled (b,C) = sum_j softmax(conf)[j] F[c][j]).  Forward = ops.conf_softmax, so a train-mode
+    conf is the eval kernel's bit for bit, and ops.conf_pool_cm; backward = ops.conf_pool_cm_backward.  Neither pass makes
+    cat[F1, F2], the weighted product or anything else of F's size; only the gradients that are asked for are computed.  Saved:
+    conf, w, F1, F2.  Every sum has a pinned order (include/dclnet_hip.h): the same inputs give the same bits.  CUDA tensors
+    only."""
+
+    @staticmethod
+    def forward(ctx, logit1, logit2, F1, F2):
+        if not (logit1.is_cuda and logit2.is_cuda and F1.is_cuda and F2.is_cuda):
+            raise RuntimeError("ConfPoolFn (train_pool='fused') runs on the GPU only: got %s / %s / %s / %s tensors; the "
+                               "'modules' composition serves CPU tensors" % (logit1.device, logit2.device, F1.device, F2.device))
+        b = F1.shape[0]
+        ctx.logit_shapes = (logit1.shape, logit2.shape)
+        logit1, logit2 = _ops.N.f32c(logit1).reshape(b, -1), _ops.N.f32c(logit2).reshape(b, -1)
+        F1, F2 = _ops.N.f32c(F1), _ops.N.f32c(F2)
+        assert F1.dim() == 3 and F2.dim() == 3 and logit1.shape[1] == F1.shape[2] and logit2.shape[1] == F2.shape[2], \
+            (tuple(logit1.shape), tuple(logit2.shape), tuple(F1.shape), tuple(F2.shape))
+        conf, w, _ = _ops.conf_softmax(b, logit1.reshape(-1), logit2.reshape(-1))
+        pooled = _ops.conf_pool_cm(w, F1, F2)
+        ctx.save_for_backward(conf, w, F1, F2)
+        return conf, pooled
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_conf, g_pooled):
+        conf, w, F1, F2 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        need_logits, need_F = need[0] or need[1], need[2] or need[3]
+        if not (need_logits or need_F):
+            return None, None, None, None
+        dl1, dl2, dF1, dF2 = _ops.conf_pool_cm_backward(conf, w, F1, F2, _ops.N.f32c(g_pooled), _ops.N.f32c(g_conf),
+                                                        need_logits=need_logits, need_F=need_F)
+        s1, s2 = ctx.logit_shapes
+        return (dl1.view(s1) if need[0] else None, dl2.view(s2) if need[1] else None,
+                dF1 if need[2] else None, dF2 if need[3] else None)

@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..autograd import CrossAttentionFn, Ortho9dFn
+from ..autograd import ConfPoolFn, CrossAttentionFn, Ortho9dFn
 from .. import spconv
 from ..libs.pointgroup_ops.functions import pointgroup_ops
 from .losses import losses  # noqa: F401  (reference: models/DCL_Net.py::losses)
@@ -54,6 +54,15 @@ def check_train_rotation(train_rotation):
     if train_rotation not in TRAIN_ROTATION_MODES:
         raise ValueError('train_rotation must be "host" or "device", got %r' % (train_rotation,))
     return train_rotation
+
+
+TRAIN_POOL_MODES = ("modules", "fused")
+
+
+def check_train_pool(train_pool):
+    if train_pool not in TRAIN_POOL_MODES:
+        raise ValueError('train_pool must be "modules" or "fused", got %r' % (train_pool,))
+    return train_pool
 
 
 def ortho9d2matrix(x_raw, y_raw, z_raw, train_rotation="host"):
@@ -86,7 +95,7 @@ class Network(nn.Module):
     def __init__(self, cfg, mode="train", fused=True, graph_max_batch=8, async_inputs=False, graph_max_points=98304,
                  single_stream=False, pipeline_chunks=1, capture_graph=True, pair_features=None,
                  train_attention="materialised", train_rotation="host", train_conv_wgrad="rows",
-                 train_conv_dgrad="conv"):
+                 train_conv_dgrad="conv", train_pool="modules"):
         """graph_max_batch > 0 (default 8): eval-mode calls with at most that many crops go through forward_graphed (one
         whole-forward hipGraph per batch size, captured on first use) -- the one-image-at-a-time eval loops of the
         reference (tools/test_LM.py:104-112: one object per call) are launch-bound otherwise: 0.53 instead of 1.1 ms
@@ -125,8 +134,14 @@ class Network(nn.Module):
         dispatcher on the transposed rulebook and a transposed copy of W; "direct" = csrc/conv_dgrad.hip, which reads W as
         registered, on the convolutions whose (cin, cout) is in ops.CONV_DGRAD_DIRECT_WIDTHS -- the widths on which it was measured
         faster (profiles/conv_dgrad.txt) -- and "conv" on the others: a rule by widths alone.  Forward and dW are the same either way.
+        train_pool: how the same path forms the confidence-weighted pooling that ends its dense half (conf_1 ... F_p_wei).
+        "modules" (default) = torch's sigmoid, softmax, cat, broadcast product and sum, which copy the fusers' (b, 1024, N + M)
+        output, write a product of the same size and keep both for the backward; "fused" = one autograd.ConfPoolFn
+        (ops.conf_softmax + csrc/conf_pool_grad.hip), which reads the two fuser outputs in place, forward and backward, in pinned
+        summation orders.  The eval-mode fused pipeline never reads it.
         These are constructor arguments on purpose: nothing on the call path reads the environment."""
         super().__init__()
+        self.train_pool = check_train_pool(train_pool)
         self.train_conv_dgrad = ops.check_conv_dgrad(train_conv_dgrad, "train_conv_dgrad")
         self.train_conv_wgrad = ops.check_conv_wgrad(train_conv_wgrad, "train_conv_wgrad")
         self.train_rotation = check_train_rotation(train_rotation)
@@ -1015,11 +1030,16 @@ class Network(nn.Module):
             F_Xo_m, F_Yc_m = torch.bmm(Yo["m1"], A1), torch.bmm(Xc["m2"], A2)
         conf_1 = self.regressor_conf(torch.cat([Xc["m1"], F_Xo_m], dim=1))
         conf_2 = self.regressor_conf_bi(torch.cat([F_Yc_m, Yo["m2"]], dim=1))
-        conf = torch.sigmoid(torch.cat([conf_1, conf_2], dim=2))
-        conf_softmax = torch.softmax(conf, dim=2)
-        F_p = torch.cat([self.neck_fuser(torch.cat([Xc["p1"], F_Xo_p], dim=1)),
-                         self.neck_fuser_bi(torch.cat([F_Yc_p, Yo["p2"]], dim=1))], dim=2)
-        F_p_wei = torch.sum(F_p * conf_softmax, dim=2, keepdim=True)
+        if self.train_pool == "fused":
+            out = ConfPoolFn.apply(conf_1, conf_2, self.neck_fuser(torch.cat([Xc["p1"], F_Xo_p], dim=1)),
+                                   self.neck_fuser_bi(torch.cat([F_Yc_p, Yo["p2"]], dim=1)))
+            conf, F_p_wei = out[0].unsqueeze(1), out[1].unsqueeze(2)
+        else:
+            conf = torch.sigmoid(torch.cat([conf_1, conf_2], dim=2))
+            conf_softmax = torch.softmax(conf, dim=2)
+            F_p = torch.cat([self.neck_fuser(torch.cat([Xc["p1"], F_Xo_p], dim=1)),
+                             self.neck_fuser_bi(torch.cat([F_Yc_p, Yo["p2"]], dim=1))], dim=2)
+            F_p_wei = torch.sum(F_p * conf_softmax, dim=2, keepdim=True)
         o9 = self.regressor_rot(F_p_wei).squeeze(-1)
         rot_pred = ortho9d2matrix(o9[:, :3], o9[:, 3:6], o9[:, 6:], self.train_rotation)
         trans_pred = self.regressor_trans(F_p_wei).squeeze(-1)

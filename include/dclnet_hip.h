@@ -1000,6 +1000,49 @@ int dcl_pose_objective_bwd_host(int b, int n, const float *posed, const float *p
                                 float *g_cd_pose_pt, float *g_cd_pose_tp, float *g_cd_Xo_pt, float *g_cd_Xo_tp,
                                 float *g_cd_Yc_pt, float *g_cd_Yc_tp);
 
+/* ------------------------------------------------------ confidence pooling, channel-major, with its gradient ---
+ * The pooling that ends stage 1's dense half on the differentiable module path (models/DCL_Net.py: conf_1 ... F_p_wei;
+ * csrc/conf_pool_grad.hip, csrc/conf_pool_grad.h).  All arrays fp32 contiguous: F1 (b,c,n1), F2 (b,c,n2) channel-major, conf
+ * and w (b, n1+n2) as dcl_conf_softmax leaves them (direction 1 first), L = n1 + n2.  Any c, n1, n2 >= 1; element offsets are
+ * 64-bit.  fma(a,b,c) is one rounding; everything else is rounded operation by operation as written.  Per crop:
+ *   pooled[c] = sum_{j<n1} w[j] F1[c][j] + sum_{j<n2} w[n1+j] F2[c][j]
+ *   d[j]      = sum_c g_pooled[c] F[c][j]                  (F = F1 | F2 along j)
+ *   dot       = sum_j w[j] d[j]
+ *   ds[j]     = fma(w[j], d[j] - dot, g_conf[j])           (g_conf NULL: w[j] * (d[j] - dot))
+ *   dlogit[j] = (ds[j] * s) * (1 - s),  s = conf[j]        (j < n1 -> dlogit1 (b,n1), else dlogit2 (b,n2))
+ *   dF[c][j]  = g_pooled[c] * w[j]
+ * PINNED ORDER of every sum, a function of c, n1, n2 alone (not of b, of the grid or of a row's alignment); no atomics:
+ *   pooled: a row has 256 slots; slot k runs one fma chain from +0 over F1's columns k, k+256, ... ascending, then over F2's
+ *     columns k, k+256, ... ascending (a missing column adds nothing); slots 4l .. 4l+3 fold as (s0 + s1) + (s2 + s3) into lane
+ *     value l, and the 64 lane values by a butterfly with strides 32, 16, ..., 1 (v[l] = v[l] + v[l ^ stride]).
+ *   d: channels in chunks of 256 (the last may be short); a chunk of a column is one fma chain from +0, channels ascending;
+ *     the chunks are added ascending from chunk 0's value.
+ *   dot: 256 lanes; lane l runs fma(w[j], d[j], acc) from +0 over j = l, l+256, ... ascending; the accumulators are folded by a
+ *     tree with strides 128, 64, ..., 1 (slot l += slot l+stride for l < stride).
+ * The same inputs give the same bits, and a crop gives the same bits alone as inside a batch.
+ *
+ * dcl_conf_pool_cm_fwd: w, F1, F2 -> pooled (b,c), one launch.
+ * dcl_conf_pool_cm_bwd: g_pooled (b,c) and g_conf (b,L; may be NULL = zero) are the upstream gradients of pooled and conf.
+ *   dlogit1 / dlogit2 are both given or both NULL, dF1 (b,c,n1) / dF2 (b,c,n2) likewise, not all four NULL; what is given is
+ *   OVERWRITTEN.  The logits' gradient takes two launches (partials of d: F read once; the per-crop rest), dF one streaming
+ *   write.  ws: scratch of at least dcl_conf_pool_cm_bwd_ws_bytes(b, c, n1, n2) bytes (the chunks' partials and d); read only
+ *   when dlogit1 / dlogit2 are given, otherwise it may be NULL.
+ * The *_host entry points run the same routines on HOST pointers, take no scratch and make no GPU call.
+ * All: b < 0, c < 1, n1 < 1, n2 < 1, a NULL required pointer (with b > 0), an incomplete pair of outputs or too small a
+ * ws_bytes return DCL_EINVAL before any GPU call; b == 0 returns 0.                                                      */
+int dcl_conf_pool_cm_fwd(int b, int c, int n1, int n2, const float *w, const float *F1, const float *F2,
+                         float *pooled, dclStream_t stream);
+int dcl_conf_pool_cm_bwd_ws_bytes(int b, int c, int n1, int n2, int64_t *bytes_host);
+int dcl_conf_pool_cm_bwd(int b, int c, int n1, int n2, const float *conf, const float *w, const float *F1,
+                         const float *F2, const float *g_pooled, const float *g_conf,
+                         float *dlogit1, float *dlogit2, float *dF1, float *dF2, void *ws, int64_t ws_bytes,
+                         dclStream_t stream);
+int dcl_conf_pool_cm_fwd_host(int b, int c, int n1, int n2, const float *w, const float *F1, const float *F2,
+                              float *pooled);
+int dcl_conf_pool_cm_bwd_host(int b, int c, int n1, int n2, const float *conf, const float *w, const float *F1,
+                              const float *F2, const float *g_pooled, const float *g_conf,
+                              float *dlogit1, float *dlogit2, float *dF1, float *dF2);
+
 /* ------------------------------------------------------ optimizer step ---
  * What follows loss.backward() in the reference's training scripts (tools/train_YCBV_stage1.py:119-125, 212-231): the global
  * gradient norm that AutoClip measures, and the Adam update with the clip factor folded in (csrc/optim.hip).  Both calls walk
