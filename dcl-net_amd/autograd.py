@@ -387,3 +387,36 @@ class ConfPoolFn(Function):
         s1, s2 = ctx.logit_shapes
         return (dl1.view(s1) if need[0] else None, dl2.view(s2) if need[1] else None,
                 dF1 if need[2] else None, dF2 if need[3] else None)
+
+
+class BnReluFn(Function):
+    """Train-mode nn.BatchNorm1d -> nn.ReLU on the (rows, C) feature matrix of a sparse tensor as one function on the library's
+    own kernels (models/Modules.py: BasicBlock_SPCONV.norm_form = "fused"): apply(x (rows,C), gamma (C,), beta (C,),
+    running_mean, running_var (C,) or None, momentum, eps) -> z (rows,C).  Forward = ops.bn_relu, which also updates the running
+    statistics in place (buffers outside the graph; num_batches_tracked stays with the caller); backward =
+    ops.bn_relu_backward.  Saved: x, gamma, beta, mean, invstd -- not y or z: the ReLU mask is recomputed from x by the same
+    expression, hence with the same bits.  Every sum is float64 in a pinned order
+    (include/dclnet_hip.h): the same inputs give the same bits.  Only the gradients that are asked for are computed.  CUDA
+    tensors only."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps):
+        if not (x.is_cuda and gamma.is_cuda and beta.is_cuda):
+            raise RuntimeError("BnReluFn (train_norm='fused') runs on the GPU only: got %s / %s / %s tensors; the 'modules' "
+                               "composition serves CPU tensors" % (x.device, gamma.device, beta.device))
+        x, gamma, beta = _ops.N.f32c(x), _ops.N.f32c(gamma), _ops.N.f32c(beta)
+        z, mean, invstd = _ops.bn_relu(x, gamma, beta, running_mean, running_var, momentum, eps)
+        ctx.save_for_backward(x, gamma, beta, mean, invstd)
+        return z
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, gamma, beta, mean, invstd = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        need_x, need_affine = need[0], need[1] or need[2]
+        if not (need_x or need_affine):
+            return (None,) * 7
+        g = _ops.N.f32c(g)
+        dx, dgamma, dbeta = _ops.bn_relu_backward(x, gamma, beta, mean, invstd, g, need_x=need_x, need_affine=need_affine)
+        return dx, dgamma if need[1] else None, dbeta if need[2] else None, None, None, None, None

@@ -29,7 +29,7 @@ from ..autograd import ConfPoolFn, CrossAttentionFn, Ortho9dFn
 from .. import spconv
 from ..libs.pointgroup_ops.functions import pointgroup_ops
 from .losses import losses  # noqa: F401  (reference: models/DCL_Net.py::losses)
-from .Modules import (Aligner, Backbone_SPCONV, BasicBlock_3DCONV, Head_MultiLayerPerceptron,
+from .Modules import (Aligner, Backbone_SPCONV, BasicBlock_3DCONV, BasicBlock_SPCONV, Head_MultiLayerPerceptron,
                       Ops_GetPointFeat_spconv)
 
 HOST_TIMES = None                   # tools/host_timeline.py sets this to a list: (label, perf_counter) marks of _forward_fused
@@ -57,6 +57,7 @@ def check_train_rotation(train_rotation):
 
 
 TRAIN_POOL_MODES = ("modules", "fused")
+TRAIN_NORM_MODES = ops.TRAIN_NORM_MODES
 
 
 def check_train_pool(train_pool):
@@ -95,7 +96,7 @@ class Network(nn.Module):
     def __init__(self, cfg, mode="train", fused=True, graph_max_batch=8, async_inputs=False, graph_max_points=98304,
                  single_stream=False, pipeline_chunks=1, capture_graph=True, pair_features=None,
                  train_attention="materialised", train_rotation="host", train_conv_wgrad="rows",
-                 train_conv_dgrad="conv", train_pool="modules"):
+                 train_conv_dgrad="conv", train_pool="modules", train_norm="modules"):
         """graph_max_batch > 0 (default 8): eval-mode calls with at most that many crops go through forward_graphed (one
         whole-forward hipGraph per batch size, captured on first use) -- the one-image-at-a-time eval loops of the
         reference (tools/test_LM.py:104-112: one object per call) are launch-bound otherwise: 0.53 instead of 1.1 ms
@@ -139,9 +140,16 @@ class Network(nn.Module):
         output, write a product of the same size and keep both for the backward; "fused" = one autograd.ConfPoolFn
         (ops.conf_softmax + csrc/conf_pool_grad.hip), which reads the two fuser outputs in place, forward and backward, in pinned
         summation orders.  The eval-mode fused pipeline never reads it.
+        train_norm: how a train-mode forward runs the BatchNorm1d -> ReLU pair behind each of the 16 sparse convolutions of the
+        two backbones (Modules.BasicBlock_SPCONV.norm_form).  "modules" (default) = nn.BatchNorm1d and nn.ReLU on the (rows, C)
+        feature matrix; "fused" = one autograd.BnReluFn per block on csrc/bn_relu.hip: batch statistics and the backward's two
+        sums in float64 in a pinned chunk order (no atomics: a backbone's forward and backward repeat bit for bit), the running
+        statistics updated by the same launches, the ReLU mask recomputed in the backward instead of kept.  Same parameters,
+        buffers and state_dict keys; eval mode, the fused inference pipeline, the graphs and the dense half never read it.
         These are constructor arguments on purpose: nothing on the call path reads the environment."""
         super().__init__()
         self.train_pool = check_train_pool(train_pool)
+        self.train_norm = ops.check_train_norm(train_norm)
         self.train_conv_dgrad = ops.check_conv_dgrad(train_conv_dgrad, "train_conv_dgrad")
         self.train_conv_wgrad = ops.check_conv_wgrad(train_conv_wgrad, "train_conv_wgrad")
         self.train_rotation = check_train_rotation(train_rotation)
@@ -170,6 +178,8 @@ class Network(nn.Module):
                 if isinstance(m, spconv.SparseConvolution):
                     m.wgrad = self.train_conv_wgrad
                     m.dgrad = ops.conv_dgrad_form(m.in_channels, m.out_channels, self.train_conv_dgrad)
+                elif isinstance(m, BasicBlock_SPCONV):
+                    m.norm_form = self.train_norm
         self.stage1_get_point_feats = Ops_GetPointFeat_spconv(SCALE_LISTS, self.unit_voxel_extent, VOXEL_NUM_LIMIT)
         block = partial(BasicBlock_3DCONV, size=1, bias=False, stride=1, padding=0, norm=True, act="relu", drop=0.0)
         for grp in ("1", "2"):                       # registration order = the reference's (state_dict order)

@@ -10,6 +10,7 @@ import torch
 import torch.nn as nn
 
 from .. import spconv
+from ..autograd import BnReluFn
 from ..libs.pointnet_sp import pointnet2_utils as pointnet2_utils_sp
 from ..spconv import SparseAvgPool3d
 
@@ -25,7 +26,13 @@ def _act_layer(act):
 
 
 class BasicBlock_SPCONV(nn.Module):
-    """sparse conv (SparseConv3d | SubMConv3d) -> BatchNorm1d -> act  (reference Modules.py:12-57)."""
+    """sparse conv (SparseConv3d | SubMConv3d) -> BatchNorm1d -> act  (reference Modules.py:12-57).
+    norm_form: how a TRAIN-mode forward runs the BatchNorm1d -> ReLU pair on the (rows, C) feature matrix.  "modules" (default)
+    = the two torch modules; "fused" = one autograd.BnReluFn on csrc/bn_relu.hip, reading the same parameters and updating
+    the same buffers -- taken only while training, on CUDA features with rows, by a block that is exactly conv ->
+    BatchNorm1d (affine, running statistics, a float momentum) -> ReLU; anything else runs the modules.  Network(train_norm=)
+    sets it; the module structure and the state_dict keys are the same either way."""
+    norm_form = "modules"
 
     def __init__(self, subm, dim_in, dim_out, bias, size, stride, padding, norm, act, drop, indice_key):
         super().__init__()
@@ -45,8 +52,28 @@ class BasicBlock_SPCONV(nn.Module):
             layers.append(nn.Dropout(drop))
         self.layers = spconv.SparseSequential(*layers)
 
+    def _fused_norm(self):
+        """the BatchNorm1d of a block that is exactly conv -> BatchNorm1d(affine, running stats, float momentum) -> ReLU, or None"""
+        if len(self.layers) != 3:
+            return None
+        bn, act = self.layers[1], self.layers[2]
+        if type(bn) is not nn.BatchNorm1d or type(act) is not nn.ReLU:
+            return None
+        if not (bn.affine and bn.track_running_stats and isinstance(bn.momentum, float)):
+            return None
+        return bn
+
     def forward(self, input):
-        return self.layers(input)
+        bn = self._fused_norm() if self.norm_form == "fused" and self.training else None
+        if bn is None:
+            return self.layers(input)
+        x = self.layers[0](input)
+        if x.features.is_cuda and x.features.shape[0] > 0:
+            x.features = BnReluFn.apply(x.features, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps)
+            bn.num_batches_tracked.add_(1)
+        elif x.indices.shape[0]:                     # SparseSequential's rule: dense layers never see an empty batch
+            x.features = self.layers[2](self.layers[1](x.features))
+        return x
 
 
 class _PointwiseConv3d(nn.Conv3d):

@@ -967,6 +967,115 @@ def conf_pool_cm_backward_host(conf, w, F1, F2, g_pooled, g_conf=None, need_logi
     return _conf_pool_cm_backward(conf, w, F1, F2, g_pooled, g_conf, need_logits, need_F, True)
 
 
+BN_ROWS = 256                  # include/dclnet_hip.h: DCL_BN_ROWS, the rows per chunk of the BatchNorm sums
+TRAIN_NORM_MODES = ("modules", "fused")
+
+
+def check_train_norm(value, what="train_norm"):
+    if value not in TRAIN_NORM_MODES:
+        raise ValueError('%s must be "modules" or "fused", got %r' % (what, value))
+    return value
+
+
+def _bn_relu_args(x, host, what, *vectors):
+    _same_side(host, what, x, *vectors)
+    assert x.dim() == 2, "%s: x must be (rows, C), got %s" % (what, tuple(x.shape))
+    rows, c = int(x.shape[0]), int(x.shape[1])
+    if rows == 1:
+        raise ValueError("%s: expected more than 1 row per channel when training, got input size %s" % (what, tuple(x.shape)))
+    for v in vectors:
+        assert v is None or tuple(v.shape) == (c,), "%s: per-channel vectors hold C = %d floats, got %s" % (what, c, tuple(v.shape))
+    return rows, c
+
+
+def _bn_relu_ws(rows, c, dev):
+    q = C.c_int64(0)
+    N.check(N.lib().dcl_bn_relu_ws_bytes(rows, c, C.byref(q)), "bn_relu_ws_bytes")
+    nbytes = int(q.value)
+    return torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=dev), nbytes
+
+
+def _running_inplace(t, what):
+    if t is not None and not (t.dtype == torch.float32 and t.is_contiguous()):
+        raise ValueError("%s is updated in place: it must be a contiguous fp32 tensor" % what)
+
+
+def _bn_relu(x, gamma, beta, running_mean, running_var, momentum, eps, relu, host):
+    what = "bn_relu_host" if host else "bn_relu"
+    rows, c = _bn_relu_args(x, host, what, gamma, beta, running_mean, running_var)
+    assert (running_mean is None) == (running_var is None), "running_mean and running_var come as a pair"
+    _running_inplace(running_mean, "running_mean"), _running_inplace(running_var, "running_var")
+    x, gamma, beta = N.f32c(x), N.f32c(gamma), N.f32c(beta)
+    z = torch.empty_like(x)
+    mean = torch.empty((c,), dtype=torch.float32, device=x.device)
+    invstd = torch.empty_like(mean)
+    if rows == 0:
+        return z, mean.zero_(), invstd.zero_()
+    args = (rows, c, N.ptr(x), N.ptr(gamma), N.ptr(beta), float(eps), float(momentum), N.ptr(running_mean),
+            N.ptr(running_var), N.ptr(mean), N.ptr(invstd), N.ptr(z), int(bool(relu)))
+    if host:
+        N.check(N.lib().dcl_bn_relu_fwd_host(*args), what)
+    else:
+        ws, nbytes = _bn_relu_ws(rows, c, x.device)
+        N.check(N.lib().dcl_bn_relu_fwd(*args, N.ptr(ws), nbytes, N.stream()), what)
+    return z, mean, invstd
+
+
+def _bn_relu_backward(x, gamma, beta, mean, invstd, g, relu, need_x, need_affine, out, host):
+    what = "bn_relu_backward_host" if host else "bn_relu_backward"
+    rows, c = _bn_relu_args(x, host, what, gamma, beta, mean, invstd)
+    _same_side(host, what, g, out)
+    assert need_x or need_affine
+    assert tuple(g.shape) == (rows, c), "g: %s wanted, got %s" % ((rows, c), tuple(g.shape))
+    x, gamma, beta, mean, invstd, g = (N.f32c(t) for t in (x, gamma, beta, mean, invstd, g))
+    dx = None
+    if need_x:
+        if out is not None:
+            assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (rows, c), "out: contiguous fp32 (rows, C)"
+            dx = out
+        else:
+            dx = torch.empty_like(x)
+    dgamma, dbeta = (torch.empty_like(gamma), torch.empty_like(gamma)) if need_affine else (None, None)
+    if rows == 0:
+        return dx, None if dgamma is None else dgamma.zero_(), None if dbeta is None else dbeta.zero_()
+    args = (rows, c, N.ptr(x), N.ptr(gamma), N.ptr(beta), N.ptr(mean), N.ptr(invstd), N.ptr(g), int(bool(relu)),
+            N.ptr(dx), N.ptr(dgamma), N.ptr(dbeta))
+    if host:
+        N.check(N.lib().dcl_bn_relu_bwd_host(*args), what)
+    else:
+        ws, nbytes = _bn_relu_ws(rows, c, x.device)
+        N.check(N.lib().dcl_bn_relu_bwd(*args, N.ptr(ws), nbytes, N.stream()), what)
+    return dx, dgamma, dbeta
+
+
+def bn_relu(x, gamma, beta, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, relu=True):
+    """Train-mode BatchNorm1d + ReLU on a (rows, C) row-major matrix (dcl_bn_relu_fwd; csrc/bn_relu.hip): batch statistics in
+    float64 in the summation order include/dclnet_hip.h pins, mean and invstd rounded to fp32 once, z = relu((x - mean) invstd
+    gamma + beta) (relu=False: without the ReLU) -> (z, mean (C,), invstd (C,)).  running_mean / running_var, when given, are
+    updated IN PLACE by the same launches with the unbiased variance, as nn.BatchNorm1d does; nothing is read back.  rows >= 2
+    (0 rows: nothing is launched); a non-contiguous x is copied first."""
+    return _bn_relu(x, gamma, beta, running_mean, running_var, momentum, eps, relu, False)
+
+
+def bn_relu_backward(x, gamma, beta, mean, invstd, g, relu=True, need_x=True, need_affine=True, out=None):
+    """Gradients of bn_relu (dcl_bn_relu_bwd): mean, invstd as bn_relu returned them, g (rows, C) the upstream gradient of z ->
+    (dx, dgamma, dbeta); what is not needed is None and is not computed.  The ReLU mask is recomputed from x by the forward's
+    expression (y and z are not kept); the two per-channel sums are float64 in the forward's order.  out: where dx goes -- a
+    contiguous fp32 (rows, C) tensor, which may be g itself."""
+    return _bn_relu_backward(x, gamma, beta, mean, invstd, g, relu, need_x, need_affine, out, False)
+
+
+def bn_relu_host(x, gamma, beta, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, relu=True):
+    """bn_relu on CPU tensors: the kernels' routines compiled for the host, in their summation order.  For checking the
+    arithmetic where there is no GPU; no model path calls it."""
+    return _bn_relu(x, gamma, beta, running_mean, running_var, momentum, eps, relu, True)
+
+
+def bn_relu_backward_host(x, gamma, beta, mean, invstd, g, relu=True, need_x=True, need_affine=True, out=None):
+    """bn_relu_backward on CPU tensors; no model path calls it."""
+    return _bn_relu_backward(x, gamma, beta, mean, invstd, g, relu, need_x, need_affine, out, True)
+
+
 OPTIM_CHUNK = 4096             # include/dclnet_hip.h: DCL_OPTIM_CHUNK
 OPTIM_TENSOR_BYTES = 48        # sizeof(dclOptimTensor): four pointers, int64 numel, float step_size, float bc2_sqrt
 

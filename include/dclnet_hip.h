@@ -1043,6 +1043,51 @@ int dcl_conf_pool_cm_bwd_host(int b, int c, int n1, int n2, const float *conf, c
                               const float *F2, const float *g_pooled, const float *g_conf,
                               float *dlogit1, float *dlogit2, float *dF1, float *dF2);
 
+/* ------------------------------------------------------ sparse-conv BatchNorm + ReLU, train mode, with its gradient ---
+ * nn.BatchNorm1d -> nn.ReLU on the (rows, c) row-major feature matrix of a sparse tensor, in train mode (models/Modules.py:
+ * BasicBlock_SPCONV.norm_form = "fused"; csrc/bn_relu.hip, csrc/bn_relu.h).  x, g, z, dx fp32 contiguous (V = rows, C = c);
+ * gamma, beta, mean, invstd, the running statistics and dgamma / dbeta hold c floats.  Any c >= 1, rows >= 2; element offsets
+ * are 64-bit.  Every operation is rounded as written (no contraction).  Per channel:
+ *   float64:  mean = S1 / V,  var = max(S2 / V - mean^2, 0),  invstd = 1 / sqrt(var + (double)eps),  S1 = sum x, S2 = sum x^2;
+ *             mean and invstd are rounded to fp32 once and are what the apply and the backward use
+ *   fp32:     running_mean = (1 - m) running_mean + m mean;  running_var = (1 - m) running_var + m (float)(var V / (V - 1))
+ *   fp32:     xhat = (x - mean) invstd;  y = xhat gamma + beta;  z = y > 0 ? y : 0          (relu = 0: z = y)
+ *   backward: dy = (relu == 0 || y > 0) ? g : 0, y recomputed from x by the same expression, hence the same bits;
+ *             T1 = sum dy, T2 = sum dy xhat in float64;  dbeta = (float)T1;  dgamma = (float)T2;
+ *             mb = (float)(T1 / V);  mg = (float)(T2 / V);  a = gamma invstd;  dx = a ((dy - mb) - xhat mg)
+ * PINNED ORDER of S1, S2, T1, T2, a function of (V, C) alone (not of the grid, of a pointer's alignment or of the load path);
+ * float64 throughout, no atomics:
+ *   the rows are cut into chunks of DCL_BN_ROWS rows (the last may be short), the channels into groups of 4 adjacent ones,
+ *   G = ceil(C / 4).  Inside a chunk a channel has S slots, S = floor(256 / min(G, 16)); slot s adds the
+ *   chunk's rows s, s + S, s + 2S, ... ascending from +0.0 (acc = acc + (double)v; acc2 = acc2 + (double)v * (double)w with an
+ *   exact product); the S slot values are added ascending from +0.0 into the chunk's partial; the chunks' partials are added
+ *   ascending from +0.0.  16-byte and float-by-float accesses feed the same accumulators in the same order.
+ * The same inputs give the same bits.  Non-finite inputs propagate as they fall; nothing is promised for them.
+ *
+ * dcl_bn_relu_fwd: three launches (chunk sums, finish, apply).  running_mean / running_var are both given or both NULL; when
+ *   given they are updated by the finish launch (no host read-back).  mean, invstd (c floats) and z (rows, c) are OVERWRITTEN.
+ * dcl_bn_relu_bwd: g (rows, c) is the upstream gradient of z.  dx (rows, c) may be NULL and may be g itself; dgamma / dbeta are
+ *   both given or both NULL; not all three NULL.  Two launches (chunk sums, finish) and one more for dx.
+ * ws: scratch of at least dcl_bn_relu_ws_bytes(rows, c) bytes (the chunks' float64 partials, then mb and mg), 8-byte aligned.
+ * The *_host entry points run the same routines on HOST pointers, take no scratch and make no GPU call.
+ * All: rows < 0, rows == 1 (no variance, as torch refuses it), c < 1, a NULL required pointer, half a pair, relu other than
+ * 0 / 1, eps < 0, momentum outside [0, 1] or too small a ws_bytes return DCL_EINVAL before any GPU call; rows == 0 returns 0. */
+#ifndef DCL_BN_ROWS
+#define DCL_BN_ROWS 256
+#endif
+int dcl_bn_relu_ws_bytes(int64_t rows, int c, int64_t *bytes_host);
+int dcl_bn_relu_fwd(int64_t rows, int c, const float *x, const float *gamma, const float *beta, float eps, float momentum,
+                    float *running_mean, float *running_var, float *mean, float *invstd, float *z, int relu,
+                    void *ws, int64_t ws_bytes, dclStream_t stream);
+int dcl_bn_relu_bwd(int64_t rows, int c, const float *x, const float *gamma, const float *beta, const float *mean,
+                    const float *invstd, const float *g, int relu, float *dx, float *dgamma, float *dbeta,
+                    void *ws, int64_t ws_bytes, dclStream_t stream);
+int dcl_bn_relu_fwd_host(int64_t rows, int c, const float *x, const float *gamma, const float *beta, float eps,
+                         float momentum, float *running_mean, float *running_var, float *mean, float *invstd, float *z,
+                         int relu);
+int dcl_bn_relu_bwd_host(int64_t rows, int c, const float *x, const float *gamma, const float *beta, const float *mean,
+                         const float *invstd, const float *g, int relu, float *dx, float *dgamma, float *dbeta);
+
 /* ------------------------------------------------------ optimizer step ---
  * What follows loss.backward() in the reference's training scripts (tools/train_YCBV_stage1.py:119-125, 212-231): the global
  * gradient norm that AutoClip measures, and the Adam update with the clip factor folded in (csrc/optim.hip).  Both calls walk
