@@ -81,7 +81,11 @@ __global__ __launch_bounds__(256, 2) void k_linear_split(const LinSplitArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
   const int nchunks = a.K / kSpKC;
-  const int whatif = a.xcd_remap >> 1;                     // (diagnostic library: timing-only what-if runs; 0 in the product)
+#ifdef DCL_DIAG
+  const int whatif = a.xcd_remap >> 1;                     // (diagnostic library: timing-only what-if runs)
+#else
+  constexpr int whatif = 0;                                // (the product's chunk loop carries none of their branches)
+#endif
   const unsigned lds0 = lds_addr(sp_lds);
   const size_t bstep = (size_t)ntn * kSpB;                 // bytes from a column tile's chunk to its next chunk
 
@@ -107,16 +111,13 @@ __global__ __launch_bounds__(256, 2) void k_linear_split(const LinSplitArgs a) {
     const unsigned boff = (unsigned)tid * 16u;
     const float *abase = a.x + (size_t)row0 * a.ldx;
     const unsigned char *bbase = a.planes + (size_t)tn * kSpB;
-    // the 7 DMA pieces of a chunk: 3 of the weight pieces, 4 x-row groups; bases advance behind the last one
+    // the 7 DMA pieces of a chunk: 3 of the weight pieces (k = 0..2), 4 x-row groups (k = 3..6); each base advances behind its last
     auto issue_piece = [&](int k, int stage) {
       const unsigned s0 = lds0 + (unsigned)(stage * kSpST);
       if (k < 3) glds16_s(boff + (unsigned)(k * 4096), bbase, s0 + (unsigned)(kSpA + k * 4096 + wave * 1024));
       else glds16_s(aoff[k - 3], abase, s0 + (unsigned)((wave * 64 + (k - 3) * 16) * 64));
-      if (k == 6) { abase += kSpKC; bbase += bstep; }
-    };
-    auto issue = [&](int stage) {
-#pragma unroll
-      for (int k = 0; k < 7; ++k) issue_piece(k, stage);
+      if (k == 2) bbase += bstep;
+      if (k == 6) abase += kSpKC;
     };
     f32x16 acc[2][4];
 #pragma unroll
@@ -126,54 +127,80 @@ __global__ __launch_bounds__(256, 2) void k_linear_split(const LinSplitArgs a) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
 
+    // x fragments (fp32) and their pieces live ACROSS chunks: a wave DMAs, reads and splits only its own 64 rows of x, so row block 0
+    // of chunk c + 1 is read and split under the MFMAs of chunk c, behind the wave's own vmcnt and in front of the barrier -- the
+    // SHORT chunk head.  Measured per epilogue (profiles/interval_heads.txt): EPI 0 / 1 / 2 gain 1.5-3 % from it, EPI 3 (K = 256 only,
+    // a store-heavy epilogue) nothing, so EPI 3 keeps the head it had: x reads, the seven DMA pieces and the split of row block 0
+    // behind the barrier.
+    constexpr bool kShortHead = EPI != 3;
+    float4 av[2][2];
+    u32x4 ap[2][3];
+    auto read_a = [&](int i, int stage) {
+      const unsigned char *sa = afrag + stage * kSpST;
+#pragma unroll
+      for (int q = 0; q < 2; ++q) av[i][q] = *reinterpret_cast<const float4 *>(sa + i * 32 * 64 + (((2 * h + q) ^ asw) << 4));
+    };
+    auto split_a = [&](int i, int part) {                  // values 2 part, 2 part + 1 of the row block's eight
+      if (!(whatif & 2)) {
+        unsigned ph, pm, pl;
+        const float4 v = av[i][part >> 1];
+        if (part & 1) bf16_split2(v.z, v.w, ph, pm, pl); else bf16_split2(v.x, v.y, ph, pm, pl);
+        ap[i][0][part] = ph; ap[i][1][part] = pm; ap[i][2][part] = pl;
+      } else {                                             // (what-if "no split": any three registers)
+        const float4 v = av[i][part >> 1];
+        ap[i][0][part] = __float_as_uint(v.x); ap[i][1][part] = __float_as_uint(v.y); ap[i][2][part] = __float_as_uint(v.z);
+      }
+    };
+
     dcl_lds_barrier();                                     // (a previous tile's last reads / epilogue scratch)
     if constexpr (EPI == 1) {                              // the tile's row weights -> LDS behind the ring
       float *wl = reinterpret_cast<float *>(sp_lds + 2 * kSpST);
       const int row = row0 + tid, crop = row / a.rows_per_crop;
       wl[tid] = row < a.M ? a.roww[(size_t)crop * a.w_stride + (row - crop * a.rows_per_crop)] : 0.0f;
     }
-    issue(0);
+#pragma unroll
+    for (int k = 0; k < 7; ++k) issue_piece(k, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (kShortHead) {
+      read_a(0, 0);                                        // the first chunk's x: this wave's own pieces, no barrier needed
+      read_a(1, 0);
+#pragma unroll
+      for (int part = 0; part < 4; ++part) split_a(0, part);
+    }
     for (int c = 0; c < nchunks; ++c) {
       const int st = c & 1;
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // everyone's pieces of chunk c are in (each wave waited for its own at the
-      __builtin_amdgcn_s_barrier();                        //  end of the previous chunk); nobody reads the other stage any more ...
+      __builtin_amdgcn_s_barrier();                        //  end of the previous chunk); nobody reads the other stage's weights any more
       // ... which chunk c + 1 lands in, under this chunk's MFMAs.  One instruction stream, pinned group by group (left alone the
-      // compiler splits all of x first, reads every weight fragment next and -- worst -- hoists the wait for the NEXT chunk's DMA in
-      // front of this chunk's MFMAs): first the fragment reads of row block 0 and column block 0 with the DMA issue under their
-      // latency, the split of row block 0, then eight blocks of six MFMAs, the first four each with a quarter of row block 1's
-      // split and the next column block's reads beside them.
-      const bool more = c + 1 < nchunks;
-      const unsigned char *sa = afrag + st * kSpST, *sb = bfrag + st * kSpST;
-      float4 av[2][2];
-      u32x4 ap[2][3], bp[4][3];
-      auto read_a = [&](int i) {
-#pragma unroll
-        for (int q = 0; q < 2; ++q) av[i][q] = *reinterpret_cast<const float4 *>(sa + i * 32 * 64 + (((2 * h + q) ^ asw) << 4));
-      };
+      // compiler reads every weight fragment first and -- worst -- hoists the wait for the NEXT chunk's DMA in front of this chunk's
+      // MFMAs).  With the short head a chunk opens with two column blocks' weight reads and the first MFMA block: row block 0 came
+      // split out of the previous chunk.  Behind the MFMA blocks, one group each: blocks 0-3 a quarter of row block 1's split,
+      // blocks 0-1 the next column blocks' reads; the next chunk's DMA pieces, x first (blocks 0-1: two each; blocks 2-4: a weight
+      // piece each); block 5 the wait that covers the x pieces (three younger pieces may be in flight) and the next chunk's x
+      // reads from the other stage; blocks 6-7 the split of its row block 0 (ap[0], av[0], av[1] are dead from block 4 on).
+      const bool more = c + 1 < nchunks, dma = more && !(whatif & 1);
+      const unsigned char *sb = bfrag + st * kSpST;
+      u32x4 bp[4][3];
       auto read_b = [&](int j) {
 #pragma unroll
         for (int p = 0; p < 3; ++p) bp[j][p] = *reinterpret_cast<const u32x4 *>(sb + p * kSpP + j * 32 * 32);
       };
-      auto split_a = [&](int i, int part) {                // values 2 part, 2 part + 1 of the row block's eight
-        unsigned ph, pm, pl;
-        const float4 v = av[i][part >> 1];
-        if (part & 1) bf16_split2(v.z, v.w, ph, pm, pl); else bf16_split2(v.x, v.y, ph, pm, pl);
-        ap[i][0][part] = ph; ap[i][1][part] = pm; ap[i][2][part] = pl;
-      };
-      read_a(0);
-      read_b(0);
-      read_a(1);
-      if (more && !(whatif & 1)) issue(st ^ 1);
-      __builtin_amdgcn_sched_barrier(0);
-      if (!(whatif & 2)) {
+      if constexpr (kShortHead) {
+        read_b(0);
+        read_b(1);
+      } else {                                             // fragment reads with the DMA issue under their latency, then the split
+        read_a(0, st);
+        read_b(0);
+        read_a(1, st);
+        if (dma) {
+#pragma unroll
+          for (int k = 0; k < 7; ++k) issue_piece(k, st ^ 1);
+        }
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int part = 0; part < 4; ++part) split_a(0, part);
-      } else {
-#pragma unroll
-        for (int p = 0; p < 3; ++p) ap[0][p] = u32x4{__float_as_uint(av[0][0].x), __float_as_uint(av[0][0].y), __float_as_uint(av[0][1].x), __float_as_uint(av[0][1].y)};
+        read_b(1);
       }
-      read_b(1);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int blk = 0; blk < 8; ++blk) {
@@ -184,11 +211,22 @@ __global__ __launch_bounds__(256, 2) void k_linear_split(const LinSplitArgs a) {
         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(ap[i][1]), as_bf16x8(bp[j][0]), acc[i][j], 0, 0, 0);
         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(ap[i][0]), as_bf16x8(bp[j][1]), acc[i][j], 0, 0, 0);
         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(ap[i][0]), as_bf16x8(bp[j][0]), acc[i][j], 0, 0, 0);
-        if (blk < 4) {
-          if (!(whatif & 2)) split_a(1, blk);
-          else { ap[1][0][blk] = __float_as_uint(av[1][blk >> 1].x); ap[1][1][blk] = __float_as_uint(av[1][blk >> 1].y); ap[1][2][blk] = __float_as_uint(av[1][blk >> 1].z); }
-        }
+        if (blk < 4) split_a(1, blk);
         if (blk < 2) read_b(blk + 2);
+        if (kShortHead && dma) {
+          if (blk == 0) { issue_piece(3, st ^ 1); issue_piece(4, st ^ 1); }
+          if (blk == 1) { issue_piece(5, st ^ 1); issue_piece(6, st ^ 1); }
+          if (blk >= 2 && blk <= 4) issue_piece(blk - 2, st ^ 1);
+        }
+        if (kShortHead && more) {
+          if (blk == 5) {
+            asm volatile("s_waitcnt vmcnt(3)" ::: "memory");   // this wave's x pieces of the next chunk have landed
+            read_a(0, st ^ 1);
+            read_a(1, st ^ 1);
+          }
+          if (blk == 6) { split_a(0, 0); split_a(0, 1); }
+          if (blk == 7) { split_a(0, 2); split_a(0, 3); }
+        }
         __builtin_amdgcn_sched_barrier(0);
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's pieces of the next chunk have landed
@@ -273,11 +311,9 @@ int launch_linear_split(const LinSplitArgs &a, hipStream_t stream) {
     return DCL_EINVAL;
   }
   constexpr size_t lds = (size_t)2 * kSpST + (EPI == 1 ? (kSpBM + 4 * kSpBN) * sizeof(float) : 0);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void *)k_linear_split<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
+  // (on every launch, as the attention does: the attribute belongs to the current device's copy of the kernel, which a
+  //  once-per-process flag would leave unset on every device after the first)
+  (void)hipFuncSetAttribute((const void *)k_linear_split<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL((k_linear_split<EPI>), dim3((unsigned)tiles), dim3(256), lds, stream, a);
   return 0;
 }
