@@ -49,6 +49,12 @@ def _open(path):
     L.dcl_conf_pool_cm_bwd_ws_bytes.argtypes = [i] * 4 + [C.POINTER(C.c_int64)]
     L.dcl_conf_pool_cm_bwd.argtypes = [i] * 4 + [vp] * 11 + [i64, vp]
     L.dcl_conf_pool_cm_bwd_host.argtypes = [i] * 4 + [vp] * 10
+    # csrc/conf_pool_pm.hip: the channel-major set's argument lists
+    L.dcl_conf_pool_pm_fwd.argtypes = [i] * 4 + [vp] * 5
+    L.dcl_conf_pool_pm_fwd_host.argtypes = [i] * 4 + [vp] * 4
+    L.dcl_conf_pool_pm_bwd_ws_bytes.argtypes = [i] * 4 + [C.POINTER(C.c_int64)]
+    L.dcl_conf_pool_pm_bwd.argtypes = [i] * 4 + [vp] * 11 + [i64, vp]
+    L.dcl_conf_pool_pm_bwd_host.argtypes = [i] * 4 + [vp] * 10
     # csrc/bn_relu.hip: int64 row counts, and eps / momentum as C floats
     f = C.c_float
     L.dcl_bn_relu_ws_bytes.argtypes = [i64, i, C.POINTER(C.c_int64)]
@@ -59,7 +65,8 @@ def _open(path):
     for fn in (L.dcl_linear_wgrad_splits, L.dcl_linear_wgrad, L.dcl_relu_bwd, L.dcl_sparse_conv_dgrad,
                L.dcl_sparse_conv_dgrad_host, L.dcl_conf_pool_cm_fwd, L.dcl_conf_pool_cm_fwd_host,
                L.dcl_conf_pool_cm_bwd_ws_bytes, L.dcl_conf_pool_cm_bwd, L.dcl_conf_pool_cm_bwd_host,
-               L.dcl_bn_relu_ws_bytes, L.dcl_bn_relu_fwd, L.dcl_bn_relu_fwd_host, L.dcl_bn_relu_bwd, L.dcl_bn_relu_bwd_host):
+               L.dcl_conf_pool_pm_fwd, L.dcl_conf_pool_pm_fwd_host, L.dcl_conf_pool_pm_bwd_ws_bytes, L.dcl_conf_pool_pm_bwd,
+               L.dcl_conf_pool_pm_bwd_host, L.dcl_bn_relu_ws_bytes, L.dcl_bn_relu_fwd, L.dcl_bn_relu_fwd_host, L.dcl_bn_relu_bwd, L.dcl_bn_relu_bwd_host):
         fn.restype = i
     return L
 

@@ -5,7 +5,8 @@ forward = the inference kernels, backward = csrc/backward.hip; and of the corres
 forward = dcl_cross_attention, backward = csrc/attention_bwd.hip), which the reference forms from bmm and softmax;
 and of the losses' Chamfer distance (ChamferFn: csrc/chamfer.hip in both passes); and of the rotation head's projection
 (Ortho9dFn: forward = dcl_ortho9d_to_matrix, backward = csrc/rotation_grad.hip); and of the stage-2 refiner's shared MLP
-(RefinerShareFn: forward = the own GEMM core, backward = csrc/linear_bwd.hip + the same core).
+(RefinerShareFn: forward = the own GEMM core, backward = csrc/linear_bwd.hip + the same core); and of the point-major dense
+half of stage 1 (PointLinearFn: the same core and csrc/linear_bwd.hip per layer; ConfPoolPmFn: csrc/conf_pool_pm.hip).
 Used by the module mirrors (spconv/, libs/) so that `Network(cfg, mode='train')` is trainable on the GPU."""
 import torch
 from torch.autograd import Function
@@ -397,15 +398,17 @@ class BnReluFn(Function):
     ops.bn_relu_backward.  Saved: x, gamma, beta, mean, invstd -- not y or z: the ReLU mask is recomputed from x by the same
     expression, hence with the same bits.  Every sum is float64 in a pinned order
     (include/dclnet_hip.h): the same inputs give the same bits.  Only the gradients that are asked for are computed.  CUDA
-    tensors only."""
+    tensors only.  A trailing relu=False gives the BatchNorm alone (the dense half's Conv -> ReLU -> BN fusers,
+    train_dense="point_major"): the kernels take the flag, and nothing else changes."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps):
+    def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps, relu=True):
         if not (x.is_cuda and gamma.is_cuda and beta.is_cuda):
             raise RuntimeError("BnReluFn (train_norm='fused') runs on the GPU only: got %s / %s / %s tensors; the 'modules' "
                                "composition serves CPU tensors" % (x.device, gamma.device, beta.device))
         x, gamma, beta = _ops.N.f32c(x), _ops.N.f32c(gamma), _ops.N.f32c(beta)
-        z, mean, invstd = _ops.bn_relu(x, gamma, beta, running_mean, running_var, momentum, eps)
+        ctx.relu = bool(relu)
+        z, mean, invstd = _ops.bn_relu(x, gamma, beta, running_mean, running_var, momentum, eps, relu=ctx.relu)
         ctx.save_for_backward(x, gamma, beta, mean, invstd)
         return z
 
@@ -416,7 +419,112 @@ class BnReluFn(Function):
         need = ctx.needs_input_grad
         need_x, need_affine = need[0], need[1] or need[2]
         if not (need_x or need_affine):
-            return (None,) * 7
+            return (None,) * 8
         g = _ops.N.f32c(g)
-        dx, dgamma, dbeta = _ops.bn_relu_backward(x, gamma, beta, mean, invstd, g, need_x=need_x, need_affine=need_affine)
-        return dx, dgamma if need[1] else None, dbeta if need[2] else None, None, None, None, None
+        dx, dgamma, dbeta = _ops.bn_relu_backward(x, gamma, beta, mean, invstd, g, relu=ctx.relu, need_x=need_x,
+                                                  need_affine=need_affine)
+        return dx, dgamma if need[1] else None, dbeta if need[2] else None, None, None, None, None, None
+
+
+class ConfPoolPmFn(Function):
+    """ConfPoolFn on point-major activations (train_dense="point_major"): apply(logit1 (b,n1) or (b,1,n1), logit2 (b,n2) or
+    (b,1,n2), F1 (b n1, C), F2 (b n2, C)) -> (conf (b, n1+n2) = sigmoid(cat[logit1, logit2]), pooled (b,C) = sum_j
+    softmax(conf)[j] F[j][c]); crop i owns rows i n .. i n + n - 1 of F.  Forward = ops.conf_softmax, so a train-mode conf is the
+    eval kernel's bit for bit, and ops.conf_pool_pm; backward = ops.conf_pool_pm_backward.  Neither pass makes cat[F1, F2], the
+    weighted product or anything else of F's size; only the gradients that are asked for are computed.  Saved: conf, w, F1, F2.
+    Every sum has a pinned order (include/dclnet_hip.h): the same inputs give the same bits.  CUDA tensors only."""
+
+    @staticmethod
+    def forward(ctx, logit1, logit2, F1, F2):
+        if not (logit1.is_cuda and logit2.is_cuda and F1.is_cuda and F2.is_cuda):
+            raise RuntimeError("ConfPoolPmFn (train_dense='point_major') runs on the GPU only: got %s / %s / %s / %s tensors; the "
+                               "'modules' composition serves CPU tensors" % (logit1.device, logit2.device, F1.device, F2.device))
+        b = logit1.shape[0]
+        ctx.logit_shapes = (logit1.shape, logit2.shape)
+        logit1, logit2 = _ops.N.f32c(logit1).reshape(b, -1), _ops.N.f32c(logit2).reshape(b, -1)
+        F1, F2 = _ops.N.f32c(F1), _ops.N.f32c(F2)
+        assert F1.dim() == 2 and F2.dim() == 2 and F1.shape[0] == logit1.numel() and F2.shape[0] == logit2.numel(), \
+            (tuple(logit1.shape), tuple(logit2.shape), tuple(F1.shape), tuple(F2.shape))
+        conf, w, _ = _ops.conf_softmax(b, logit1.reshape(-1), logit2.reshape(-1))
+        pooled = _ops.conf_pool_pm(w, F1, F2)
+        ctx.save_for_backward(conf, w, F1, F2)
+        return conf, pooled
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_conf, g_pooled):
+        conf, w, F1, F2 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        need_logits, need_F = need[0] or need[1], need[2] or need[3]
+        if not (need_logits or need_F):
+            return None, None, None, None
+        dl1, dl2, dF1, dF2 = _ops.conf_pool_pm_backward(conf, w, F1, F2, _ops.N.f32c(g_pooled), _ops.N.f32c(g_conf),
+                                                        need_logits=need_logits, need_F=need_F)
+        s1, s2 = ctx.logit_shapes
+        return (dl1.view(s1) if need[0] else None, dl2.view(s2) if need[1] else None,
+                dF1 if need[2] else None, dF2 if need[3] else None)
+
+
+def _rows_dense(t):
+    """a 2-D fp32 tensor whose rows are dense (a column block of a wider matrix stays a view; anything else is copied)"""
+    t = t if t.dtype == torch.float32 else t.float()
+    return t if t.stride(1) == 1 or t.shape[1] == 1 else t.contiguous()
+
+
+class PointLinearFn(Function):
+    """A per-point linear layer (a Conv1d / Conv3d with a 1-sized kernel) of the point-major dense half, trained on the library's
+    own GEMM kernels: apply(x (M,K), W, bias, relu) -> (M,N), W the convolution's weight as registered, (N, K, 1...).  Two forms:
+    (bias=None, relu=False), the layers a BatchNorm follows, and (bias, relu=True); a bias without the ReLU raises ValueError (no
+    layer of this path has one).  Forward = ops.linear_dma(x, W^T, bias, relu); backward = ops.relu_bwd (mask + bias gradient),
+    dW = ops.linear_wgrad(dz, x) viewed to W's shape, dx = ops.linear_dma(dz, W2d) with the registered matrix as the (K', N')
+    operand, as RefinerShareFn does.  The split-bf16 core and the vendor library take no part; a shape linear_dma cannot take
+    (K and N in whole 32-chunks, 16-byte aligned operands and row pitches) raises ValueError.  x and the gradient may be column
+    blocks of wider matrices.  Saved: x, W, and the output when relu is set.  Every reduction has a pinned order: the same inputs
+    give the same gradients bit for bit.  Only the gradients that are asked for are computed."""
+
+    @staticmethod
+    def forward(ctx, x, W, bias, relu):
+        relu = bool(relu)
+        if (bias is None) == relu:
+            raise ValueError("PointLinearFn has two forms, (bias=None, relu=False) and (bias, relu=True): got bias %s, relu=%s"
+                             % ("None" if bias is None else "given", relu))
+        for t in (x, W) + (() if bias is None else (bias,)):
+            if not (t.is_cuda and t.dtype == torch.float32):
+                raise RuntimeError("PointLinearFn runs on float32 CUDA tensors only (got %s on %s)" % (t.dtype, t.device))
+        assert x.dim() == 2 and W.dim() >= 2 and W.numel() == W.shape[0] * W.shape[1] and W.shape[1] == x.shape[1], \
+            (tuple(x.shape), tuple(W.shape))
+        x = _rows_dense(x)
+        W2d = W.contiguous().view(W.shape[0], W.shape[1])
+        Wt = W2d.t().contiguous()
+        if not _ops.linear_dma_ok(x, Wt):
+            raise ValueError("PointLinearFn: linear_dma cannot take x %s (row pitch %d) with W %s: K must be a multiple of 32 and "
+                             "the operands and their row pitches 16-byte aligned" % (tuple(x.shape), x.stride(0), tuple(W.shape)))
+        if W2d.shape[0] % 32:
+            raise ValueError("PointLinearFn: the input gradient runs linear_dma with N = %d as its inner size: N must be a "
+                             "multiple of 32" % W2d.shape[0])
+        y = _ops.linear_dma(x, Wt, None if bias is None else bias.contiguous(), relu)
+        ctx.relu = relu
+        ctx.save_for_backward(x, W, *((y,) if relu else ()))
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, W = ctx.saved_tensors[:2]
+        need = ctx.needs_input_grad
+        if not any(need[:3]):
+            return None, None, None, None
+        g = _rows_dense(g)
+        if g.data_ptr() % 16 or (g.shape[0] > 1 and g.stride(0) % 4):
+            g = g.contiguous()
+        db = None
+        if ctx.relu:
+            dz, db = _ops.relu_bwd(ctx.saved_tensors[2], g)
+        else:
+            dz = g
+        dW = _ops.linear_wgrad(dz, x).view_as(W) if need[1] else None
+        dx = None
+        if need[0]:
+            W2d = W.contiguous().view(W.shape[0], W.shape[1])
+            dx = _ops.linear_dma(dz, W2d)
+        return dx, dW, db if need[2] else None, None

@@ -140,3 +140,22 @@ CPG_HD float cpg_dlogit(float w, float d, float dot, const float *g_conf_j, floa
 }
 
 static inline int cpg_nchunks(int c) { return (c + kCpgChunk - 1) / kCpgChunk; }
+
+// ---- the per-crop rest (dot, ds, dlogit), shared with the point-major pooling (conf_pool_pm.hip) ------------------------------
+// host: one crop's rows of w, d, conf, g_conf (may be NULL) and of the two outputs
+inline void cpg_logits_crop_host(int n1, int n2, const float *w, const float *d, const float *conf, const float *g_conf,
+                                 float *dlogit1, float *dlogit2) {
+  const int L = n1 + n2;
+  float slot[kCpgDotLanes];
+  for (int l = 0; l < kCpgDotLanes; ++l) slot[l] = cpg_dot_lane(w, d, L, l);
+  const float dot = cpg_dot_tree_host(slot);
+  for (int j = 0; j < L; ++j) {
+    const float v = cpg_dlogit(w[j], d[j], dot, g_conf ? g_conf + j : nullptr, conf[j]);
+    if (j < n1) dlogit1[j] = v;
+    else dlogit2[j - n1] = v;
+  }
+}
+// device: launches k_cpg_logits (conf_pool_grad.hip), one workgroup per crop, on `stream` (a hipStream_t).  part: the chunks'
+// partials of d, (b, nchunks, L), folded into d first; NULL: d (b, L) holds its values already.
+void cpg_launch_logits(int b, int n1, int n2, int nchunks, const float *conf, const float *w, const float *part, float *d,
+                       const float *g_conf, float *dlogit1, float *dlogit2, void *stream);

@@ -128,10 +128,11 @@ __global__ __launch_bounds__(kLogitThreads) void k_cpg_logits(int n1, int n2, in
   __shared__ float red[kCpgDotLanes];
   const int tid = threadIdx.x, L = n1 + n2;
   const size_t crop = blockIdx.x, row = crop * (size_t)L;
-  const float *wr = w + row, *pr = part + crop * (size_t)nchunks * L;
+  const float *wr = w + row, *pr = part ? part + crop * (size_t)nchunks * L : nullptr;
   float *dr = d + row;
-  for (int j = tid; j < L; j += kLogitThreads) dr[j] = cpg_d_fold(pr + j, (size_t)L, nchunks);
-  __syncthreads();                                           // d goes through memory: the dot's lanes read other threads' columns
+  if (part)                                                  // NULL: the caller left d's values in place (conf_pool_pm.hip)
+    for (int j = tid; j < L; j += kLogitThreads) dr[j] = cpg_d_fold(pr + j, (size_t)L, nchunks);
+  __syncthreads();                                          // d goes through memory: the dot's lanes read other threads' columns
   if (tid < kCpgDotLanes) red[tid] = cpg_dot_lane(wr, dr, L, tid);
   __syncthreads();
   for (int s = kCpgDotLanes / 2; s >= 1; s >>= 1) {
@@ -162,6 +163,12 @@ inline bool cpg_bwd_outputs_ok(const float *dlogit1, const float *dlogit2, const
 }
 
 }  // namespace
+
+void cpg_launch_logits(int b, int n1, int n2, int nchunks, const float *conf, const float *w, const float *part, float *d,
+                       const float *g_conf, float *dlogit1, float *dlogit2, void *stream) {
+  hipLaunchKernelGGL(k_cpg_logits, dim3(b), dim3(kLogitThreads), 0, (hipStream_t)stream, n1, n2, nchunks, conf, w, part, d, g_conf,
+                     dlogit1, dlogit2);
+}
 
 DCL_API int dcl_conf_pool_cm_fwd(int b, int c, int n1, int n2, const float *w, const float *F1, const float *F2,
                                  float *pooled, dclStream_t stream) {
@@ -215,8 +222,7 @@ DCL_API int dcl_conf_pool_cm_bwd(int b, int c, int n1, int n2, const float *conf
   if (dlogit1) {
     float *part = (float *)ws, *d = part + (size_t)b * nchunks * ((size_t)n1 + n2);
     hipLaunchKernelGGL(k_cpg_d, grid, dim3(256), 0, s, c, n1, n2, t1, t2, nchunks, F1, F2, g_pooled, part);
-    hipLaunchKernelGGL(k_cpg_logits, dim3(b), dim3(kLogitThreads), 0, s, n1, n2, nchunks, conf, w, (const float *)part, d,
-                       g_conf, dlogit1, dlogit2);
+    cpg_launch_logits(b, n1, n2, nchunks, conf, w, part, d, g_conf, dlogit1, dlogit2, s);
   }
   if (dF1) {
     const int ngroups = dcl_div_up(c, kDFRows);
@@ -247,15 +253,8 @@ DCL_API int dcl_conf_pool_cm_bwd_host(int b, int c, int n1, int n2, const float 
         }
       }
       for (int j = 0; j < L; ++j) d[j] = cpg_d_fold(part.data() + j, (size_t)L, nchunks);
-      float slot[kCpgDotLanes];
-      for (int l = 0; l < kCpgDotLanes; ++l) slot[l] = cpg_dot_lane(wr, d.data(), L, l);
-      const float dot = cpg_dot_tree_host(slot);
-      for (int j = 0; j < L; ++j) {
-        const size_t r = (size_t)crop * L + j;
-        const float v = cpg_dlogit(wr[j], d[j], dot, g_conf ? g_conf + r : nullptr, conf[r]);
-        if (j < n1) dlogit1[(size_t)crop * n1 + j] = v;
-        else dlogit2[(size_t)crop * n2 + (j - n1)] = v;
-      }
+      cpg_logits_crop_host(n1, n2, wr, d.data(), conf + (size_t)crop * L, g_conf ? g_conf + (size_t)crop * L : nullptr,
+                           dlogit1 + (size_t)crop * n1, dlogit2 + (size_t)crop * n2);
     }
     if (dF1)
       for (int ch = 0; ch < c; ++ch) {

@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..autograd import ConfPoolFn, CrossAttentionFn, Ortho9dFn
+from ..autograd import BnReluFn, ConfPoolFn, ConfPoolPmFn, CrossAttentionFn, Ortho9dFn, PointLinearFn
 from .. import spconv
 from ..libs.pointgroup_ops.functions import pointgroup_ops
 from .losses import losses  # noqa: F401  (reference: models/DCL_Net.py::losses)
@@ -58,6 +58,18 @@ def check_train_rotation(train_rotation):
 
 TRAIN_POOL_MODES = ("modules", "fused")
 TRAIN_NORM_MODES = ops.TRAIN_NORM_MODES
+
+
+TRAIN_DENSE_MODES = ("modules", "point_major")
+
+
+def check_train_dense(train_dense, train_attention):
+    if train_dense not in TRAIN_DENSE_MODES:
+        raise ValueError('train_dense must be "modules" or "point_major", got %r' % (train_dense,))
+    if train_dense == "point_major" and train_attention != "fused":
+        raise ValueError('train_dense="point_major" requires train_attention="fused" (the materialised Aligner is channel-major '
+                         'by construction), got train_attention=%r' % (train_attention,))
+    return train_dense
 
 
 def check_train_pool(train_pool):
@@ -96,7 +108,7 @@ class Network(nn.Module):
     def __init__(self, cfg, mode="train", fused=True, graph_max_batch=8, async_inputs=False, graph_max_points=98304,
                  single_stream=False, pipeline_chunks=1, capture_graph=True, pair_features=None,
                  train_attention="materialised", train_rotation="host", train_conv_wgrad="rows",
-                 train_conv_dgrad="conv", train_pool="modules", train_norm="modules"):
+                 train_conv_dgrad="conv", train_pool="modules", train_norm="modules", train_dense="modules"):
         """graph_max_batch > 0 (default 8): eval-mode calls with at most that many crops go through forward_graphed (one
         whole-forward hipGraph per batch size, captured on first use) -- the one-image-at-a-time eval loops of the
         reference (tools/test_LM.py:104-112: one object per call) are launch-bound otherwise: 0.53 instead of 1.1 ms
@@ -146,6 +158,18 @@ class Network(nn.Module):
         sums in float64 in a pinned chunk order (no atomics: a backbone's forward and backward repeat bit for bit), the running
         statistics updated by the same launches, the ReLU mask recomputed in the backward instead of kept.  Same parameters,
         buffers and state_dict keys; eval mode, the fused inference pipeline, the graphs and the dense half never read it.
+        train_dense: how a train-mode forward of the same path runs the dense half, from the read-out's (b n, 480) point features
+        to the pooled descriptor.  "modules" (default) = the channel-major nn modules on (b, C, n) activations, whose 1x1
+        convolutions are torch.matmul calls.  "point_major" = the same parameters on (b n, C) matrices that are never transposed
+        (_dense_point_major): every wide layer is an autograd.PointLinearFn on the library's own GEMM kernels, every BatchNorm an
+        autograd.BnReluFn (the four first disengage layers of a side as ONE 480 -> 1024 GEMM + one BatchNorm over 1024 channels,
+        as the eval pipeline lays them out), the attention a CrossAttentionFn on views, the pooling an autograd.ConfPoolPmFn
+        (csrc/conf_pool_pm.hip).  Only the heads' last layers (1, 3 or 9 columns) and the b-row pose heads stay
+        torch.nn.functional.linear / modules: the only vendor GEMMs left.  It requires train_attention="fused" (ValueError
+        otherwise) and does NOT read train_pool: its pooling is always ConfPoolPmFn.  Same parameters, buffers and state_dict
+        keys; running statistics and num_batches_tracked are updated as the modules would.  Read only by train-mode forwards of
+        the module path: eval mode (a fused=False instance included, whose BatchNorms use running statistics), the fused
+        inference pipeline and the graphs never read it.
         These are constructor arguments on purpose: nothing on the call path reads the environment."""
         super().__init__()
         self.train_pool = check_train_pool(train_pool)
@@ -156,6 +180,7 @@ class Network(nn.Module):
         if train_attention not in ("materialised", "fused"):
             raise ValueError('train_attention must be "materialised" or "fused", got %r' % (train_attention,))
         self.train_attention = train_attention
+        self.train_dense = check_train_dense(train_dense, train_attention)
         self.single_stream = bool(single_stream)
         self._pair_features = pair_features              # both backbones' layers as ONE launch each; None = automatic (see property)
         self.pipeline_chunks = int(pipeline_chunks)
@@ -1007,8 +1032,21 @@ class Network(nn.Module):
         dev = self.regressor_rot.layers[0].weight.device
         if dev.type != "cuda":
             raise RuntimeError("dcl-net_amd.Network runs on the GPU only: call .cuda() first (no CPU fallback)")
-        vlim = np.asarray(data["voxel_num_limit"]).astype(np.int64)
         b = int(data["batch_offsets"].size(0)) - 1
+        F_Xc, points_inp, F_Yo, points_tmp = self._readout_compat(data, dev, b)
+        sym_flag = data["flags"].to(dev) if self.mode != "test" else None
+        if self.train_dense == "point_major" and self.training:
+            prediction = self._dense_point_major(F_Xc, F_Yo, b, sym_flag)
+        else:
+            prediction = self._dense_modules(F_Xc, F_Yo, b, sym_flag)
+        data["labels"]["points_tmp"] = points_tmp
+        data["labels"]["points_inp"] = points_inp
+        return prediction
+
+    def _readout_compat(self, data, dev, b):
+        """the sparse half of the module path: voxelisation, the two backbones and the multi-scale read-out -> each side's
+        point-major (b n, 480) feature matrix and its (b, n, 3) points"""
+        vlim = np.asarray(data["voxel_num_limit"]).astype(np.int64)
         out = {}
         for side, bb, n in (("inp", self.backbone_inp, self.n_inp), ("tmp", self.backbone_tmp, self.n_tmp)):
             feats = data[side]["feats"].to(dev).float().contiguous()
@@ -1019,9 +1057,13 @@ class Network(nn.Module):
             points = feats[:, 4:].reshape(b, n, 3).reshape(-1, 3)
             bids = torch.arange(b, device=dev).unsqueeze(1).repeat(1, n).view(-1, 1)
             F = self.stage1_get_point_feats(points, bids, *levels)
-            out[side] = (F.view(b, n, -1).transpose(1, 2)[:, :, :, None, None], points.view(b, n, 3))
-        F_Xc, points_inp = out["inp"]
-        F_Yo, points_tmp = out["tmp"]
+            out[side] = (F, points.view(b, n, 3))
+        return out["inp"] + out["tmp"]
+
+    def _dense_modules(self, F_Xc, F_Yo, b, sym_flag):
+        """the dense half on the channel-major nn modules (train_dense="modules")"""
+        F_Xc = F_Xc.view(b, self.n_inp, -1).transpose(1, 2)[:, :, :, None, None]
+        F_Yo = F_Yo.view(b, self.n_tmp, -1).transpose(1, 2)[:, :, :, None, None]
 
         def dis(name, x):
             return getattr(self, name)(x).squeeze(-1).squeeze(-1)
@@ -1055,11 +1097,97 @@ class Network(nn.Module):
         trans_pred = self.regressor_trans(F_p_wei).squeeze(-1)
         prediction = {"trans_pred": trans_pred, "rot_pred": rot_pred, "conf": conf.squeeze(1), "F_Xo_p": F_Xo_p}
         if self.mode != "test":
-            prediction["sym_flag"] = data["flags"].to(dev)
+            prediction["sym_flag"] = sym_flag
             prediction["Xo_pred"] = self.regressor_Xo(F_Xo_p).transpose(1, 2)
             prediction["Yc_pred"] = self.regressor_Yc(F_Yc_p).transpose(1, 2)
-        data["labels"]["points_tmp"] = points_tmp
-        data["labels"]["points_inp"] = points_inp
+        return prediction
+
+    # -------- the point-major dense half (train_dense="point_major"): the same parameters on (b n, C) matrices
+    @staticmethod
+    def _pm_norm(x, bns, relu):
+        """train-mode BatchNorm (+ ReLU) of x (rows, C) by the BatchNorm modules `bns`, which own x's column blocks in order: one
+        BnReluFn over all of them (BatchNorm is per channel: the concatenation is exact), their running statistics updated in
+        place and their num_batches_tracked incremented, as the modules' own forwards would"""
+        for bn in bns:
+            assert bn.affine and bn.track_running_stats and isinstance(bn.momentum, float) and \
+                (bn.momentum, bn.eps) == (bns[0].momentum, bns[0].eps), "point_major: a plain BatchNorm with a float momentum"
+        one = len(bns) == 1
+        gamma, beta = (bns[0].weight, bns[0].bias) if one else (torch.cat([m.weight for m in bns]), torch.cat([m.bias for m in bns]))
+        rm, rv = (bns[0].running_mean, bns[0].running_var) if one else \
+            (torch.cat([m.running_mean for m in bns]), torch.cat([m.running_var for m in bns]))
+        z = BnReluFn.apply(x, gamma, beta, rm, rv, bns[0].momentum, bns[0].eps, relu)
+        with torch.no_grad():
+            c0 = 0
+            for m in bns:
+                c = m.num_features
+                if not one:
+                    m.running_mean.copy_(rm[c0:c0 + c])
+                    m.running_var.copy_(rv[c0:c0 + c])
+                m.num_batches_tracked.add_(1)
+                c0 += c
+        return z
+
+    def _pm_disengage(self, side, F):
+        """one side's four disengage stacks on F (b n, 480): ONE PointLinearFn with the four first-layer weights concatenated
+        to (1024, 480) and one BatchNorm + ReLU over the 1024 channels (the eval pipeline's layout, _disengage), then the four
+        second layers on the hidden matrix's column blocks -> {"p1": (M,256), "m1": (M,64), "p2": (M,256), "m2": (M,64)}"""
+        names = ("p1", "m1", "p2", "m2")
+        stacks = [getattr(self, "disengage_%s_%s" % (side, t)) for t in names]
+        first = [st[0].layers for st in stacks]
+        assert all(l[0].bias is None for l in first)
+        h = PointLinearFn.apply(F, torch.cat([l[0].weight for l in first], dim=0), None, False)
+        h = self._pm_norm(h, [l[1] for l in first], True)
+        out, c0 = {}, 0
+        for t, st in zip(names, stacks):
+            conv, bn = st[1].layers[0], st[1].layers[1]
+            assert conv.bias is None
+            c = conv.in_channels
+            out[t] = self._pm_norm(PointLinearFn.apply(h[:, c0:c0 + c], conv.weight, None, False), [bn], True)
+            c0 += c
+        return out
+
+    def _pm_fuser(self, fuser, x):
+        """a neck fuser, three times Conv1d -> ReLU -> BatchNorm1d, on x (M, 512): PointLinearFn(relu) + BatchNorm without ReLU"""
+        layers = fuser.layers
+        for i in range(0, len(layers), 3):
+            x = self._pm_norm(PointLinearFn.apply(x, layers[i].weight, layers[i].bias, True), [layers[i + 2]], False)
+        return x
+
+    @staticmethod
+    def _pm_head(head, x):
+        """a per-point head, Conv1d -> ReLU -> Conv1d -> ReLU -> Conv1d, on x (M, K): the two wide layers on PointLinearFn, the
+        last one (1 or 3 columns) torch.nn.functional.linear on the same parameters"""
+        c0, c1, c2 = head.layers[0], head.layers[2], head.layers[4]
+        h = PointLinearFn.apply(x, c0.weight, c0.bias, True)
+        h = PointLinearFn.apply(h, c1.weight, c1.bias, True)
+        return torch.nn.functional.linear(h, c2.weight.view(c2.out_channels, c2.in_channels), c2.bias)
+
+    def _dense_point_major(self, F_Xc, F_Yo, b, sym_flag):
+        """the dense half on point-major matrices: F_Xc (b n_inp, 480), F_Yo (b n_tmp, 480) as the read-out leaves them; no
+        transposes, the only copies are the four channel concatenations (torch.cat on (M, .) matrices)"""
+        n_inp, n_tmp = self.n_inp, self.n_tmp
+        Xc, Yo = self._pm_disengage("Xc", F_Xc), self._pm_disengage("Yo", F_Yo)
+
+        def att(q, nq, k, v, nk):                     # (b n, C) matrices as (b, n, C) views; the keys are the second values
+            kv = k.view(b, nk, -1)
+            o1, o2 = CrossAttentionFn.apply(q.view(b, nq, -1), kv, v.view(b, nk, -1), kv)
+            return o1.view(b * nq, -1), o2.view(b * nq, -1)
+        F_Xo_p, F_Xo_m = att(Xc["m1"], n_inp, Yo["m1"], Yo["p1"], n_tmp)
+        F_Yc_p, F_Yc_m = att(Yo["m2"], n_tmp, Xc["m2"], Xc["p2"], n_inp)
+        conf_1 = self._pm_head(self.regressor_conf, torch.cat([Xc["m1"], F_Xo_m], dim=1)).view(b, n_inp)
+        conf_2 = self._pm_head(self.regressor_conf_bi, torch.cat([F_Yc_m, Yo["m2"]], dim=1)).view(b, n_tmp)
+        conf, pooled = ConfPoolPmFn.apply(conf_1, conf_2, self._pm_fuser(self.neck_fuser, torch.cat([Xc["p1"], F_Xo_p], dim=1)),
+                                          self._pm_fuser(self.neck_fuser_bi, torch.cat([F_Yc_p, Yo["p2"]], dim=1)))
+        F_p_wei = pooled.unsqueeze(2)
+        o9 = self.regressor_rot(F_p_wei).squeeze(-1)
+        rot_pred = ortho9d2matrix(o9[:, :3], o9[:, 3:6], o9[:, 6:], self.train_rotation)
+        trans_pred = self.regressor_trans(F_p_wei).squeeze(-1)
+        prediction = {"trans_pred": trans_pred, "rot_pred": rot_pred, "conf": conf,
+                      "F_Xo_p": F_Xo_p.view(b, n_inp, -1).transpose(1, 2)}
+        if self.mode != "test":
+            prediction["sym_flag"] = sym_flag
+            prediction["Xo_pred"] = self._pm_head(self.regressor_Xo, F_Xo_p).view(b, n_inp, 3)
+            prediction["Yc_pred"] = self._pm_head(self.regressor_Yc, F_Yc_p).view(b, n_tmp, 3)
         return prediction
 
     def _admit_graph(self, b, data):

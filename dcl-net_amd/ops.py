@@ -967,6 +967,86 @@ def conf_pool_cm_backward_host(conf, w, F1, F2, g_pooled, g_conf=None, need_logi
     return _conf_pool_cm_backward(conf, w, F1, F2, g_pooled, g_conf, need_logits, need_F, True)
 
 
+POOL_PM_ROWS = 64              # include/dclnet_hip.h: DCL_POOL_PM_ROWS, the rows per chunk of the point-major pooling's sums
+
+
+def _conf_pool_pm_args(w, F1, F2, host, what):
+    _same_side(host, what, w, F1, F2)
+    assert F1.dim() == 2 and F2.dim() == 2 and F1.shape[1] == F2.shape[1], (tuple(F1.shape), tuple(F2.shape))
+    assert w.dim() == 2, tuple(w.shape)
+    b, c = w.shape[0], F1.shape[1]
+    assert b >= 1 and F1.shape[0] % b == 0 and F2.shape[0] % b == 0, (b, tuple(F1.shape), tuple(F2.shape))
+    n1, n2 = F1.shape[0] // b, F2.shape[0] // b
+    assert tuple(w.shape) == (b, n1 + n2), "w: (b, n1 + n2) = %s wanted, got %s" % ((b, n1 + n2), tuple(w.shape))
+    return b, c, n1, n2, N.f32c(w), N.f32c(F1), N.f32c(F2)
+
+
+def _conf_pool_pm(w, F1, F2, host):
+    what = "conf_pool_pm_host" if host else "conf_pool_pm"
+    b, c, n1, n2, w, F1, F2 = _conf_pool_pm_args(w, F1, F2, host, what)
+    pooled = torch.empty((b, c), dtype=torch.float32, device=F1.device)
+    if host:
+        N.check(N.lib().dcl_conf_pool_pm_fwd_host(b, c, n1, n2, N.ptr(w), N.ptr(F1), N.ptr(F2), N.ptr(pooled)), what)
+    else:
+        N.check(N.lib().dcl_conf_pool_pm_fwd(b, c, n1, n2, N.ptr(w), N.ptr(F1), N.ptr(F2), N.ptr(pooled), N.stream()), what)
+    return pooled
+
+
+def _conf_pool_pm_backward(conf, w, F1, F2, g_pooled, g_conf, need_logits, need_F, host):
+    what = "conf_pool_pm_backward_host" if host else "conf_pool_pm_backward"
+    b, c, n1, n2, w, F1, F2 = _conf_pool_pm_args(w, F1, F2, host, what)
+    _same_side(host, what, conf, g_pooled, g_conf)
+    assert need_logits or need_F
+    assert tuple(conf.shape) == (b, n1 + n2) and tuple(g_pooled.shape) == (b, c), (tuple(conf.shape), tuple(g_pooled.shape))
+    assert g_conf is None or tuple(g_conf.shape) == (b, n1 + n2), tuple(g_conf.shape)
+    conf, g_pooled = N.f32c(conf), N.f32c(g_pooled)
+    g_conf = None if g_conf is None else N.f32c(g_conf)
+    dev = F1.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)                  # noqa: E731
+    dl1, dl2 = (new(b, n1), new(b, n2)) if need_logits else (None, None)
+    dF1, dF2 = (torch.empty_like(F1), torch.empty_like(F2)) if need_F else (None, None)
+    ins = (N.ptr(conf), N.ptr(w), N.ptr(F1), N.ptr(F2), N.ptr(g_pooled), N.ptr(g_conf))
+    outs = (N.ptr(dl1), N.ptr(dl2), N.ptr(dF1), N.ptr(dF2))
+    if host:
+        N.check(N.lib().dcl_conf_pool_pm_bwd_host(b, c, n1, n2, *ins, *outs), what)
+    else:
+        ws, nbytes = None, 0
+        if need_logits:
+            q = C.c_int64(0)
+            N.check(N.lib().dcl_conf_pool_pm_bwd_ws_bytes(b, c, n1, n2, C.byref(q)), "conf_pool_pm_bwd_ws_bytes")
+            nbytes = int(q.value)
+            ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=dev)
+        N.check(N.lib().dcl_conf_pool_pm_bwd(b, c, n1, n2, *ins, *outs, N.ptr(ws), nbytes, N.stream()), what)
+    return dl1, dl2, dF1, dF2
+
+
+def conf_pool_pm(w, F1, F2):
+    """The confidence-weighted pooling on point-major activations (dcl_conf_pool_pm_fwd; csrc/conf_pool_pm.hip): w (b, n1+n2)
+    the softmax weights as conf_softmax leaves them, F1 (b n1, C), F2 (b n2, C) row-major, crop i owning rows i n .. i n + n - 1
+    -> pooled (b,C) = sum_j w[j] F[j][c] over both directions, in the summation order include/dclnet_hip.h pins (chunks of
+    POOL_PM_ROWS rows).  One launch; F is read once and nothing of its size is made (a non-contiguous F is copied first)."""
+    return _conf_pool_pm(w, F1, F2, False)
+
+
+def conf_pool_pm_backward(conf, w, F1, F2, g_pooled, g_conf=None, need_logits=True, need_F=True):
+    """Gradients of sigmoid -> softmax -> conf_pool_pm (dcl_conf_pool_pm_bwd): conf, w (b, n1+n2) as conf_softmax returned them,
+    g_pooled (b,C) and g_conf (b, n1+n2) or None (zero) the upstream gradients of pooled and conf -> (dlogit1 (b,n1), dlogit2
+    (b,n2), dF1 (b n1, C), dF2 (b n2, C)); a pair that is not needed is None and is not computed.  F is read once (for the
+    logits), dF is a pure write; no atomics, every sum in a pinned order: the same inputs give the same bits."""
+    return _conf_pool_pm_backward(conf, w, F1, F2, g_pooled, g_conf, need_logits, need_F, False)
+
+
+def conf_pool_pm_host(w, F1, F2):
+    """conf_pool_pm on CPU tensors: the kernel's routines compiled for the host, in their summation order.  For checking the
+    arithmetic where there is no GPU; no model path calls it."""
+    return _conf_pool_pm(w, F1, F2, True)
+
+
+def conf_pool_pm_backward_host(conf, w, F1, F2, g_pooled, g_conf=None, need_logits=True, need_F=True):
+    """conf_pool_pm_backward on CPU tensors; no model path calls it."""
+    return _conf_pool_pm_backward(conf, w, F1, F2, g_pooled, g_conf, need_logits, need_F, True)
+
+
 BN_ROWS = 256                  # include/dclnet_hip.h: DCL_BN_ROWS, the rows per chunk of the BatchNorm sums
 TRAIN_NORM_MODES = ("modules", "fused")
 

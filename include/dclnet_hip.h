@@ -1043,6 +1043,50 @@ int dcl_conf_pool_cm_bwd_host(int b, int c, int n1, int n2, const float *conf, c
                               const float *F2, const float *g_pooled, const float *g_conf,
                               float *dlogit1, float *dlogit2, float *dF1, float *dF2);
 
+/* ------------------------------------------------------ confidence pooling, point-major, with its gradient ---
+ * The same pooling on POINT-major activations (models/DCL_Net.py: train_dense = "point_major"; csrc/conf_pool_pm.hip,
+ * csrc/conf_pool_pm.h).  All arrays fp32 contiguous: F1 (b n1, c), F2 (b n2, c) row-major, a point's channels contiguous, crop i
+ * owning rows i n1 .. i n1 + n1 - 1 of F1 and likewise of F2; conf and w (b, n1+n2) as dcl_conf_softmax leaves them (direction 1
+ * first), L = n1 + n2.  Any c, n1, n2 >= 1; element offsets are 64-bit.  Per crop, with F = F1 | F2 along j:
+ *   pooled[c] = sum_{j<n1} w[j] F1[j][c] + sum_{j<n2} w[n1+j] F2[j][c]
+ *   d[j]      = sum_c g_pooled[c] F[j][c]
+ *   dot, ds[j], dlogit[j]   as for dcl_conf_pool_cm_bwd above (the same per-crop kernel and host routine)
+ *   dF[j][c]  = g_pooled[c] * w[j]
+ * PINNED ORDER of every sum, a function of c, n1, n2 alone (not of b, of the grid or of a row's alignment); no atomics:
+ *   pooled: each direction's rows are cut into chunks of DCL_POOL_PM_ROWS rows (a direction's last chunk may be short, no chunk
+ *     spans both directions); a chunk of a channel is one fma chain from +0, fma(w[j], F[j][c], p), rows ascending; the chunks
+ *     are added ascending, all of F1's before F2's, from the first chunk's value: ((p_0 + p_1) + p_2) + ...
+ *   d: a row has 256 slots; slot k runs one fma chain from +0, fma(g_pooled[c], F[j][c], s), over channels k, k+256, ...
+ *     ascending (a missing channel adds nothing); slots 4l .. 4l+3 fold as (s0 + s1) + (s2 + s3) into lane value l, and the 64
+ *     lane values by a butterfly with strides 32, 16, ..., 1 (v[l] = v[l] + v[l ^ stride]).
+ *   dot: as above (256 lanes, tree with strides 128, ..., 1).
+ * 16-byte and float-by-float accesses give the same bits (every channel of pooled and every slot of d has its own chain); the
+ * same inputs give the same bits, and a crop gives the same bits alone as inside a batch.
+ *
+ * dcl_conf_pool_pm_fwd: w, F1, F2 -> pooled (b,c), one launch, F read once; no scratch (the chunks meet in LDS).
+ * dcl_conf_pool_pm_bwd: arguments and rules of dcl_conf_pool_cm_bwd.  The logits' gradient takes three launches (d of each
+ *   direction: F read once; the per-crop rest), dF one streaming write per direction.  ws: scratch of at least
+ *   dcl_conf_pool_pm_bwd_ws_bytes(b, c, n1, n2) bytes (d: b L floats); read only when dlogit1 / dlogit2 are given, otherwise
+ *   it may be NULL.
+ * The *_host entry points run the same routines on HOST pointers, take no scratch and make no GPU call.
+ * All: b < 0, c < 1, n1 < 1, n2 < 1, a NULL required pointer (with b > 0), an incomplete pair of outputs or too small a
+ * ws_bytes return DCL_EINVAL before any GPU call; b == 0 returns 0.                                                      */
+#ifndef DCL_POOL_PM_ROWS
+#define DCL_POOL_PM_ROWS 64        /* rows per chunk of pooled; measured against 16, 32 and 128 (profiles/dense_pm.txt) */
+#endif
+int dcl_conf_pool_pm_fwd(int b, int c, int n1, int n2, const float *w, const float *F1, const float *F2,
+                         float *pooled, dclStream_t stream);
+int dcl_conf_pool_pm_bwd_ws_bytes(int b, int c, int n1, int n2, int64_t *bytes_host);
+int dcl_conf_pool_pm_bwd(int b, int c, int n1, int n2, const float *conf, const float *w, const float *F1,
+                         const float *F2, const float *g_pooled, const float *g_conf,
+                         float *dlogit1, float *dlogit2, float *dF1, float *dF2, void *ws, int64_t ws_bytes,
+                         dclStream_t stream);
+int dcl_conf_pool_pm_fwd_host(int b, int c, int n1, int n2, const float *w, const float *F1, const float *F2,
+                              float *pooled);
+int dcl_conf_pool_pm_bwd_host(int b, int c, int n1, int n2, const float *conf, const float *w, const float *F1,
+                              const float *F2, const float *g_pooled, const float *g_conf,
+                              float *dlogit1, float *dlogit2, float *dF1, float *dF2);
+
 /* ------------------------------------------------------ sparse-conv BatchNorm + ReLU, train mode, with its gradient ---
  * nn.BatchNorm1d -> nn.ReLU on the (rows, c) row-major feature matrix of a sparse tensor, in train mode (models/Modules.py:
  * BasicBlock_SPCONV.norm_form = "fused"; csrc/bn_relu.hip, csrc/bn_relu.h).  x, g, z, dx fp32 contiguous (V = rows, C = c);
