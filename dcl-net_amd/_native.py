@@ -62,6 +62,22 @@ def _open(path):
     L.dcl_bn_relu_fwd_host.argtypes = [i64, i] + [vp] * 3 + [f, f] + [vp] * 5 + [i]
     L.dcl_bn_relu_bwd.argtypes = [i64, i] + [vp] * 6 + [i] + [vp] * 3 + [vp, i64, vp]
     L.dcl_bn_relu_bwd_host.argtypes = [i64, i] + [vp] * 6 + [i] + [vp] * 3
+    # csrc/linear_narrow.hip: an int64 row count and row pitch
+    L.dcl_linear_narrow_fwd.argtypes = [i64, i, i, vp, i64] + [vp] * 4
+    L.dcl_linear_narrow_fwd_host.argtypes = [i64, i, i, vp, i64] + [vp] * 3
+    L.dcl_linear_narrow_bwd_ws_bytes.argtypes = [i64, i, i, C.POINTER(C.c_int64)]
+    L.dcl_linear_narrow_bwd.argtypes = [i64, i, i, vp, i64] + [vp] * 6 + [i64, vp]
+    L.dcl_linear_narrow_bwd_host.argtypes = [i64, i, i, vp, i64] + [vp] * 5
+    # csrc/pose_heads_grad.hip
+    L.dcl_pose_heads_train_fwd.argtypes = [i] * 6 + [vp] * 18
+    L.dcl_pose_heads_train_fwd_host.argtypes = [i] * 6 + [vp] * 17
+    L.dcl_pose_heads_train_bwd_ws_bytes.argtypes = [i] * 6 + [C.POINTER(C.c_int64)]
+    L.dcl_pose_heads_train_bwd.argtypes = [i] * 6 + [vp] * 25 + [i64, vp]
+    L.dcl_pose_heads_train_bwd_host.argtypes = [i] * 6 + [vp] * 24
+    for fn in (L.dcl_linear_narrow_fwd, L.dcl_linear_narrow_fwd_host, L.dcl_linear_narrow_bwd_ws_bytes, L.dcl_linear_narrow_bwd,
+               L.dcl_linear_narrow_bwd_host, L.dcl_pose_heads_train_fwd, L.dcl_pose_heads_train_fwd_host,
+               L.dcl_pose_heads_train_bwd_ws_bytes, L.dcl_pose_heads_train_bwd, L.dcl_pose_heads_train_bwd_host):
+        fn.restype = i
     for fn in (L.dcl_linear_wgrad_splits, L.dcl_linear_wgrad, L.dcl_relu_bwd, L.dcl_sparse_conv_dgrad,
                L.dcl_sparse_conv_dgrad_host, L.dcl_conf_pool_cm_fwd, L.dcl_conf_pool_cm_fwd_host,
                L.dcl_conf_pool_cm_bwd_ws_bytes, L.dcl_conf_pool_cm_bwd, L.dcl_conf_pool_cm_bwd_host,

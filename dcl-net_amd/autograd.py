@@ -6,7 +6,8 @@ forward = dcl_cross_attention, backward = csrc/attention_bwd.hip), which the ref
 and of the losses' Chamfer distance (ChamferFn: csrc/chamfer.hip in both passes); and of the rotation head's projection
 (Ortho9dFn: forward = dcl_ortho9d_to_matrix, backward = csrc/rotation_grad.hip); and of the stage-2 refiner's shared MLP
 (RefinerShareFn: forward = the own GEMM core, backward = csrc/linear_bwd.hip + the same core); and of the point-major dense
-half of stage 1 (PointLinearFn: the same core and csrc/linear_bwd.hip per layer; ConfPoolPmFn: csrc/conf_pool_pm.hip).
+half of stage 1 (PointLinearFn: the same core and csrc/linear_bwd.hip per layer; ConfPoolPmFn: csrc/conf_pool_pm.hip); and of what train_heads="kernels" switches (NarrowLinearFn: csrc/linear_narrow.hip,
+the per-point heads' last layers; PoseHeadsFn: csrc/pose_heads_grad.hip, the two pose heads of stage 1 and stage 2).
 Used by the module mirrors (spconv/, libs/) so that `Network(cfg, mode='train')` is trainable on the GPU."""
 import torch
 from torch.autograd import Function
@@ -528,3 +529,71 @@ class PointLinearFn(Function):
             W2d = W.contiguous().view(W.shape[0], W.shape[1])
             dx = _ops.linear_dma(dz, W2d)
         return dx, dW, db if need[2] else None, None
+
+
+class NarrowLinearFn(Function):
+    """The last layer of a per-point head (1 or 3 output columns, at most ops.NARROW_MAX_N) of the point-major dense half on the
+    library's own streaming kernels (models/DCL_Net.py: train_heads="kernels"; csrc/linear_narrow.hip): apply(x (M,K), W, bias)
+    -> (M,N) = x W^T + bias, W the convolution's weight as registered, (N,K) or (N,K,1...), bias (N,) or None.  Forward =
+    ops.linear_narrow, backward = ops.linear_narrow_backward: x may be a column block of a wider matrix and is read where it
+    lies, no transposed copy of W is made, and the arriving gradient is made dense if it is a view.  Saved: x, W.  Every sum has
+    a pinned order (include/dclnet_hip.h): the same inputs give the same bits.  Only the gradients that are asked for are
+    computed.  CUDA tensors only."""
+
+    @staticmethod
+    def forward(ctx, x, W, bias):
+        for t in (x, W) + (() if bias is None else (bias,)):
+            if not (t.is_cuda and t.dtype == torch.float32):
+                raise RuntimeError("NarrowLinearFn (train_heads='kernels') runs on float32 CUDA tensors only (got %s on %s); the "
+                                   "'modules' composition serves CPU tensors" % (t.dtype, t.device))
+        x = _rows_dense(x)
+        y = _ops.linear_narrow(x, W, bias)
+        ctx.save_for_backward(x, W)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, W = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if not any(need[:3]):
+            return None, None, None
+        dx, dW, db = _ops.linear_narrow_backward(x, W, g.contiguous(), need_x=need[0], need_w=need[1], need_b=need[2])
+        return dx, None if dW is None else dW.view_as(W), db
+
+
+class PoseHeadsFn(Function):
+    """The rotation and the translation head (1024 -> 512 -> 128 -> 9 | 3, Conv1d -> ReLU -> Conv1d -> ReLU -> Conv1d each) on the b
+    pooled rows of a training step, on the library's own kernels (models/DCL_Net.py, models/refiner.py: train_heads="kernels";
+    csrc/pose_heads_grad.hip): apply(x (b,1024), rot W0, b0, W1, b1, W2, b2, trans W0, b0, W1, b1, W2, b2) -> (o9 (b,9), t3 (b,3)),
+    the weights as registered, (out, in, 1), read in that layout: nothing is folded, transposed or cached, so an optimizer step is
+    seen at once.  Forward = ops.pose_heads_train (three launches for both heads), backward = ops.pose_heads_train_backward (at
+    most six).  Saved: x, the parameters, the hidden activations h1 (2,b,512), h2 (2,b,128); the ReLU masks are h > 0.  Every sum
+    has a pinned order (include/dclnet_hip.h): the same inputs give the same bits, and a crop gives the same bits alone as inside
+    a batch.  The train-mode values are NOT the eval kernels' bits (ops.pose_heads reads folded, transposed weights in other slice
+    orders).  Only the gradients that are asked for are computed.  CUDA tensors only."""
+
+    @staticmethod
+    def forward(ctx, x, *params):
+        if len(params) != 12:
+            raise ValueError("PoseHeadsFn.apply(x, rot W0, b0, W1, b1, W2, b2, trans W0, ..., b2): got %d parameters" % len(params))
+        for t in (x,) + params:
+            if not (t.is_cuda and t.dtype == torch.float32):
+                raise RuntimeError("PoseHeadsFn (train_heads='kernels') runs on float32 CUDA tensors only (got %s on %s); the "
+                                   "'modules' composition serves CPU tensors" % (t.dtype, t.device))
+        x = x.contiguous()
+        o9, t3, h1, h2 = _ops.pose_heads_train(x, params)
+        ctx.save_for_backward(x, h1, h2, *params)
+        return o9, t3
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_o9, g_t3):
+        x, h1, h2 = ctx.saved_tensors[:3]
+        params = ctx.saved_tensors[3:]
+        need = ctx.needs_input_grad
+        if not any(need):
+            return (None,) * 13
+        dx, grads = _ops.pose_heads_train_backward(x, params, h1, h2, g_o9.contiguous(), g_t3.contiguous(), need_x=need[0],
+                                                   need_params=tuple(need[1:]))
+        return (dx,) + tuple(None if g is None else g.view_as(p) for g, p in zip(grads, params))

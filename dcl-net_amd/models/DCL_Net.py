@@ -25,7 +25,8 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..autograd import BnReluFn, ConfPoolFn, ConfPoolPmFn, CrossAttentionFn, Ortho9dFn, PointLinearFn
+from ..autograd import (BnReluFn, ConfPoolFn, ConfPoolPmFn, CrossAttentionFn, NarrowLinearFn, Ortho9dFn, PointLinearFn,
+                        PoseHeadsFn)
 from .. import spconv
 from ..libs.pointgroup_ops.functions import pointgroup_ops
 from .losses import losses  # noqa: F401  (reference: models/DCL_Net.py::losses)
@@ -72,6 +73,26 @@ def check_train_dense(train_dense, train_attention):
     return train_dense
 
 
+TRAIN_HEADS_MODES = ops.TRAIN_HEADS_MODES
+
+
+def check_train_heads(train_heads, train_dense):
+    ops.check_train_heads(train_heads)
+    if train_heads == "kernels" and train_dense != "point_major":
+        raise ValueError('train_heads="kernels" requires train_dense="point_major" (the per-point heads\' last layers read '
+                         'point-major activations), got train_dense=%r' % (train_dense,))
+    return train_heads
+
+
+def pose_head_params(rot, trans):
+    """the twelve registered tensors of two pose heads in autograd.PoseHeadsFn's order: rot W0, b0, W1, b1, W2, b2, then trans"""
+    out = []
+    for head in (rot, trans):
+        for i in (0, 2, 4):
+            out += [head.layers[i].weight, head.layers[i].bias]
+    return out
+
+
 def check_train_pool(train_pool):
     if train_pool not in TRAIN_POOL_MODES:
         raise ValueError('train_pool must be "modules" or "fused", got %r' % (train_pool,))
@@ -108,7 +129,8 @@ class Network(nn.Module):
     def __init__(self, cfg, mode="train", fused=True, graph_max_batch=8, async_inputs=False, graph_max_points=98304,
                  single_stream=False, pipeline_chunks=1, capture_graph=True, pair_features=None,
                  train_attention="materialised", train_rotation="host", train_conv_wgrad="rows",
-                 train_conv_dgrad="conv", train_pool="modules", train_norm="modules", train_dense="modules"):
+                 train_conv_dgrad="conv", train_pool="modules", train_norm="modules", train_dense="modules",
+                 train_heads="modules"):
         """graph_max_batch > 0 (default 8): eval-mode calls with at most that many crops go through forward_graphed (one
         whole-forward hipGraph per batch size, captured on first use) -- the one-image-at-a-time eval loops of the
         reference (tools/test_LM.py:104-112: one object per call) are launch-bound otherwise: 0.53 instead of 1.1 ms
@@ -165,11 +187,20 @@ class Network(nn.Module):
         autograd.BnReluFn (the four first disengage layers of a side as ONE 480 -> 1024 GEMM + one BatchNorm over 1024 channels,
         as the eval pipeline lays them out), the attention a CrossAttentionFn on views, the pooling an autograd.ConfPoolPmFn
         (csrc/conf_pool_pm.hip).  Only the heads' last layers (1, 3 or 9 columns) and the b-row pose heads stay
-        torch.nn.functional.linear / modules: the only vendor GEMMs left.  It requires train_attention="fused" (ValueError
+        torch.nn.functional.linear / modules: the only vendor GEMMs left (train_heads="kernels" takes those too).  It requires train_attention="fused" (ValueError
         otherwise) and does NOT read train_pool: its pooling is always ConfPoolPmFn.  Same parameters, buffers and state_dict
         keys; running statistics and num_batches_tracked are updated as the modules would.  Read only by train-mode forwards of
         the module path: eval mode (a fused=False instance included, whose BatchNorms use running statistics), the fused
         inference pipeline and the graphs never read it.
+        train_heads: how a train-mode forward of the point-major dense half runs what train_dense="point_major" leaves to torch.
+        "modules" (default) = torch.nn.functional.linear for the last layer of the four per-point heads and the registered
+        modules for the two b-row pose heads: the vendor GEMMs named above.  "kernels" = the last layers as
+        autograd.NarrowLinearFn (csrc/linear_narrow.hip: x read once, dx a pure stream, no transposed weight) and
+        regressor_rot / regressor_trans as ONE autograd.PoseHeadsFn on the pooled rows (csrc/pose_heads_grad.hip: three
+        launches forward and at most six backward for both heads, the weights read as registered), every sum in a pinned order.
+        It requires train_dense="point_major" (ValueError otherwise).  Same parameters, buffers and state_dict keys, no cached
+        weights; the train-mode pose-head values are not the eval kernels' bits.  Eval mode, the fused pipeline and the graphs
+        never read it.
         These are constructor arguments on purpose: nothing on the call path reads the environment."""
         super().__init__()
         self.train_pool = check_train_pool(train_pool)
@@ -181,6 +212,7 @@ class Network(nn.Module):
             raise ValueError('train_attention must be "materialised" or "fused", got %r' % (train_attention,))
         self.train_attention = train_attention
         self.train_dense = check_train_dense(train_dense, train_attention)
+        self.train_heads = check_train_heads(train_heads, self.train_dense)
         self.single_stream = bool(single_stream)
         self._pair_features = pair_features              # both backbones' layers as ONE launch each; None = automatic (see property)
         self.pipeline_chunks = int(pipeline_chunks)
@@ -1154,18 +1186,23 @@ class Network(nn.Module):
         return x
 
     @staticmethod
-    def _pm_head(head, x):
+    def _pm_head(head, x, kernels=False):
         """a per-point head, Conv1d -> ReLU -> Conv1d -> ReLU -> Conv1d, on x (M, K): the two wide layers on PointLinearFn, the
-        last one (1 or 3 columns) torch.nn.functional.linear on the same parameters"""
+        last one (1 or 3 columns) torch.nn.functional.linear on the same parameters, or, with kernels (train_heads="kernels"),
+        an autograd.NarrowLinearFn on them"""
         c0, c1, c2 = head.layers[0], head.layers[2], head.layers[4]
         h = PointLinearFn.apply(x, c0.weight, c0.bias, True)
         h = PointLinearFn.apply(h, c1.weight, c1.bias, True)
+        if kernels:
+            return NarrowLinearFn.apply(h, c2.weight, c2.bias)
         return torch.nn.functional.linear(h, c2.weight.view(c2.out_channels, c2.in_channels), c2.bias)
 
     def _dense_point_major(self, F_Xc, F_Yo, b, sym_flag):
         """the dense half on point-major matrices: F_Xc (b n_inp, 480), F_Yo (b n_tmp, 480) as the read-out leaves them; no
         transposes, the only copies are the four channel concatenations (torch.cat on (M, .) matrices)"""
         n_inp, n_tmp = self.n_inp, self.n_tmp
+        kernels = self.train_heads == "kernels"
+        head = (lambda h, x: self._pm_head(h, x, True)) if kernels else self._pm_head
         Xc, Yo = self._pm_disengage("Xc", F_Xc), self._pm_disengage("Yo", F_Yo)
 
         def att(q, nq, k, v, nk):                     # (b n, C) matrices as (b, n, C) views; the keys are the second values
@@ -1174,20 +1211,23 @@ class Network(nn.Module):
             return o1.view(b * nq, -1), o2.view(b * nq, -1)
         F_Xo_p, F_Xo_m = att(Xc["m1"], n_inp, Yo["m1"], Yo["p1"], n_tmp)
         F_Yc_p, F_Yc_m = att(Yo["m2"], n_tmp, Xc["m2"], Xc["p2"], n_inp)
-        conf_1 = self._pm_head(self.regressor_conf, torch.cat([Xc["m1"], F_Xo_m], dim=1)).view(b, n_inp)
-        conf_2 = self._pm_head(self.regressor_conf_bi, torch.cat([F_Yc_m, Yo["m2"]], dim=1)).view(b, n_tmp)
+        conf_1 = head(self.regressor_conf, torch.cat([Xc["m1"], F_Xo_m], dim=1)).view(b, n_inp)
+        conf_2 = head(self.regressor_conf_bi, torch.cat([F_Yc_m, Yo["m2"]], dim=1)).view(b, n_tmp)
         conf, pooled = ConfPoolPmFn.apply(conf_1, conf_2, self._pm_fuser(self.neck_fuser, torch.cat([Xc["p1"], F_Xo_p], dim=1)),
                                           self._pm_fuser(self.neck_fuser_bi, torch.cat([F_Yc_p, Yo["p2"]], dim=1)))
-        F_p_wei = pooled.unsqueeze(2)
-        o9 = self.regressor_rot(F_p_wei).squeeze(-1)
+        if kernels:
+            o9, trans_pred = PoseHeadsFn.apply(pooled, *pose_head_params(self.regressor_rot, self.regressor_trans))
+        else:
+            F_p_wei = pooled.unsqueeze(2)
+            o9 = self.regressor_rot(F_p_wei).squeeze(-1)
+            trans_pred = self.regressor_trans(F_p_wei).squeeze(-1)
         rot_pred = ortho9d2matrix(o9[:, :3], o9[:, 3:6], o9[:, 6:], self.train_rotation)
-        trans_pred = self.regressor_trans(F_p_wei).squeeze(-1)
         prediction = {"trans_pred": trans_pred, "rot_pred": rot_pred, "conf": conf,
                       "F_Xo_p": F_Xo_p.view(b, n_inp, -1).transpose(1, 2)}
         if self.mode != "test":
             prediction["sym_flag"] = sym_flag
-            prediction["Xo_pred"] = self._pm_head(self.regressor_Xo, F_Xo_p).view(b, n_inp, 3)
-            prediction["Yc_pred"] = self._pm_head(self.regressor_Yc, F_Yc_p).view(b, n_tmp, 3)
+            prediction["Xo_pred"] = head(self.regressor_Xo, F_Xo_p).view(b, n_inp, 3)
+            prediction["Yc_pred"] = head(self.regressor_Yc, F_Yc_p).view(b, n_tmp, 3)
         return prediction
 
     def _admit_graph(self, b, data):

@@ -37,19 +37,26 @@ class Refiner(nn.Module):
 
     TRAIN_MLP_MODES = ("modules", "kernels")
 
-    def __init__(self, cfg=None, train_rotation="host", train_mlp="modules"):
+    TRAIN_HEADS_MODES = ops.TRAIN_HEADS_MODES
+
+    def __init__(self, cfg=None, train_rotation="host", train_mlp="modules", train_heads="modules"):
         """train_rotation: "host" (default) or "device" -- how a call that needs a gradient differentiates the rotation
         head's projection; see DCL_Net.Network.
         train_mlp: how train() mode runs MLP_share and the pooling.  "modules" (default): the registered nn.Conv1d / nn.ReLU
         modules (vendor GEMMs in both passes).  "kernels": autograd.RefinerShareFn -- the library's own GEMM core forward, its
         own weight-gradient GEMM and ReLU / bias kernels backward, every reduction in a pinned order (DESIGN.md section 9);
-        needs n % 128 == 0 and inputs that do not require grad (ValueError otherwise).  eval() mode is the same either way."""
+        needs n % 128 == 0 and inputs that do not require grad (ValueError otherwise).  eval() mode is the same either way.
+        train_heads: how train() mode runs regressor_rot2 / regressor_trans2, in either train_mlp form.  "modules" (default): the
+        registered modules (vendor GEMMs and element-wise launches on b rows).  "kernels": ONE autograd.PoseHeadsFn on the pooled
+        feature (csrc/pose_heads_grad.hip: three launches forward, at most six backward, the weights read as registered, pinned
+        summation orders).  Same parameters and state_dict keys, no cached weights; eval() mode never reads it."""
         super().__init__()
         from .DCL_Net import check_train_rotation
         self.train_rotation = check_train_rotation(train_rotation)
         if train_mlp not in self.TRAIN_MLP_MODES:
             raise ValueError('train_mlp must be "modules" or "kernels", got %r' % (train_mlp,))
         self.train_mlp = train_mlp
+        self.train_heads = ops.check_train_heads(train_heads)
         self.MLP_share = Head_MultiLayerPerceptron([256 + 3, 512, 512, 1024], ["relu"] * 3, [False] * 3, [0.0] * 3)
         self.regressor_rot2 = Head_MultiLayerPerceptron([1024, 512, 128, 9], ["relu", "relu", "none"], [False] * 3,
                                                         [0.0] * 3)
@@ -134,15 +141,24 @@ class Refiner(nn.Module):
         o9 = head(shared, f["regressor_rot2"])
         return head(shared, f["regressor_trans2"]), ops.ortho9d_to_matrix(o9)
 
+    def _train_heads(self, shared):
+        """the two heads of a train-mode forward on shared (b, 1024, 1) -> the prediction dict"""
+        if self.train_heads == "kernels":
+            from ..autograd import PoseHeadsFn
+            from .DCL_Net import pose_head_params
+            o9, delta_t = PoseHeadsFn.apply(shared.squeeze(2), *pose_head_params(self.regressor_rot2, self.regressor_trans2))
+        else:
+            o9 = self.regressor_rot2(shared).squeeze(-1)
+            delta_t = self.regressor_trans2(shared).squeeze(-1)
+        return {"trans_pred": delta_t, "rot_pred": ortho9d2matrix(o9[:, :3], o9[:, 3:6], o9[:, 6:], self.train_rotation)}
+
     def _forward_modules(self, x, conf):
         """training path (tools/train_YCBV_stage2.py:169,243-262 calls refiner.train(); outputs = refiner(inp);
         loss.backward()): the registered modules composed as the reference composes them (models/refiner.py:78-95), every
         step differentiable, no cached weights."""
         conf_softmax = torch.softmax(conf.unsqueeze(1), dim=2)[:, :, :1024]
         shared = (self.MLP_share(x) * conf_softmax).sum(dim=2, keepdim=True)
-        o9 = self.regressor_rot2(shared).squeeze(-1)
-        delta_t = self.regressor_trans2(shared).squeeze(-1)
-        return {"trans_pred": delta_t, "rot_pred": ortho9d2matrix(o9[:, :3], o9[:, 3:6], o9[:, 6:], self.train_rotation)}
+        return self._train_heads(shared)
 
     def _forward_kernels(self, x, conf):
         """training path with train_mlp="kernels": the shared MLP and the pooling as autograd.RefinerShareFn on point-major
@@ -167,9 +183,7 @@ class Refiner(nn.Module):
         L = self.MLP_share.layers
         shared = RefinerShareFn.apply(xyz_pm, F_pm, conf_w, L[0].weight, L[0].bias, L[2].weight, L[2].bias, L[4].weight,
                                       L[4].bias).unsqueeze(2)
-        o9 = self.regressor_rot2(shared).squeeze(-1)
-        delta_t = self.regressor_trans2(shared).squeeze(-1)
-        return {"trans_pred": delta_t, "rot_pred": ortho9d2matrix(o9[:, :3], o9[:, 3:6], o9[:, 6:], self.train_rotation)}
+        return self._train_heads(shared)
 
     def forward(self, input_dict):
         """reference contract: {"input_features" (b,259,n), "conf" (b,n+m), "obj_idx"} ->

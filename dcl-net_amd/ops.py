@@ -1047,6 +1047,194 @@ def conf_pool_pm_backward_host(conf, w, F1, F2, g_pooled, g_conf=None, need_logi
     return _conf_pool_pm_backward(conf, w, F1, F2, g_pooled, g_conf, need_logits, need_F, True)
 
 
+N_ = N                         # (below, N is a layer's width)
+NARROW_MAX_N = 16              # include/dclnet_hip.h: DCL_NARROW_MAX_N, the widest layer linear_narrow serves
+NARROW_ROWS = 64               # include/dclnet_hip.h: DCL_NARROW_ROWS, the rows per chunk of its dW / db sums
+TRAIN_HEADS_MODES = ("modules", "kernels")
+
+
+def check_train_heads(value, what="train_heads"):
+    if value not in TRAIN_HEADS_MODES:
+        raise ValueError('%s must be "modules" or "kernels", got %r' % (what, value))
+    return value
+
+
+def _narrow_args(x, W, host, what):
+    """x (M,K) fp32 with dense rows (a column block of a wider matrix stays a view), W (N,K) or (N,K,1...) -> M, K, N, x, pitch, W2d"""
+    _same_side(host, what, x, W)
+    assert x.dim() == 2 and W.dim() >= 2 and W.numel() == W.shape[0] * W.shape[1] and W.shape[1] == x.shape[1], \
+        (tuple(x.shape), tuple(W.shape))
+    x = x if x.dtype == torch.float32 else x.float()
+    if x.shape[1] > 1 and x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    M, K = x.shape
+    N = W.shape[0]
+    if not 1 <= N <= NARROW_MAX_N:
+        raise ValueError("%s serves 1 <= N <= %d output columns, got N = %d" % (what, NARROW_MAX_N, N))
+    return M, K, N, x, (x.stride(0) if M > 1 else K), N_.f32c(W).view(N, K)
+
+
+def _linear_narrow(x, W, bias, host):
+    what = "linear_narrow_host" if host else "linear_narrow"
+    M, K, N, x, pitch, W = _narrow_args(x, W, host, what)
+    _same_side(host, what, bias)
+    bias = None if bias is None else N_.f32c(bias)
+    assert bias is None or tuple(bias.shape) == (N,), tuple(bias.shape)
+    y = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    if host:
+        N_.check(N_.lib().dcl_linear_narrow_fwd_host(M, K, N, N_.ptr(x), pitch, N_.ptr(W), N_.ptr(bias), N_.ptr(y)), what)
+    else:
+        N_.check(N_.lib().dcl_linear_narrow_fwd(M, K, N, N_.ptr(x), pitch, N_.ptr(W), N_.ptr(bias), N_.ptr(y), N_.stream()), what)
+    return y
+
+
+def _linear_narrow_backward(x, W, g, need_x, need_w, need_b, host):
+    what = "linear_narrow_backward_host" if host else "linear_narrow_backward"
+    M, K, N, x, pitch, W = _narrow_args(x, W, host, what)
+    _same_side(host, what, g)
+    assert need_x or need_w or need_b
+    assert tuple(g.shape) == (M, N), "g: (M, N) = %s wanted, got %s" % ((M, N), tuple(g.shape))
+    g = N_.f32c(g)
+    dev = x.device
+    # (an empty batch launches nothing: the sums are zero)
+    new = (lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)) if M == 0 else \
+        (lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev))
+    dx, dW, db = new(M, K) if need_x else None, new(N, K) if need_w else None, new(N) if need_b else None
+    if host:
+        N_.check(N_.lib().dcl_linear_narrow_bwd_host(M, K, N, N_.ptr(x), pitch, N_.ptr(W), N_.ptr(g), N_.ptr(dx), N_.ptr(dW),
+                                                     N_.ptr(db)), what)
+    else:
+        ws, nbytes = None, 0
+        if need_w or need_b:
+            q = C.c_int64(0)
+            N_.check(N_.lib().dcl_linear_narrow_bwd_ws_bytes(M, K, N, C.byref(q)), "linear_narrow_bwd_ws_bytes")
+            nbytes = int(q.value)
+            ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=dev)
+        N_.check(N_.lib().dcl_linear_narrow_bwd(M, K, N, N_.ptr(x), pitch, N_.ptr(W), N_.ptr(g), N_.ptr(dx), N_.ptr(dW), N_.ptr(db),
+                                                N_.ptr(ws), nbytes, N_.stream()), what)
+    return dx, dW, db
+
+
+def linear_narrow(x, W, bias=None):
+    """A per-point linear layer with 1 <= N <= NARROW_MAX_N output columns (dcl_linear_narrow_fwd; csrc/linear_narrow.hip):
+    x (M,K) -- dense, or a column block of a wider matrix, served as it lies -- W (N,K) or (N,K,1...) as the convolution registers
+    it, bias (N,) or None -> y (M,N) = x W^T + bias.  One launch, x read once, no transposed copy of W; the summation order
+    include/dclnet_hip.h pins: any pitch and alignment give the same bits."""
+    return _linear_narrow(x, W, bias, False)
+
+
+def linear_narrow_backward(x, W, g, need_x=True, need_w=True, need_b=True):
+    """Gradients of linear_narrow (dcl_linear_narrow_bwd): g (M,N) the upstream gradient -> (dx (M,K), dW (N,K), db (N,)); one that
+    is not needed is None and is not computed.  x and g are read once, dx is a pure streaming write, the dW / db partials of
+    NARROW_ROWS-row chunks are formed in the same pass and added in ascending order by a finish launch; no atomics: the same
+    inputs give the same bits."""
+    return _linear_narrow_backward(x, W, g, need_x, need_w, need_b, False)
+
+
+def linear_narrow_host(x, W, bias=None):
+    """linear_narrow on CPU tensors: the kernel's routines compiled for the host, in their summation order.  For checking the
+    arithmetic where there is no GPU; no model path calls it."""
+    return _linear_narrow(x, W, bias, True)
+
+
+def linear_narrow_backward_host(x, W, g, need_x=True, need_w=True, need_b=True):
+    """linear_narrow_backward on CPU tensors; no model path calls it."""
+    return _linear_narrow_backward(x, W, g, need_x, need_w, need_b, True)
+
+
+POSE_TRAIN_GRADS = ("rW0", "rb0", "rW1", "rb1", "rW2", "rb2", "tW0", "tb0", "tW1", "tb1", "tW2", "tb2")
+
+
+def _pose_train_args(x, params, host, what):
+    """x (b,d0), params = (rW0, rb0, rW1, rb1, rW2, rb2, tW0, ..., tb2) as the convolutions register them -> dims, fp32 contiguous
+    tensors (a contiguous fp32 parameter is used where it lies)"""
+    assert len(params) == 12, len(params)
+    _same_side(host, what, x, *params)
+    x = N_.f32c(x)
+    params = [N_.f32c(p) for p in params]
+    assert x.dim() == 2, tuple(x.shape)
+    b, d0 = x.shape
+    Ws = params[0::2]
+    for Wm, bias in zip(Ws, params[1::2]):
+        assert Wm.dim() >= 2 and Wm.numel() == Wm.shape[0] * Wm.shape[1] and tuple(bias.shape) == (Wm.shape[0],), \
+            (tuple(Wm.shape), tuple(bias.shape))
+    d1, d2, n_rot, n_trans = Ws[0].shape[0], Ws[1].shape[0], Ws[2].shape[0], Ws[5].shape[0]
+    want = [(d1, d0), (d2, d1), (n_rot, d2), (d1, d0), (d2, d1), (n_trans, d2)]
+    assert [tuple(Wm.shape[:2]) for Wm in Ws] == want, ([tuple(Wm.shape) for Wm in Ws], want)
+    return (b, d0, d1, d2, n_rot, n_trans), x, params
+
+
+def _pose_heads_train(x, params, host):
+    what = "pose_heads_train_host" if host else "pose_heads_train"
+    dims, x, params = _pose_train_args(x, params, host, what)
+    b, d0, d1, d2, n_rot, n_trans = dims
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)            # noqa: E731
+    h1, h2, o9, t3 = new(2, b, d1), new(2, b, d2), new(b, n_rot), new(b, n_trans)
+    ptrs = [N_.ptr(t) for t in [x] + params + [h1, h2, o9, t3]]
+    if host:
+        N_.check(N_.lib().dcl_pose_heads_train_fwd_host(*dims, *ptrs), what)
+    else:
+        N_.check(N_.lib().dcl_pose_heads_train_fwd(*dims, *ptrs, N_.stream()), what)
+    return o9, t3, h1, h2
+
+
+def _pose_heads_train_backward(x, params, h1, h2, g_o9, g_t3, need_x, need_params, host):
+    what = "pose_heads_train_backward_host" if host else "pose_heads_train_backward"
+    dims, x, params = _pose_train_args(x, params, host, what)
+    b, d0, d1, d2, n_rot, n_trans = dims
+    _same_side(host, what, h1, h2, g_o9, g_t3)
+    assert g_o9 is not None or g_t3 is not None
+    assert tuple(h1.shape) == (2, b, d1) and tuple(h2.shape) == (2, b, d2), (tuple(h1.shape), tuple(h2.shape))
+    assert g_o9 is None or tuple(g_o9.shape) == (b, n_rot), tuple(g_o9.shape)
+    assert g_t3 is None or tuple(g_t3.shape) == (b, n_trans), tuple(g_t3.shape)
+    if need_params is True or need_params is False:
+        need_params = (bool(need_params),) * 12
+    assert len(need_params) == 12 and (need_x or any(need_params))
+    h1, h2 = N_.f32c(h1), N_.f32c(h2)
+    g_o9, g_t3 = None if g_o9 is None else N_.f32c(g_o9), None if g_t3 is None else N_.f32c(g_t3)
+    new = torch.zeros_like if b == 0 else torch.empty_like                                   # an empty batch launches nothing
+    dx = new(x) if need_x else None
+    grads = [new(p) if need else None for p, need in zip(params, need_params)]
+    ins = [N_.ptr(t) for t in [x] + params[0:6:2] + params[6:12:2] + [h1, h2, g_o9, g_t3]]
+    outs = [N_.ptr(dx)] + [N_.ptr(t) for t in grads]
+    if host:
+        N_.check(N_.lib().dcl_pose_heads_train_bwd_host(*dims, *ins, *outs), what)
+    else:
+        q = C.c_int64(0)
+        N_.check(N_.lib().dcl_pose_heads_train_bwd_ws_bytes(*dims, C.byref(q)), "pose_heads_train_bwd_ws_bytes")
+        nbytes = int(q.value)
+        ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=x.device)
+        N_.check(N_.lib().dcl_pose_heads_train_bwd(*dims, *ins, *outs, N_.ptr(ws), nbytes, N_.stream()), what)
+    return dx, grads
+
+
+def pose_heads_train(x, params):
+    """Both pose heads on the pooled rows of a training step (dcl_pose_heads_train_fwd; csrc/pose_heads_grad.hip): x (b,d0),
+    params = (rW0, rb0, rW1, rb1, rW2, rb2, tW0, tb0, tW1, tb1, tW2, tb2), the rotation then the translation head's weights
+    (out, in[, 1]) and biases as registered -> (o9 (b,n_rot), t3 (b,n_trans), h1 (2,b,d1), h2 (2,b,d2)), the hidden activations
+    for the backward.  Three launches shared by both heads, each weight matrix read once for all b rows; NOT the eval kernels'
+    bits (ops.pose_heads: folded weights, other slice orders)."""
+    return _pose_heads_train(x, params, False)
+
+
+def pose_heads_train_backward(x, params, h1, h2, g_o9, g_t3, need_x=True, need_params=True):
+    """Gradients of pose_heads_train (dcl_pose_heads_train_bwd): g_o9 (b,n_rot) / g_t3 (b,n_trans) the upstream gradients (None =
+    zero, not both) -> (dx (b,d0) or None, [the twelve parameter gradients in POSE_TRAIN_GRADS order, shaped as their parameters,
+    None where need_params -- a bool or twelve of them -- says so]).  At most six launches, the ReLU masks recomputed from h1 / h2,
+    every sum in a pinned order: the same inputs give the same bits."""
+    return _pose_heads_train_backward(x, params, h1, h2, g_o9, g_t3, need_x, need_params, False)
+
+
+def pose_heads_train_host(x, params):
+    """pose_heads_train on CPU tensors, in the kernels' summation orders; no model path calls it."""
+    return _pose_heads_train(x, params, True)
+
+
+def pose_heads_train_backward_host(x, params, h1, h2, g_o9, g_t3, need_x=True, need_params=True):
+    """pose_heads_train_backward on CPU tensors; no model path calls it."""
+    return _pose_heads_train_backward(x, params, h1, h2, g_o9, g_t3, need_x, need_params, True)
+
+
 BN_ROWS = 256                  # include/dclnet_hip.h: DCL_BN_ROWS, the rows per chunk of the BatchNorm sums
 TRAIN_NORM_MODES = ("modules", "fused")
 

@@ -1132,6 +1132,102 @@ int dcl_bn_relu_fwd_host(int64_t rows, int c, const float *x, const float *gamma
 int dcl_bn_relu_bwd_host(int64_t rows, int c, const float *x, const float *gamma, const float *beta, const float *mean,
                          const float *invstd, const float *g, int relu, float *dx, float *dgamma, float *dbeta);
 
+/* ------------------------------------------------------ narrow per-point layer, with its gradients ---
+ * A per-point linear layer with very few output columns -- the last layers (1 or 3 columns) of stage 1's per-point heads -- for
+ * the training path (models/DCL_Net.py: train_heads = "kernels"; csrc/linear_narrow.hip, csrc/linear_narrow.h).  fp32:
+ *   y[m][j]  = sum_k x[m][k] W[j][k] + bias[j]          x (M, K) with a row pitch of x_pitch floats (>= K: a column block of a
+ *   dx[m][k] = sum_j g[m][j] W[j][k]                    wider matrix is served as it lies), W (N, K) as the convolution registers
+ *   dW[j][k] = sum_m g[m][j] x[m][k]                    it (no transposed copy), bias (N) or NULL, y, g (M, N) and dx (M, K)
+ *   db[j]    = sum_m g[m][j]                            dense.  1 <= N <= DCL_NARROW_MAX_N, any K >= 1, any M >= 0.
+ * Nothing needs an alignment; element offsets are 64-bit.  Bandwidth-bound: the forward reads x once, the backward reads x and g
+ * once and writes dx once as a stream, the dW / db partials formed in the same pass.
+ * PINNED ORDER of every sum, a function of (M, K, N) alone (not of the grid, of the pitch or of a pointer's alignment); no atomics:
+ *   y: a row has 64 slots; slot k = 4 l + e of lane l < 16 runs one fma chain from +0, fma(x[m][c], W[j][c], s), over the columns
+ *     k, k+64, k+128, ... ascending (a missing column adds nothing); slots 4l .. 4l+3 fold as (s0 + s1) + (s2 + s3) into lane value
+ *     l, and the 16 lane values by a butterfly with strides 8, 4, 2, 1 (v[l] = v[l] + v[l ^ stride]); then + bias[j].
+ *   dx: one fma chain from +0 over the outputs, fma(g[m][j], W[j][k], d), j ascending.
+ *   dW, db: the rows are cut into chunks of DCL_NARROW_ROWS rows (the last may be short); a chunk of an element is one chain from
+ *     +0, rows ascending -- fma(g[m][j], x[m][k], p) for dW, p + g[m][j] for db; a finish launch adds the chunks ascending from the
+ *     first chunk's value: ((p_0 + p_1) + p_2) + ...
+ * 16-byte and float-by-float accesses give the same bits (every element has its own chain), any pitch and any alignment give the
+ * same bits, and the same inputs give the same bits.
+ *
+ * dcl_linear_narrow_fwd: one launch.
+ * dcl_linear_narrow_bwd: any subset of dx, dW (N, K), db (N) is given, the others NULL; not all NULL.  One launch for dx and
+ *   the partials, one more (the finish) when dW or db is given.  ws: scratch of at least dcl_linear_narrow_bwd_ws_bytes(M, K, N)
+ *   bytes (the chunks' partials), read only when dW or db is given, otherwise it may be NULL.
+ * The *_host entry points run the same routines on HOST pointers, take no scratch and make no GPU call.
+ * All: M < 0, K < 1, N < 1, N > DCL_NARROW_MAX_N, x_pitch < K (with M > 1), a NULL required pointer (with M > 0), no output at
+ * all or too small a ws_bytes return DCL_EINVAL before any GPU call; M == 0 returns 0 and writes nothing.                    */
+#define DCL_NARROW_MAX_N 16        /* widest layer served: the accumulators of all outputs live in registers */
+#ifndef DCL_NARROW_ROWS
+#define DCL_NARROW_ROWS 64         /* rows per chunk of dW / db */
+#endif
+int dcl_linear_narrow_fwd(int64_t M, int K, int N, const float *x, int64_t x_pitch, const float *W, const float *bias,
+                          float *y, dclStream_t stream);
+int dcl_linear_narrow_bwd_ws_bytes(int64_t M, int K, int N, int64_t *bytes_host);
+int dcl_linear_narrow_bwd(int64_t M, int K, int N, const float *x, int64_t x_pitch, const float *W, const float *g,
+                          float *dx, float *dW, float *db, void *ws, int64_t ws_bytes, dclStream_t stream);
+int dcl_linear_narrow_fwd_host(int64_t M, int K, int N, const float *x, int64_t x_pitch, const float *W, const float *bias,
+                               float *y);
+int dcl_linear_narrow_bwd_host(int64_t M, int K, int N, const float *x, int64_t x_pitch, const float *W, const float *g,
+                               float *dx, float *dW, float *db);
+
+/* ------------------------------------------------------ the two pose heads in training, with their gradients ---
+ * The rotation and the translation head on the b pooled rows of a training step (models/DCL_Net.py, models/refiner.py:
+ * train_heads = "kernels"; csrc/pose_heads_grad.hip, csrc/pose_heads_grad.h).  Each head is three layers on x (b, d0):
+ *   h1 = relu(x W0^T + b0) (b, d1),  h2 = relu(h1 W1^T + b1) (b, d2),  out = h2 W2^T + b2 (b, n_rot | n_trans)
+ * with the weights as the convolutions register them -- W0 (d1, d0), W1 (d2, d1), W2 (n, d2), read in that layout, nothing folded
+ * or transposed.  The r.. arguments are the rotation head's, the t.. ones the translation head's.  All arrays fp32 contiguous;
+ * h1 (2, b, d1) and h2 (2, b, d2) hold the rotation head's activations first.  Both heads share every launch, and a weight matrix
+ * is read once per launch for all b rows.  The values are NOT the eval kernels' bits (dcl_pose_heads: folded, transposed weights
+ * and other slice orders).
+ * Accepted: any b >= 0; d0, d1, d2 multiples of 4 in [4, DCL_POSE_TRAIN_MAX_WIDTH] (the model's 1024, 512, 128); 1 <= n_rot,
+ * n_trans <= DCL_POSE_TRAIN_MAX_OUT (the model's 9 and 3); x, the weight matrices, h1, h2, dx, the weight gradients and ws 16-byte
+ * aligned.  Anything else returns DCL_EINVAL.
+ * PINNED ORDER of every sum, a function of the widths alone (not of b, of the grid or of the outputs asked for); no atomics:
+ *   z[r][o]: 256 slots; slot k = 4 l + e of lane l < 64 runs one fma chain from +0, fma(in[r][c], W[o][c], s), over the columns
+ *     k, k+256, ... ascending; slots fold as (s0 + s1) + (s2 + s3), the 64 lane values by a butterfly with strides 32, ..., 1;
+ *     then + bias[o]; relu is z > 0 ? z : 0.
+ *   dW[o][k], db[o]: one chain from +0, rows ascending: fma(dz[r][o], in[r][k], p) and p + dz[r][o].
+ *   input gradients: a layer's outputs are cut into chunks of DCL_POSE_TRAIN_CHUNK (the last may be short); a chunk is one fma
+ *     chain from +0, fma(dz[r][o], W[o][k], p), outputs ascending; the chunks are added ascending from the first chunk's value.
+ *     dz of the layer below = h > 0 ? that sum : 0, the mask recomputed from the stored activation.  dx = R + T: the rotation
+ *     head's sum, then the translation head's.
+ * The same inputs give the same bits, and a crop gives the same o9, t3 and dx bits alone as inside a batch.
+ *
+ * dcl_pose_heads_train_fwd: three launches (one per layer); h1, h2, o9 (b, n_rot) and t3 (b, n_trans) are overwritten.
+ * dcl_pose_heads_train_bwd: g_o9 (b, n_rot) and / or g_t3 (b, n_trans), the upstream gradients; a NULL one is a zero gradient.
+ *   dx (b, d0) and the twelve parameter gradients (shaped as their parameters) may each be NULL, not all of them.  At most six
+ *   launches: per layer one for dW, db and the chunk partials of the input gradient, one that adds the chunks and masks.
+ *   ws: scratch of at least dcl_pose_heads_train_bwd_ws_bytes(...) bytes, always required.
+ * The *_host entry points run the same orders on HOST pointers, take no scratch, need no alignment and make no GPU call.
+ * b == 0 returns 0 and writes nothing; a NULL required pointer, no gradient or no output at all, too small a ws_bytes return
+ * DCL_EINVAL before any GPU call.                                                                                          */
+#define DCL_POSE_TRAIN_MAX_WIDTH 1024   /* a weight row of an output lives in one wave's registers */
+#define DCL_POSE_TRAIN_MAX_OUT 16
+#define DCL_POSE_TRAIN_CHUNK 32         /* outputs per chain of an input gradient: the weight tile of a chunk fills 32 KB of LDS */
+int dcl_pose_heads_train_fwd(int b, int d0, int d1, int d2, int n_rot, int n_trans, const float *x, const float *rW0,
+                             const float *rb0, const float *rW1, const float *rb1, const float *rW2, const float *rb2,
+                             const float *tW0, const float *tb0, const float *tW1, const float *tb1, const float *tW2,
+                             const float *tb2, float *h1, float *h2, float *o9, float *t3, dclStream_t stream);
+int dcl_pose_heads_train_bwd_ws_bytes(int b, int d0, int d1, int d2, int n_rot, int n_trans, int64_t *bytes_host);
+int dcl_pose_heads_train_bwd(int b, int d0, int d1, int d2, int n_rot, int n_trans, const float *x, const float *rW0,
+                             const float *rW1, const float *rW2, const float *tW0, const float *tW1, const float *tW2,
+                             const float *h1, const float *h2, const float *g_o9, const float *g_t3, float *dx, float *d_rW0,
+                             float *d_rb0, float *d_rW1, float *d_rb1, float *d_rW2, float *d_rb2, float *d_tW0, float *d_tb0,
+                             float *d_tW1, float *d_tb1, float *d_tW2, float *d_tb2, void *ws, int64_t ws_bytes,
+                             dclStream_t stream);
+int dcl_pose_heads_train_fwd_host(int b, int d0, int d1, int d2, int n_rot, int n_trans, const float *x, const float *rW0,
+                                  const float *rb0, const float *rW1, const float *rb1, const float *rW2, const float *rb2,
+                                  const float *tW0, const float *tb0, const float *tW1, const float *tb1, const float *tW2,
+                                  const float *tb2, float *h1, float *h2, float *o9, float *t3);
+int dcl_pose_heads_train_bwd_host(int b, int d0, int d1, int d2, int n_rot, int n_trans, const float *x, const float *rW0,
+                                  const float *rW1, const float *rW2, const float *tW0, const float *tW1, const float *tW2,
+                                  const float *h1, const float *h2, const float *g_o9, const float *g_t3, float *dx,
+                                  float *d_rW0, float *d_rb0, float *d_rW1, float *d_rb1, float *d_rW2, float *d_rb2,
+                                  float *d_tW0, float *d_tb0, float *d_tW1, float *d_tb1, float *d_tW2, float *d_tb2);
+
 /* ------------------------------------------------------ optimizer step ---
  * What follows loss.backward() in the reference's training scripts (tools/train_YCBV_stage1.py:119-125, 212-231): the global
  * gradient norm that AutoClip measures, and the Adam update with the clip factor folded in (csrc/optim.hip).  Both calls walk

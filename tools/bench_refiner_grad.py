@@ -18,13 +18,19 @@ Parts, each a process of its own so that a fault in one ends the chain there (ev
   kernels   the library calls of one backward alone (device events) at 20 x 1024 rows, beside torch's matmul / sum
   op        forward + backward of refiner(inp), both forms, at 20 x 1024 (the reference's bs 40 / 2 iterations) and 32 x 1024
   step      a stage-2 step at the same shapes: eval-mode Network forward, two refinement iterations of refiner +
-            losses_refiner(chamfer="fused", objective="fused") + backward, then AutoClip + dcl.optim.Adam
+            losses_refiner(chamfer="fused", objective="fused") + backward, then AutoClip + dcl.optim.Adam; the pose arithmetic
+            between the iterations is ops.rigid_points and broadcast products (no torch.bmm), in every form
   launches  kernel launches of one forward + backward of each form by name (vendor GEMMs are the Cijk_* rows) and the
             peak memory above what was allocated before it
+  trace     13 stage-2 steps (3 warm-up + 10) at 32 x 1024 with train_mlp="kernels" and the given --heads alone, nothing timed:
+            the subject of a `rocprofv3 --kernel-trace --stats` run of its own per --heads value
 
 Timing: bench_rotation_grad.compare -- a host clock around a block of calls ended by a device synchronise, blocks of at
 least a quarter of a second, six blocks that alternate the two forms in both orders, in one process; reported are the
-median of a form's three block means and their range.  profiles/refiner_grad.txt holds one run's output."""
+median of a form's three block means and their range.  profiles/refiner_grad.txt holds one run's output.
+
+--heads modules|kernels: Refiner(train_heads=) of BOTH forms -- the two pose heads as the registered modules (default) or as one
+autograd.PoseHeadsFn (csrc/pose_heads_grad.hip); profiles/train_heads.txt compares the two."""
 import argparse
 import importlib
 import os
@@ -43,6 +49,7 @@ from bench_rotation_grad import MIN_BLOCK_S, compare  # noqa: E402
 
 FORMS = ("kernels", "modules")
 SHAPES = ((20, 1024), (32, 1024))
+HEADS = "modules"                        # --heads
 
 
 def line(what, res):
@@ -53,7 +60,7 @@ def line(what, res):
 
 
 def make_refiner(dcl, form, rotation="device"):
-    ref = dcl.refiner.Refiner(train_rotation=rotation, train_mlp=form)
+    ref = dcl.refiner.Refiner(train_rotation=rotation, train_mlp=form, train_heads=HEADS)
     ref.load_state_dict(dcl.synth.synth_state_dict(ref, 2))
     return ref.cuda().train()
 
@@ -160,12 +167,14 @@ def stage2_step(dcl, net, data, form, iteration=2):
         for p in ref.parameters():
             p.grad = None
         for _ in range(iteration):
-            cur = torch.bmm(pts - trans_cur.unsqueeze(1), rot_cur)
+            # (the loop's own pose arithmetic on ops.rigid_points and broadcast products: torch.bmm on (b, n, 3) x (b, 3, 3) and on
+            #  3 x 3 matrices is three vendor GEMM launches per iteration, the only ones left once both switches are "kernels")
+            cur = dcl.ops.rigid_points(pts.contiguous(), rot_cur.contiguous(), trans_cur.contiguous(), inverse=True)
             inp = torch.cat([cur.transpose(1, 2), F], dim=1).detach()
             out = ref({"input_features": inp, "conf": conf, "obj_idx": None})
             crit(out, trans_cur.detach(), rot_cur.detach(), cld, sym, gt)["loss_all"].backward()
-            trans_cur = ((rot_cur @ out["trans_pred"].unsqueeze(2)).squeeze(2) + trans_cur).detach()
-            rot_cur = (rot_cur @ out["rot_pred"]).detach()
+            trans_cur = ((rot_cur * out["trans_pred"].unsqueeze(1)).sum(2) + trans_cur).detach()
+            rot_cur = (rot_cur.unsqueeze(3) * out["rot_pred"].unsqueeze(1)).sum(2).detach()
         clip(ref)
         opt.step()
     return step
@@ -200,20 +209,35 @@ def part_launches(dcl, args):
             print("    %3d  %s" % (c, k[:150]))
 
 
+def part_trace(dcl, args):
+    b, n = SHAPES[1]
+    net = dcl.DCL_Net.Network(dcl.synth.default_cfg(n, n), mode="test")
+    net.load_state_dict(dcl.synth.synth_state_dict(net, 1))
+    net = net.cuda().eval()
+    step = stage2_step(dcl, net, dcl.synth.make_batch(b, n, n), "kernels")
+    for _ in range(13):
+        step()
+    torch.cuda.synchronize()
+    print("  13 stage-2 steps at %d x %d, train_mlp=\"kernels\", train_heads=\"%s\"" % (b, n, HEADS))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=("accuracy", "kernels", "op", "step", "launches"), required=True)
+    ap.add_argument("--part", choices=("accuracy", "kernels", "op", "step", "launches", "trace"), required=True)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--step-iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--heads", choices=("modules", "kernels"), default="modules")
     args = ap.parse_args()
+    global HEADS
+    HEADS = args.heads
     if not torch.cuda.is_available():
         raise SystemExit("bench_refiner_grad: needs the GPU (no CPU timing is meaningful)")
     dcl = importlib.import_module("dcl-net_amd")
-    print("== refiner training, part %s: train_mlp=\"kernels\" (csrc/linear_bwd.hip + the own GEMM core) vs \"modules\" (torch)" % args.part)
+    print("== refiner training, part %s: train_mlp=\"kernels\" (csrc/linear_bwd.hip + the own GEMM core) vs \"modules\" (torch); train_heads=\"%s\"" % (args.part, args.heads))
     print("device: %s, torch %s; blocks of at least %d calls / %d steps and %.2f s, six alternating blocks after %d warm-up rounds" %
           (torch.cuda.get_device_name(0), torch.__version__, args.iters, args.step_iters, MIN_BLOCK_S, args.warmup))
-    {"accuracy": part_accuracy, "kernels": part_kernels, "op": part_op, "step": part_step, "launches": part_launches}[args.part](dcl, args)
+    {"accuracy": part_accuracy, "kernels": part_kernels, "op": part_op, "step": part_step, "launches": part_launches, "trace": part_trace}[args.part](dcl, args)
 
 
 if __name__ == "__main__":
