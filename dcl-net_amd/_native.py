@@ -43,6 +43,9 @@ def _open(path):
     # csrc/conv_dgrad.hip
     L.dcl_sparse_conv_dgrad.argtypes = [vp, i, vp, i, i, vp, i, i, i, vp, vp]
     L.dcl_sparse_conv_dgrad_host.argtypes = [vp, i, vp, i, i, vp, i, i, i, vp]
+    # csrc/conv_fwd_compact.hip
+    L.dcl_sparse_conv_fwd_compact.argtypes = [vp, i, vp, i, i, vp, i, i, i, i, vp, vp]
+    L.dcl_sparse_conv_fwd_compact_host.argtypes = [vp, i, vp, i, i, vp, i, i, i, i, vp]
     # csrc/conf_pool_grad.hip: an int64 scratch size among the pointers
     L.dcl_conf_pool_cm_fwd.argtypes = [i] * 4 + [vp] * 5
     L.dcl_conf_pool_cm_fwd_host.argtypes = [i] * 4 + [vp] * 4
@@ -79,7 +82,7 @@ def _open(path):
                L.dcl_pose_heads_train_bwd_ws_bytes, L.dcl_pose_heads_train_bwd, L.dcl_pose_heads_train_bwd_host):
         fn.restype = i
     for fn in (L.dcl_linear_wgrad_splits, L.dcl_linear_wgrad, L.dcl_relu_bwd, L.dcl_sparse_conv_dgrad,
-               L.dcl_sparse_conv_dgrad_host, L.dcl_conf_pool_cm_fwd, L.dcl_conf_pool_cm_fwd_host,
+               L.dcl_sparse_conv_dgrad_host, L.dcl_sparse_conv_fwd_compact, L.dcl_sparse_conv_fwd_compact_host, L.dcl_conf_pool_cm_fwd, L.dcl_conf_pool_cm_fwd_host,
                L.dcl_conf_pool_cm_bwd_ws_bytes, L.dcl_conf_pool_cm_bwd, L.dcl_conf_pool_cm_bwd_host,
                L.dcl_conf_pool_pm_fwd, L.dcl_conf_pool_pm_fwd_host, L.dcl_conf_pool_pm_bwd_ws_bytes, L.dcl_conf_pool_pm_bwd,
                L.dcl_conf_pool_pm_bwd_host, L.dcl_bn_relu_ws_bytes, L.dcl_bn_relu_fwd, L.dcl_bn_relu_fwd_host, L.dcl_bn_relu_bwd, L.dcl_bn_relu_bwd_host):

@@ -19,21 +19,23 @@ from . import ops as _ops
 class SparseConvFn(Function):
     """SparseConvFunction / SubMConvFunction (functional.py:20-88).  wgrad: the form of the weight gradient, "rows" (default) or
     "pairs" (ops.sparse_conv_backward); the pair list is built in the backward call and dies with it.  dgrad: the form of the
-    input gradient, "conv" (default) or "direct" (ops.sparse_conv_dgrad)."""
+    input gradient, "conv" (default) or "direct" (ops.sparse_conv_dgrad).  fwd: the form of the forward, "tiles" (default) or
+    "compact" (ops.sparse_conv_compact); the backward does not depend on it, and its dgrad="conv" route keeps re-entering the
+    default forward dispatcher."""
 
     @staticmethod
-    def forward(ctx, features, W, nbr, n_out, subm, wgrad="rows", dgrad="conv"):
+    def forward(ctx, features, W, nbr, n_out, subm, wgrad="rows", dgrad="conv", fwd="tiles"):
         ctx.save_for_backward(features, W, nbr)
         ctx.n_out, ctx.subm, ctx.wgrad = int(n_out), bool(subm), _ops.check_conv_wgrad(wgrad)
         ctx.dgrad = _ops.check_conv_dgrad(dgrad)
-        return _ops.sparse_conv(features, nbr, n_out, W, subm)
+        return _ops.sparse_conv(features, nbr, n_out, W, subm, form=_ops.check_conv_fwd(fwd))
 
     @staticmethod
     def backward(ctx, grad_output):
         features, W, nbr = ctx.saved_tensors
         dx, dW = _ops.sparse_conv_backward(features, W, grad_output, nbr, ctx.n_out, ctx.subm,
                                            need_dx=ctx.needs_input_grad[0], wgrad=ctx.wgrad, dgrad=ctx.dgrad)
-        return dx, dW.view_as(W), None, None, None, None, None
+        return dx, dW.view_as(W), None, None, None, None, None, None
 
 
 class SparseAvgPoolFn(Function):

@@ -130,7 +130,7 @@ class Network(nn.Module):
                  single_stream=False, pipeline_chunks=1, capture_graph=True, pair_features=None,
                  train_attention="materialised", train_rotation="host", train_conv_wgrad="rows",
                  train_conv_dgrad="conv", train_pool="modules", train_norm="modules", train_dense="modules",
-                 train_heads="modules"):
+                 train_heads="modules", train_conv_fwd="tiles"):
         """graph_max_batch > 0 (default 8): eval-mode calls with at most that many crops go through forward_graphed (one
         whole-forward hipGraph per batch size, captured on first use) -- the one-image-at-a-time eval loops of the
         reference (tools/test_LM.py:104-112: one object per call) are launch-bound otherwise: 0.53 instead of 1.1 ms
@@ -201,11 +201,18 @@ class Network(nn.Module):
         It requires train_dense="point_major" (ValueError otherwise).  Same parameters, buffers and state_dict keys, no cached
         weights; the train-mode pose-head values are not the eval kernels' bits.  Eval mode, the fused pipeline and the graphs
         never read it.
+        train_conv_fwd: the form of the sparse convolutions' FORWARD on the same path (spconv.SparseConvolution.fwd).  "tiles"
+        (default) = the dispatcher of csrc/sparse_conv.hip; "compact" = csrc/conv_fwd_compact.hip, which puts only the present (row,
+        offset) pairs on the matrix pipe, on the dilating convolutions whose (cin, cout) is in ops.CONV_FWD_COMPACT_WIDTHS -- the
+        widths on which it was measured faster (profiles/conv_fwd_compact.txt: none so far, the table is empty and "compact"
+        changes no layer) -- and "tiles" on the others, on every subm layer and on the stem.  Independent of every other train_* switch; same parameters, buffers and state_dict keys; the backward is the
+        same either way.  Eval mode's fused pipeline, the graphs and forward_graphed never read it.
         These are constructor arguments on purpose: nothing on the call path reads the environment."""
         super().__init__()
         self.train_pool = check_train_pool(train_pool)
         self.train_norm = ops.check_train_norm(train_norm)
         self.train_conv_dgrad = ops.check_conv_dgrad(train_conv_dgrad, "train_conv_dgrad")
+        self.train_conv_fwd = ops.check_conv_fwd(train_conv_fwd, "train_conv_fwd")
         self.train_conv_wgrad = ops.check_conv_wgrad(train_conv_wgrad, "train_conv_wgrad")
         self.train_rotation = check_train_rotation(train_rotation)
         if train_attention not in ("materialised", "fused"):
@@ -235,6 +242,7 @@ class Network(nn.Module):
                 if isinstance(m, spconv.SparseConvolution):
                     m.wgrad = self.train_conv_wgrad
                     m.dgrad = ops.conv_dgrad_form(m.in_channels, m.out_channels, self.train_conv_dgrad)
+                    m.fwd = ops.conv_fwd_form(m.in_channels, m.out_channels, m.subm, self.train_conv_fwd)
                 elif isinstance(m, BasicBlock_SPCONV):
                     m.norm_form = self.train_norm
         self.stage1_get_point_feats = Ops_GetPointFeat_spconv(SCALE_LISTS, self.unit_voxel_extent, VOXEL_NUM_LIMIT)

@@ -308,9 +308,16 @@ def order_rows(out_set, in_mask, subm):
     return order[:n], bal[:nt + 1], smask[:nt]
 
 
-def sparse_conv(feat, nbr, n_out, W, subm, scale=None, shift=None, relu=False, order=None):
+def sparse_conv(feat, nbr, n_out, W, subm, scale=None, shift=None, relu=False, order=None, form="tiles"):
     """indice_conv_fp32 (+ folded BatchNorm1d(eval) + ReLU).  feat (V_in,Cin); W (kvol,Cin,Cout).  order: the triple of
-    order_rows -- the launch then computes its rows in that order and deals its work in used chunks (same output)."""
+    order_rows -- the launch then computes its rows in that order and deals its work in used chunks (same output).  form: "tiles"
+    (default: the dispatcher of csrc/sparse_conv.hip, whose tiles run every offset any of their rows has) or "compact"
+    (sparse_conv_compact: csrc/conv_fwd_compact.hip, the present (row, offset) pairs only, in a pinned order; it has no
+    epilogue and no row order -- ValueError if scale, shift, relu or order is given)."""
+    if check_conv_fwd(form, "form") == "compact":
+        if scale is not None or shift is not None or relu or order is not None:
+            raise ValueError('sparse_conv(form="compact") has no scale / shift / relu epilogue and takes no row order')
+        return sparse_conv_compact(feat, nbr, n_out, W, subm)
     N.need_cuda(feat, nbr, W)
     kvol, cap = nbr.shape
     cin, cout = W.shape[-2], W.shape[-1]
@@ -2453,6 +2460,64 @@ def sparse_conv_wgrad_pairs(feat, dout, pairs, cin, cout):
                                                 N.ptr(pairs.split_tab), pairs.max_splits, N.ptr(partial), N.ptr(dW),
                                                 N.stream()), "sparse_conv_wgrad_pairs")
     return dW
+
+
+CONV_FWD_FORMS = ("tiles", "compact")
+# the (cin, cout) of the DILATING (non-subm) backbone layers among 32 -> 32, 64 -> 64 and 128 -> 128 on which
+# tools/bench_conv_fwd.py measured "compact" faster than "tiles" with disjoint block ranges on the layers of BOTH backbones
+# (profiles/conv_fwd_compact.txt); Network(train_conv_fwd="compact") goes by this table.  EMPTY as measured: the compact form
+# is 1.35-2.2 times slower than "tiles" on all three widths, so the switch changes no layer until the kernel earns a width
+CONV_FWD_COMPACT_WIDTHS = frozenset()
+
+
+def check_conv_fwd(value, what="fwd"):
+    if value not in CONV_FWD_FORMS:
+        raise ValueError('%s must be "tiles" or "compact", got %r' % (what, value))
+    return value
+
+
+def conv_fwd_form(cin, cout, subm, train_conv_fwd="compact"):
+    """the forward form of a convolution of these widths under Network(train_conv_fwd=): by the widths and the kind of the
+    layer alone, never by the data.  Subm layers and the stem always stay with "tiles"."""
+    compact = check_conv_fwd(train_conv_fwd, "train_conv_fwd") == "compact"
+    return "compact" if compact and not subm and (int(cin), int(cout)) in CONV_FWD_COMPACT_WIDTHS else "tiles"
+
+
+def sparse_conv_compact(feat, nbr, n_out, W, subm):
+    """out (n_out, cout) = sum_k sum_ci feat[nbr[k][o]][ci] W[k][ci][co] on csrc/conv_fwd_compact.hip: only the present (row,
+    offset) pairs reach the matrix pipe.  An entry of nbr is a neighbour iff it names one of feat's rows.  Pinned order
+    (csrc/conv_fwd_compact.h): per present offset a chain of its own over ci ascending, added with one fp32 add, offsets in the
+    forward's visiting order; the same bits on every call.  Every element is written.  feat and W may be views that start off
+    a 16-byte boundary (contiguous rows): the kernel then loads float by float, the same bits."""
+    N.need_cuda(feat, nbr, W)
+    assert nbr.dtype == torch.int32 and nbr.dim() == 2 and nbr.is_contiguous()
+    kvol, cap = nbr.shape
+    cin, cout = int(W.shape[-2]), int(W.shape[-1])
+    n_out = int(n_out)
+    assert feat.dtype == torch.float32 and W.dtype == torch.float32 and feat.is_contiguous() and W.is_contiguous()
+    assert feat.dim() == 2 and feat.shape[1] == cin and W.numel() == kvol * cin * cout and 0 <= n_out <= cap
+    out = torch.empty((n_out, cout), dtype=torch.float32, device=feat.device)
+    N.check(N.lib().dcl_sparse_conv_fwd_compact(N.ptr(feat), int(feat.shape[0]), N.ptr(nbr), cap, n_out, N.ptr(W), cin, cout, kvol,
+                                                int(bool(subm)), N.ptr(out), N.stream()), "sparse_conv_fwd_compact")
+    return out
+
+
+def sparse_conv_compact_host(feat, nbr, n_out, W, subm, n_in=None):
+    """the host twin of sparse_conv_compact (dcl_sparse_conv_fwd_compact_host, plain C++, no GPU) on numpy arrays: the same
+    steps, literally.  n_in: the rows of feat that count (default: all of them)."""
+    import numpy as np
+    nbr = np.ascontiguousarray(nbr, np.int32)
+    kvol, cap = nbr.shape
+    cin, cout = int(W.shape[-2]), int(W.shape[-1])
+    feat = np.ascontiguousarray(feat, np.float32)
+    W = np.ascontiguousarray(np.asarray(W, np.float32).reshape(kvol, cin, cout))
+    n_in = feat.shape[0] if n_in is None else int(n_in)
+    assert feat.ndim == 2 and feat.shape[1] == cin and n_in <= feat.shape[0] and int(n_out) <= cap
+    out = np.full((int(n_out), cout), np.nan, np.float32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    N.check(N.lib().dcl_sparse_conv_fwd_compact_host(vp(feat), n_in, vp(nbr), cap, int(n_out), vp(W), cin, cout, kvol,
+                                                     int(bool(subm)), vp(out)), "sparse_conv_fwd_compact_host")
+    return out
 
 
 CONV_DGRAD_FORMS = ("conv", "direct")

@@ -14,6 +14,8 @@ from .tensor import SparseConvTensor
 
 
 class SparseConvolution(SparseModule):
+    fwd = "tiles"                      # the forward's form on the differentiable path: "tiles" or "compact" (ops.sparse_conv)
+
     def __init__(self, ndim, in_channels, out_channels, kernel_size=3, stride=1, padding=0, dilation=1, groups=1,
                  bias=True, subm=False, output_padding=0, transposed=False, inverse=False, indice_key=None):
         super(SparseConvolution, self).__init__()
@@ -74,7 +76,8 @@ class SparseConvolution(SparseModule):
             input.indice_dict[self.indice_key] = (out_set, indices, nbr, None, input.spatial_shape)
         n_out = indices.shape[0] if self.subm else out_set.n
         W = self.weight.view(-1, self.in_channels, self.out_channels)
-        out_features = SparseConvFn.apply(features.contiguous(), W.contiguous(), nbr, n_out, self.subm, self.wgrad, self.dgrad)
+        out_features = SparseConvFn.apply(features.contiguous(), W.contiguous(), nbr, n_out, self.subm, self.wgrad, self.dgrad,
+                                          self.fwd)
         if self.bias is not None:
             out_features += self.bias
         out_tensor = SparseConvTensor(out_features, indices if self.subm else out_set.indices, out_shape,

@@ -659,6 +659,30 @@ int dcl_sparse_conv_dgrad(const float *dout, int n_out, const int32_t *inv, int 
                           int cout, int kvol, float *dx, dclStream_t stream);
 int dcl_sparse_conv_dgrad_host(const float *dout, int n_out, const int32_t *inv, int cap_in, int n_in, const float *W, int cin,
                                int cout, int kvol, float *dx);
+/* ---- the forward of indice_conv over the PRESENT (row, offset) pairs, in a pinned order (csrc/conv_fwd_compact.hip,
+ * conv_fwd_compact.h): the second forward form, ops.sparse_conv(form="compact"), beside dcl_sparse_conv_fwd ("tiles").
+ *
+ *   out[o][co] = sum_k sum_ci feat[nbr[k][o]][ci] * W[k][ci][co]         o < n_out, co < cout
+ *
+ * feat n_in x cin, out n_out x cout, W kvol x cin x cout, all dense row-major; nbr kvol x cap (i32).  An entry is a neighbour
+ * iff 0 <= nbr[k][o] < n_in; any other entry takes no part and is never an address, so rows of feat at or past n_in and rows
+ * of nbr at or past n_out are never read.  fp32 MFMA (v_mfma_f32_32x32x2_f32): exact products, one rounding per step.
+ * PINNED ORDER: an element of out is acc, started at +0; the offsets are visited in the forward's visiting order (k
+ * ascending, the centre kvol / 2 first if subm != 0), an offset that is no neighbour skipped; a visited offset forms
+ *   part = +0;  for ci = 0 .. cin - 1 ascending: part = fmaf(feat[nbr[k][o]][ci], W[k][ci][co], part)
+ * and joins with ONE fp32 add, acc = acc + part -- the reference's own association (a GEMM per offset, then a scatter-add),
+ * which the host twin runs literally.  The element is a function of its row's neighbours, of the feat rows they name and of W
+ * alone: not of n_out, cap, other rows or the launch.  Every element of the n_out rows of out is written, +0 for a row
+ * without neighbours; nothing at or past row n_out is.  Any cin, cout >= 1 and kvol <= 27, subm or not, through one body
+ * (zero-filled lanes; 16-byte loads and stores are only the fast path of aligned rows); W and the named rows of feat are
+ * taken to be finite.  No BatchNorm / ReLU epilogue.  No float atomics, no waiting on counters, no scratch, no stream-K; one
+ * launch, capturable.  dcl_sparse_conv_fwd_compact_host is the same routine in plain C++ on HOST pointers and makes no GPU
+ * call.  DCL_EINVAL before any GPU work for kvol outside 1..27, a negative size, cin or cout < 1, cap < n_out, a NULL or
+ * misaligned buffer that a non-empty side needs; n_out == 0 returns 0 and touches nothing, n_in == 0 writes +0.          */
+int dcl_sparse_conv_fwd_compact(const float *feat, int n_in, const int32_t *nbr, int cap, int n_out, const float *W, int cin,
+                                int cout, int kvol, int subm, float *out, dclStream_t stream);
+int dcl_sparse_conv_fwd_compact_host(const float *feat, int n_in, const int32_t *nbr, int cap, int n_out, const float *W, int cin,
+                                     int cout, int kvol, int subm, float *out);
 /* indice_avgpool backward (avgpool.cu:178-206): din[i] = sum_k asc dout[inv[k][i]] / (float)rf[inv[k][i]].  C % 4 == 0. */
 int dcl_sparse_avgpool_bwd(const float *dout, const int32_t *inv, int cap_in, int n_in, const int32_t *rf, int c, int kvol,
                            float *din, dclStream_t stream);
@@ -1394,6 +1418,8 @@ int dcl_debug_order_stamps(unsigned long long *host16);
 /* Tuning hook: 1 (default) = the LDS-DMA conv kernel renumbers its workgroups XCD-aware (column tiles of a row tile and
  * neighbouring row tiles share an L2), 0 = plain blockIdx order. */
 void dcl_debug_conv_xcd_remap(int on);
+/* Tuning hook: output rows per tile of dcl_sparse_conv_fwd_compact, 64 or 128; 0 (default) = by the layer's width. */
+void dcl_debug_conv_fwd_compact_bm(int bm);
 /* Tuning hook for dcl_group_points' LDS-staged kernel: channel rows per workgroup, x-blocks, threads per workgroup,
  * store kind (2 = plain instead of nontemporal); 0 = built-in choice for each. */
 void dcl_debug_group_points_cfg(int cc, int xb, int threads, int nontemporal);
