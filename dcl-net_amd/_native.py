@@ -77,6 +77,10 @@ def _open(path):
     L.dcl_pose_heads_train_bwd_ws_bytes.argtypes = [i] * 6 + [C.POINTER(C.c_int64)]
     L.dcl_pose_heads_train_bwd.argtypes = [i] * 6 + [vp] * 25 + [i64, vp]
     L.dcl_pose_heads_train_bwd_host.argtypes = [i] * 6 + [vp] * 24
+    # csrc/template_rows.hip: an int64 class pitch
+    L.dcl_template_rows.argtypes = [vp, i64, i, i, vp, i, vp, i, vp, i, vp, vp]
+    L.dcl_template_rows_host.argtypes = [vp, i64, i, i, vp, i, vp, i, vp, i, vp]
+    L.dcl_template_rows.restype = L.dcl_template_rows_host.restype = i
     for fn in (L.dcl_linear_narrow_fwd, L.dcl_linear_narrow_fwd_host, L.dcl_linear_narrow_bwd_ws_bytes, L.dcl_linear_narrow_bwd,
                L.dcl_linear_narrow_bwd_host, L.dcl_pose_heads_train_fwd, L.dcl_pose_heads_train_fwd_host,
                L.dcl_pose_heads_train_bwd_ws_bytes, L.dcl_pose_heads_train_bwd, L.dcl_pose_heads_train_bwd_host):

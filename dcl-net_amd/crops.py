@@ -212,7 +212,8 @@ def _mark(label):
 
 
 class CropBuilder(object):
-    def __init__(self, cfg, cad_points_mm, cad_colors, camera=YCBV_CAMERA, device="cuda", capacity=False, v2p_pitch=33):
+    def __init__(self, cfg, cad_points_mm, cad_colors, camera=YCBV_CAMERA, device="cuda", capacity=False, v2p_pitch=33,
+                 template_ids=False):
         """cfg: mapping with input_size, tmp_size, unit_voxel_extent, voxel_num_limit, voxelization_mode (the `test`
         block of configs/config_YCBV_bs32.yaml).  cad_points_mm / cad_colors: {class id: (tmp_size,3) float64}, the
         loader's list_pc_CAD / list_rgb_CAD (millimetres; colours already mean-subtracted, :57-58).
@@ -221,8 +222,14 @@ class CropBuilder(object):
         read-back per frame (the per-instance point counts the loader's random draws need) instead of two; Network.forward
         takes that form on its graph path (exact_form(data) converts, with the read-back).  v2p_pitch: 1 + the most points of
         a crop one voxel may hold.  Exact mode repeats an image whose crops exceed it with the general op; in capacity mode
-        the device-side flag data["inp"]["vi_info"][2] says so (the caller reads it with its results; exact_form raises)."""
+        the device-side flag data["inp"]["vi_info"][2] says so (the caller reads it with its results; exact_form raises).
+        template_ids=True: the eval builders name the template side instead of building it -- build() emits data["tmp_cls"], a
+        device tensor of the crops' class ids, and no data["tmp"]; build_lm / build_lmo return that one-element tensor and None
+        in place of (feat_tmp, voxel_tmp).  For a Network with a per-class template cache: net.cache_templates(builder.templates(),
+        voxel_num_limit) once, then every such call runs no template-side work (models/DCL_Net.py).  The training builders
+        (build_train, build_train_lm) do not read it."""
         self.capacity, self.v2p_pitch = bool(capacity), int(v2p_pitch)
+        self.template_ids = bool(template_ids)
         self.n_inp, self.n_tmp = int(cfg["input_size"]), int(cfg["tmp_size"])
         self.unit = np.array(cfg["unit_voxel_extent"]).astype(float)
         self.limit = np.array(cfg["voxel_num_limit"]).astype(float)
@@ -255,6 +262,15 @@ class CropBuilder(object):
             v2p = v2p.cpu().numpy()
             ids = (np.arange(v2p.shape[1])[None, :] >= 1) & (np.arange(v2p.shape[1])[None, :] <= v2p[:, :1])
             self._tmp_tab.append((occ.cpu().numpy(), p2v.cpu().numpy(), v2p, ids))
+
+    def templates(self):
+        """{class id: one-crop data["tmp"]} of every class the builder holds -- feats (n_tmp, 7) on the device, occupied_voxels
+        (v, 4) and v2p_maps (v, ma + 1) of crop index 0 from the per-class tables: the dict Network.cache_templates takes"""
+        out = {}
+        for c, r in self.cls_row.items():
+            occ, _, v2p, _ = self._tmp_tab[r]
+            out[int(c)] = {"feats": self.tmp_feats[r], "occupied_voxels": torch.from_numpy(occ), "v2p_maps": torch.from_numpy(v2p)}
+        return out
 
     def _template_side(self, rows):
         """occupied_voxels / p2v_maps / v2p_maps of the template clouds of the classes `rows` (one per crop), exactly what
@@ -340,9 +356,13 @@ class CropBuilder(object):
         # that then drops an instance (an empty mask) redoes this part for the kept ones.
         def count_free_part(keep):
             rows = [self.cls_row[int(gt_obj[cand[k]])] for k in keep]
-            cls_rows = _upload(np.asarray(rows, np.int64), dev)
-            part = {"rows": rows, "feats_tmp": self.tmp_feats[cls_rows].reshape(len(keep) * self.n_tmp, 7),
-                    "tmp_side": self._template_side(rows), "labels": {}}
+            if self.template_ids:                   # the template side by name: the candidates' class ids are on the device already
+                part = {"rows": rows, "labels": {},
+                        "tmp_cls": o_t if len(keep) == len(cand) else o_t[_upload(np.asarray(keep, np.int64), dev)].contiguous()}
+            else:
+                cls_rows = _upload(np.asarray(rows, np.int64), dev)
+                part = {"rows": rows, "feats_tmp": self.tmp_feats[cls_rows].reshape(len(keep) * self.n_tmp, 7),
+                        "tmp_side": self._template_side(rows), "labels": {}}
             cen = centroid if len(keep) == len(cand) else centroid[_upload(np.asarray(keep, np.int64), dev)]
             if poses is not None:
                 # rot_gt = poses[:, 0:3], trans_gt = poses[:, 3] - centroid (:226-240: float64 difference, rounded to float32
@@ -391,14 +411,17 @@ class CropBuilder(object):
         feats_inp, coords_inp = ops.crop_sample(xyz, col, pick_t, counts, self.extent[0] * 0.5, self.unit,
                                                 int(self.limit[0]), min_valid=MIN_VALID)
         b = len(keep)
-        rows, feats_tmp = part["rows"], part["feats_tmp"]
         data = dict(part["host"], all_flags=torch.IntTensor(flags), all_centroids=part["centroid"], labels=part["labels"],
                     counts=cnt[keep])
         _mark("sample + labels issued")
         data["inp"] = self._inp_side(feats_inp, coords_inp, b)
         _mark("voxelisation issued")
-        occ, p2v, v2p, coords_tmp = part["tmp_side"]                                # tables: no kernel, no read-back
-        data["tmp"] = {"feats": feats_tmp, "coords": coords_tmp, "occupied_voxels": occ, "p2v_maps": p2v, "v2p_maps": v2p}
+        if self.template_ids:
+            data["tmp_cls"] = part["tmp_cls"]
+        else:
+            occ, p2v, v2p, coords_tmp = part["tmp_side"]                            # tables: no kernel, no read-back
+            data["tmp"] = {"feats": part["feats_tmp"], "coords": coords_tmp, "occupied_voxels": occ, "p2v_maps": p2v,
+                           "v2p_maps": v2p}
         # a Network(async_inputs=True) lets its side streams wait for exactly this point instead of the whole stream
         data["ready_event"] = torch.cuda.Event()
         data["ready_event"].record(torch.cuda.current_stream(dev))
@@ -796,6 +819,8 @@ class CropBuilder(object):
         pick_t = torch.from_numpy(pick.astype(np.int64)).view(1, -1).to(dev)
         feats, coords = ops.crop_sample(xyz, col, pick_t, None, self.extent[0] * 0.5, self.unit, int(self.limit[0]))
         row = self.cls_row[int(obj)]
+        if self.template_ids:
+            return feats, coords[:, 1:].contiguous(), torch.tensor([int(obj)], dtype=torch.int32, device=dev), None, centroid[0]
         return feats, coords[:, 1:].contiguous(), self.tmp_feats[row], self.tmp_vox[row], centroid[0]
 
 

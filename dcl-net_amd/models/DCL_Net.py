@@ -125,6 +125,59 @@ def _fuser():
     return Head_MultiLayerPerceptron([512, 512, 512, 1024], ["relu"] * 3, [True] * 3, [0.0] * 3)
 
 
+class TemplateCache(object):
+    """What the template half of an eval-mode forward leaves behind, per object class (Network.cache_templates).
+
+    With BatchNorm folded, the template side of a crop -- geometry, voxelisation, backbone_tmp, the multi-scale read-out and the
+    four disengage_Yo stacks -- is a pure function of (weights, the class's CAD cloud).  The rest of the forward consumes four
+    matrices per crop from it, and the caller the cloud's coordinates:
+        rows (C, n_tmp, 643) float32 = [Yo p1 256 | Yo m1 64 | Yo p2 256 | Yo m2 64 | xyz 3]
+    a view of (C, n_tmp, 644) storage, so that every row starts 16-byte aligned and ops.template_rows moves 16 bytes per lane.
+    Memory: C * n_tmp * 644 * 4 bytes -- 55 MB for YCB-V's 21 classes at n_tmp = 1024.
+        lut        (max class id + 1,) int32 on the device: class id -> slot of `rows`, -1 where the class is not cached
+        class_ids  the cached ids, in slot order
+        miss       1-element int32 device tensor: set to 1 by a call that carried an id outside the cache (that crop's template
+                   activations were zeros); it travels with the predictions as pred["template_miss"] and is never read here
+        inputs     {class id: one-crop data["tmp"]} as given, kept so that the rows can follow the weights
+        S          the voxel grid side the inputs were made for
+    `valid` / `version`: the rows belong to the parameters' version counters `version`; Network._invalidate clears `valid`, and
+    the next cached call recomputes the rows -- into the same tensors where the shape allows (graphs bake addresses).
+    Pickling / deepcopy keeps the inputs and drops the device tensors."""
+    COLS = 643
+    PITCH = 644
+    BLOCKS = (("p1", 0, 256), ("m1", 256, 64), ("p2", 320, 256), ("m2", 576, 64), ("xyz", 640, 3))
+
+    def __init__(self, inputs, S, n_tmp):
+        self.inputs = dict(inputs)
+        self.class_ids = sorted(int(c) for c in self.inputs)
+        if not self.class_ids or self.class_ids[0] < 0:
+            raise ValueError("cache_templates: class ids must be non-negative integers, at least one")
+        self.slot = {c: i for i, c in enumerate(self.class_ids)}
+        self.S, self.n_tmp = int(S), int(n_tmp)
+        self.storage = self.rows = self.lut = self.miss = None
+        self.valid, self.version = False, None
+
+    def nbytes(self):
+        return len(self.class_ids) * self.n_tmp * self.PITCH * 4
+
+    def allocate(self, dev):
+        """device tensors on `dev`; the ones that are already there are kept (their addresses may be baked into graphs)"""
+        if self.storage is not None and self.storage.device == dev:
+            return
+        C = len(self.class_ids)
+        self.storage = torch.zeros((C, self.n_tmp, self.PITCH), dtype=torch.float32, device=dev)
+        self.rows = self.storage[:, :, :self.COLS]
+        lut = torch.full((self.class_ids[-1] + 1,), -1, dtype=torch.int32)
+        lut[torch.tensor(self.class_ids, dtype=torch.int64)] = torch.arange(C, dtype=torch.int32)
+        self.lut = lut.to(dev)
+        self.miss = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.update(storage=None, rows=None, lut=None, miss=None, valid=False, version=None)
+        return state
+
+
 class Network(nn.Module):
     def __init__(self, cfg, mode="train", fused=True, graph_max_batch=8, async_inputs=False, graph_max_points=98304,
                  single_stream=False, pipeline_chunks=1, capture_graph=True, pair_features=None,
@@ -262,6 +315,7 @@ class Network(nn.Module):
         self.regressor_rot = _mlp3([1024, 512, 128, 9])
         self.regressor_trans = _mlp3([1024, 512, 128, 3])
         self._folded = None
+        self.template_cache = None                       # per-class template rows (cache_templates): calls with data["tmp_cls"]
 
     @property
     def pair_features(self):
@@ -282,6 +336,8 @@ class Network(nn.Module):
     def _invalidate(self):
         """folded weights and captured graphs (which have the folded tensors' addresses baked in) follow the parameters"""
         self._folded = None
+        if self.__dict__.get("template_cache") is not None:
+            self.template_cache.valid = False            # recomputed from the kept inputs by the next cached call
         for ent in (self.__dict__.pop("_graphs", None) or {}).values():
             self._drop_graph(ent)
         self.__dict__.pop("_graph_seen", None)
@@ -388,6 +444,108 @@ class Network(nn.Module):
         self._folded = f
         return f
 
+    # ------------------------------------------------------------------ per-class template cache (eval mode)
+    def cache_templates(self, templates, voxel_num_limit):
+        """Compute the template half of the eval-mode forward ONCE per object class and keep it (self.template_cache, a
+        TemplateCache): a call whose `data` carries data["tmp_cls"] -- the crops' class ids -- instead of data["tmp"] then runs
+        no template-side work at all; one ops.template_rows launch deals the cached rows into its activation buffers.
+        templates: {class id: {"feats": (n_tmp, 7), "occupied_voxels": (v, 4), "v2p_maps": (v, ma + 1)}}, each entry exactly a
+        ONE-crop data["tmp"] (crop index 0; crops.CropBuilder.templates() and synth.class_template_side make them).
+        voxel_num_limit: as data["voxel_num_limit"].
+        Every class is computed alone, as a one-crop, launch-by-launch pass of the fused path's own template-side code on the
+        current stream (fp32 V stack), so an entry's bits depend on (weights, that class's input) and on nothing else -- not on
+        which other classes are cached, nor in what order.  Eval mode and fused=True only (ValueError): in training the
+        BatchNorms use batch statistics and the template activations depend on the batch.  The cache follows the weights like
+        the folded parameters do (version counters, _invalidate): after load_state_dict, .cuda(), an in-place weight change or
+        train() / eval() the next cached call recomputes the rows from the kept inputs, into the same tensors.
+        Memory: classes * n_tmp * 644 * 4 bytes (55 MB for YCB-V's 21 classes at n_tmp = 1024)."""
+        if not self.fused or self.training:
+            raise ValueError("cache_templates: the template cache serves the fused eval-mode pipeline only (fused=True, .eval())")
+        S = int(np.asarray(voxel_num_limit).astype(np.int64).reshape(-1)[0])
+        for c, d in templates.items():
+            if tuple(d["feats"].shape) != (self.n_tmp, 7) or d["occupied_voxels"].dim() != 2 or d["v2p_maps"].dim() != 2 or \
+                    d["occupied_voxels"].shape[0] != d["v2p_maps"].shape[0]:
+                raise ValueError("cache_templates: class %r is not a one-crop data['tmp'] of %d points" % (c, self.n_tmp))
+        graphs = self.__dict__.get("_graphs") or {}
+        for key in [k for k in graphs if k[-1] == "tmp_cls"]:               # (their nodes hold the previous cache's addresses)
+            self._drop_graph(graphs.pop(key))
+        self.template_cache = TemplateCache({int(c): {k: d[k] for k in ("feats", "occupied_voxels", "v2p_maps")}
+                                             for c, d in templates.items()}, S, self.n_tmp)
+        self._current_template_cache(self._fold())
+        return self.template_cache
+
+    def _current_template_cache(self, f):
+        """the cache with rows that belong to the present weights (f = self._fold(), called first: it notices changed weights)"""
+        cache = self.template_cache
+        dev = self.regressor_rot.layers[0].weight.device
+        if dev.type != "cuda":
+            raise RuntimeError("dcl-net_amd.Network runs on the GPU only: call .cuda() first (no CPU fallback)")
+        ver = self.__dict__.get("_fold_version")
+        if cache.valid and cache.version == ver and cache.storage is not None and cache.storage.device == dev:
+            return cache
+        cache.allocate(dev)
+        unit = self.unit_voxel_extent
+        assert unit[0] == unit[1] == unit[2], "anisotropic voxels: use fused=False"
+        off = float(np.float32(-0.5 * unit[0] * VOXEL_NUM_LIMIT[0]))
+        extents = [float(np.float32(unit[0] * sc)) for sc in SCALE_LISTS]
+        n = self.n_tmp
+        with torch.no_grad():
+            for c in cache.class_ids:
+                d = cache.inputs[c]
+                feats = d["feats"].to(dev).float().contiguous()
+                v2p = d["v2p_maps"].to(dev).int().contiguous()
+                occ = d["occupied_voxels"].to(dev).int().contiguous()
+                run = ops.BackboneRun(occ, 1, cache.S)
+                run.set_counts(run.counts_dev.cpu().tolist())              # (one read-back per class, once per set of weights)
+                run.features(ops.voxelize_fp(feats, v2p, self.voxelization_mode), *f["backbone_tmp_ptrs"])
+                pb4 = torch.cat([torch.zeros((n, 1), dtype=torch.float32, device=dev), feats[:, 4:7]], 1)
+                pf = run.point_features(pb4, extents, off)
+                act = self._disengage_buffers("Yo", n, dev, fuse=None)     # fuse=None: the V stack stays fp32
+                self._disengage(f, "Yo", pf, act)
+                dst = cache.storage[cache.slot[c]]
+                for tag, col, width in TemplateCache.BLOCKS:
+                    dst[:, col:col + width].copy_(feats[:, 4:7] if tag == "xyz" else act["Yo" + tag])
+        cache.valid, cache.version = True, ver
+        return cache
+
+    def _class_ids(self, data, cache, b, dev):
+        """data["tmp_cls"] -> (b,) int32 class ids on the device.  A device tensor is taken as it is (never read back: an id
+        that is not cached shows in pred["template_miss"]); host ids are validated here, by name."""
+        ids = data["tmp_cls"]
+        if torch.is_tensor(ids) and ids.is_cuda:
+            if ids.dim() != 1 or ids.numel() != b or ids.dtype not in (torch.int32, torch.int64):
+                raise ValueError('data["tmp_cls"] must hold one integer class id per crop (%d), got %s %s'
+                                 % (b, ids.dtype, tuple(ids.shape)))
+            return ids if ids.dtype == torch.int32 and ids.is_contiguous() else ids.int().contiguous()
+        host = [int(v) for v in (ids.reshape(-1).tolist() if torch.is_tensor(ids) else np.asarray(ids).reshape(-1).tolist())]
+        if len(host) != b:
+            raise ValueError('data["tmp_cls"] must hold one class id per crop (%d), got %d' % (b, len(host)))
+        for v in host:
+            if v not in cache.slot:
+                raise ValueError("class %d is not in the template cache (cached: %s)" % (v, cache.class_ids))
+        return torch.tensor(host, dtype=torch.int32).to(dev, non_blocking=True)
+
+    def _cached_call(self, data, f, b, S, dev):
+        """what a call with data["tmp_cls"] deals from: (the cache at the present weights, the (b,) int32 class ids on the device)"""
+        self._check_cached_call()
+        cache = self._current_template_cache(f)
+        if S != cache.S:
+            raise ValueError("the template cache was made for a %d^3 grid, this call has %d^3" % (cache.S, S))
+        return cache, self._class_ids(data, cache, b, dev)
+
+    def _check_cached_call(self):
+        if not self.fused:
+            raise ValueError('data["tmp_cls"]: the template cache serves the fused pipeline only (fused=True)')
+        if self.training:
+            raise ValueError('data["tmp_cls"]: the template cache is eval-mode only (train-mode BatchNorms use batch statistics)')
+        if self.template_cache is None:
+            raise ValueError('data["tmp_cls"] without a template cache: call net.cache_templates(templates, voxel_num_limit) first')
+
+    def _template_blocks(self, act, pts_tmp):
+        """the destinations of a call's one ops.template_rows launch, in TemplateCache.BLOCKS order"""
+        dst = {"p1": act["Yop1"], "m1": act["Yom1"], "p2": act["Yop2"], "m2": act["Yom2"], "xyz": pts_tmp}
+        return [(col, dst[tag]) for tag, col, _ in TemplateCache.BLOCKS]
+
     # ------------------------------------------------------------------ fused pipeline
     @staticmethod
     def _lin_relu(x, Wt, bias):
@@ -438,6 +596,12 @@ class Network(nn.Module):
             raise RuntimeError("dcl-net_amd.Network runs on the GPU only: call .cuda() first (no CPU fallback)")
         b = int(data["batch_offsets"].size(0)) - 1
         S = int(np.asarray(data["voxel_num_limit"]).astype(np.int64)[0])
+        # A call that carries class ids (data["tmp_cls"]) instead of template clouds runs NO template-side work: its Yo
+        # activations and points_tmp are dealt out of the per-class cache by one launch on the caller's stream (cache_templates)
+        cached = "tmp_cls" in data
+        sides = ("inp",) if cached else ("inp", "tmp")
+        if cached:
+            tcache, cls_dev = self._cached_call(data, f, b, S, dev)
         # Schedule.  (1) The two backbones are independent until the correspondence attention: each side has its own HIP
         # stream (input conversion, geometry, features, point read-out); the dense half runs on the caller's stream and
         # starts a side's disengage GEMMs as soon as that side is done.  (2) With async_inputs the side streams do not wait
@@ -445,11 +609,11 @@ class Network(nn.Module):
         # (3) Optional chunking of the sparse half (pipeline_chunks, measured slower).  One host read-back of the level sizes,
         # made on a side stream.  single_stream=True switches all overlap off.
         main = torch.cuda.current_stream(dev)
-        sstream = {"inp": self._side_stream(dev, 0), "tmp": self._side_stream(dev, 1)}
+        sstream = {s: self._side_stream(dev, i) for i, s in enumerate(("inp", "tmp")) if s in sides}
         single = sstream["inp"] is main
         K = self._pipeline_chunks(b)
         bc = b // K
-        on_device = all(data[s][k].is_cuda for s in ("inp", "tmp") for k in ("feats", "v2p_maps", "occupied_voxels"))
+        on_device = all(data[s][k].is_cuda for s in sides for k in ("feats", "v2p_maps", "occupied_voxels"))
         decoupled = self.async_inputs and on_device and not single
         for st in sstream.values():
             if not decoupled:
@@ -497,7 +661,7 @@ class Network(nn.Module):
         off = float(np.float32(-0.5 * unit[0] * VOXEL_NUM_LIMIT[0]))
         extents = [float(np.float32(unit[0] * sc)) for sc in SCALE_LISTS]
         done = {}
-        if self.pair_features and K == 1:
+        if self.pair_features and K == 1 and not cached:
             # Both sides' geometry first (each on its stream, staging underneath), ONE wait for the 16 level sizes, then the
             # feature stage of BOTH backbones as one launch sequence -- every layer one launch over both sides' tiles -- on the
             # observed side's stream; the two read-outs run side by side again.
@@ -543,10 +707,12 @@ class Network(nn.Module):
         # 3.2 ms instead of 0.13, the sparse prefix of the stress step is GPU time, not host time).
         both_first = (self.HEAD_ORDER == 1 if self.HEAD_ORDER is not None else b * max(self.n_inp, self.n_tmp) <= 65536) and not paired
         if both_first:
-            for side in ("inp", "tmp"):
+            for side in sides:
                 geometry(side)
                 stage(side)
         for side, bb in (() if paired else (("inp", "backbone_inp"), ("tmp", "backbone_tmp"))):
+            if side not in sides:
+                continue
             n = npts[side]
             if not both_first:
                 geometry(side)
@@ -566,10 +732,18 @@ class Network(nn.Module):
         act = {}
         tail_par = (not self.single_stream and not self.async_inputs and self._tail_parallel(b, launch_by_launch=True))
         for side, key in (("Xc", "inp"), ("Yo", "tmp")):
-            act.update(self._disengage_buffers(side, b * npts[key], dev, fuse=(b, 2 if tail_par else 1) if K == 1 else None))
+            # (a cached template side keeps its V stack fp32 -- fuse=None: the rows are dealt as floats, and the attention takes
+            #  V1 as given, splitting it itself where it runs the split-bf16 kernel)
+            fuse = (b, 2 if tail_par else 1) if K == 1 and key in sides else None
+            act.update(self._disengage_buffers(side, b * npts[key], dev, fuse=fuse))
+        if cached:
+            pts["tmp"] = torch.empty((b, self.n_tmp, 3), dtype=torch.float32, device=dev)
+            ops.template_rows(tcache.rows, tcache.lut, cls_dev, self._template_blocks(act, pts["tmp"].view(-1, 3)), tcache.miss)
         mark("sparse issued")
         for c in range(K):                                                     # dense stage 1, chunk by chunk on main
             for side, key in (("Xc", "inp"), ("Yo", "tmp")):
+                if key not in sides:
+                    continue
                 main.wait_event(done[key, c])
                 rows = slice(c * bc * npts[key], (c + 1) * bc * npts[key])
                 self._disengage(f, side, pf[key][rows], act, rows)
@@ -583,6 +757,8 @@ class Network(nn.Module):
         tail_side = sstream["inp"] if tail_par else None
         prediction = self._dense_tail(f, act, b, dev, side=tail_side)
         mark("dense issued")
+        if cached:
+            prediction["template_miss"] = tcache.miss       # a device tensor, like crop_overflow: no synchronisation here
         if self.mode != "test":
             prediction["sym_flag"] = data["flags"].to(dev)
         data["labels"]["points_tmp"] = pts["tmp"]
@@ -832,26 +1008,33 @@ class Network(nn.Module):
         dev = self.regressor_rot.layers[0].weight.device
         b = int(data["batch_offsets"].size(0)) - 1
         S = int(np.asarray(data["voxel_num_limit"]).astype(np.int64)[0])
-        need_ma = {s: int(data[s]["v2p_maps"].shape[1]) - 1 for s in ("inp", "tmp")}
-        key = (b, self.n_inp, self.n_tmp, S)
+        # the cached form (data["tmp_cls"]: class ids instead of template clouds, cache_templates) is a graph of its own under the
+        # same key rules: the observed side's stages, one template_rows node, the tail
+        cached = "tmp_cls" in data
+        sides = ("inp",) if cached else ("inp", "tmp")
+        tcache = cls_dev = None
+        if cached:
+            tcache, cls_dev = self._cached_call(data, f, b, S, dev)
+        need_ma = {s: int(data[s]["v2p_maps"].shape[1]) - 1 for s in sides}
+        key = self._graph_key(b, S, cached)
         cache = self.__dict__.setdefault("_graphs", {})
         ent = cache.pop(key, None)                                           # re-inserted below: dict order = recency
-        if ent is None or any(need_ma[s] > ent["ma"][s] for s in ("inp", "tmp")):
+        if ent is None or any(need_ma[s] > ent["ma"][s] for s in sides):
             self._drop_graph(ent)                                            # an outgrown capture is released first
             ent = None
             while len(cache) >= self.MAX_GRAPHS:                             # capacity-sized buffers per batch size: bounded
                 self._drop_graph(cache.pop(next(iter(cache))))               # least recently used
-            ent = self._capture(f, dev, b, S, {s: max(32, 2 * need_ma[s]) for s in ("inp", "tmp")})
+            ent = self._capture(f, dev, b, S, {s: max(32, 2 * need_ma[s]) for s in sides}, tcache)
         cache[key] = ent
         # resident inputs go through ops.pad_copy_many, which wants dense 2-D rows of 4-byte elements (int64 voxel rows are
         # narrowed); anything else -- host tensors, column slices, other dtypes -- takes the copy_() staging below
         def stageable(t, dtypes):
             return t.is_cuda and t.dim() == 2 and t.stride(1) == 1 and t.dtype in dtypes
         on_dev = all(stageable(data[s]["feats"], (torch.float32,)) and stageable(data[s]["v2p_maps"], (torch.int32,)) and
-                     stageable(data[s]["occupied_voxels"], (torch.int32, torch.int64)) for s in ("inp", "tmp"))
+                     stageable(data[s]["occupied_voxels"], (torch.int32, torch.int64)) for s in sides)
         if on_dev:                                     # resident inputs: all eight staging copies / fills in one launch
-            jobs = []
-            for s in ("inp", "tmp"):
+            jobs = [(ent["cls"].view(1, b), cls_dev.view(1, b))] if cached else []    # (the class ids ride along)
+            for s in sides:
                 st, d = ent[s], data[s]
                 # (capacity-form crops carry their live row count on the device: copied, not read)
                 v0 = d["v0_dev"].view(1, 1) if "v0_dev" in d else int(d["occupied_voxels"].shape[0])
@@ -861,7 +1044,9 @@ class Network(nn.Module):
             ops.pad_copy_many(jobs)
         else:
             assert "v0_dev" not in data["inp"], "capacity-form crops must be resident, dense CUDA tensors"
-            for s, n in (("inp", self.n_inp), ("tmp", self.n_tmp)):
+            if cached:
+                ent["cls"].copy_(cls_dev, non_blocking=True)
+            for s in sides:
                 st, d = ent[s], data[s]
                 v0 = int(d["occupied_voxels"].shape[0])
                 st["feats"].copy_(d["feats"], non_blocking=True)
@@ -886,7 +1071,7 @@ class Network(nn.Module):
                "pts_inp": torch.empty((b, self.n_inp, 3), dtype=torch.float32, device=dev)}
         ops.pad_copy_many([(res["trans_pred"], o["trans_pred"]), (res["rot_pred"], o["rot_pred"].reshape(b, 9)),
                            (res["conf"], o["conf"]), (res["F"], F.reshape(b * self.n_inp, 256)),
-                           (res["pts_tmp"].view(b * self.n_tmp, 3), ent["tmp"]["feats"][:, 4:7]),
+                           (res["pts_tmp"].view(b * self.n_tmp, 3), ent["pts_tmp"] if cached else ent["tmp"]["feats"][:, 4:7]),
                            (res["pts_inp"].view(b * self.n_inp, 3), ent["inp"]["feats"][:, 4:7])])
         out = {"trans_pred": res["trans_pred"], "rot_pred": res["rot_pred"], "conf": res["conf"],
                "F_Xo_p": res["F"].transpose(1, 2)}
@@ -903,7 +1088,13 @@ class Network(nn.Module):
             # travels WITH the predictions (a 1-element int32 device tensor, no synchronisation here); a caller that tabulates
             # these poses checks it once after its own synchronisation
             out["crop_overflow"] = data["inp"]["vi_info"][2:3]
+        if cached:
+            out["template_miss"] = tcache.miss                               # likewise: a device flag, read by the caller if at all
         return out
+
+    def _graph_key(self, b, S, cached):
+        """key of a captured whole-forward graph: the call's shape, and its form where it is the cached one"""
+        return (b, self.n_inp, self.n_tmp, S) + (("tmp_cls",) if cached else ())
 
     def _select_capture(self, ent, f, dev, b, S):
         """Which capture of a new whole-forward graph is kept (one-time cost per captured batch size).  A graph's second branch runs
@@ -932,15 +1123,17 @@ class Network(nn.Module):
             self._pair_features = self.pair_features
             self.single_stream = bool(one_stream) or keep
             try:
-                cand = self._capture(f, dev, b, S, ma)
+                cand = self._capture(f, dev, b, S, ma, tcache)
             finally:
                 self.single_stream, self._pair_features = keep, keep_pf
             cand.pop("fresh", None)
-            for sd in ("inp", "tmp"):
+            for sd in ma:                                          # (the cached form stages the observed side and the class ids)
                 for k in ("feats", "occ", "v2p", "v0", "pb4"):
                     cand[sd][k].copy_(src[sd][k])
+            if "cls" in src:
+                cand["cls"].copy_(src["cls"])
             return cand
-        ma = dict(ent["ma"])
+        ma, tcache = dict(ent["ma"]), ent.get("tcache")            # (read now: a dropped entry is emptied)
         best, t_best = ent, timed(ent)
         seen = [("two branches", t_best)]
         ref = capture(True, best)
@@ -969,13 +1162,23 @@ class Network(nn.Module):
         best["capture_ms"] = [(k, round(x * 1e3, 3)) for k, x in seen]
         return best
 
-    def _capture(self, f, dev, b, S, ma):
+    def _capture(self, f, dev, b, S, ma, tcache=None):
+        """tcache (a TemplateCache): the cached form -- `ma` names the observed side only, no template-side staging buffers, and
+        the body is the observed side's five stages, ONE template_rows node that reads the staged class ids, then the tail"""
         unit = self.unit_voxel_extent
         assert unit[0] == unit[1] == unit[2]
         off = float(np.float32(-0.5 * unit[0] * VOXEL_NUM_LIMIT[0]))
         extents = [float(np.float32(unit[0] * sc)) for sc in SCALE_LISTS]
         ent = {"ma": ma}
+        cached = tcache is not None
+        if cached:
+            ent["tcache"] = tcache
+            ent["cls"] = torch.zeros(b, dtype=torch.int32, device=dev)
+            ent["cls"].fill_(tcache.class_ids[0])                          # (the warm-up runs and the capture deal a cached class)
+            ent["pts_tmp"] = torch.zeros((b * self.n_tmp, 3), dtype=torch.float32, device=dev)
         for s, n in (("inp", self.n_inp), ("tmp", self.n_tmp)):
+            if s not in ma:
+                continue
             st = {"feats": torch.zeros((b * n, 7), dtype=torch.float32, device=dev),
                   "occ": torch.zeros((b * n, 4), dtype=torch.int32, device=dev),
                   "v2p": torch.zeros((b * n, ma[s] + 1), dtype=torch.int32, device=dev),
@@ -998,13 +1201,14 @@ class Network(nn.Module):
             par_dense = self._tail_parallel(b)
             stamp = self._stage_done                               # a no-op; tools/graph_timeline.py hangs time stamps on it
             stamp("start", main)
-            side_stream.wait_stream(main)
+            if not cached:
+                side_stream.wait_stream(main)
             # The two branches are issued stage by stage, alternating: a graph launch hands its nodes to the queues in
             # creation order, so a branch captured as a whole after the other one starts ~50 nodes late on replay.
-            sides = (("inp", "backbone_inp", main, "Xc"), ("tmp", "backbone_tmp", side_stream, "Yo"))
+            sides = (("inp", "backbone_inp", main, "Xc"), ("tmp", "backbone_tmp", side_stream, "Yo"))[:1 if cached else 2]
             xs, pb4s = {}, {}
             for stage in range(5):
-                if stage == 2 and self.pair_features:
+                if stage == 2 and self.pair_features and not cached:
                     # the feature stage of both backbones as ONE launch sequence on the main branch (join, run, fork again)
                     main.wait_stream(side_stream)
                     ops.backbone_features_pair(ent["inp"]["run"], xs["inp"], f["backbone_inp_ptrs"],
@@ -1027,7 +1231,14 @@ class Network(nn.Module):
                             act.update(self._disengage_buffers(dside, st["pf"].shape[0], dev, fuse=(b, 2 if par_dense else 1)))
                             self._disengage(f, dside, st["pf"], act)
                     stamp("%s stage %d done" % (s, stage), stream)
-            main.wait_stream(side_stream)                                  # join
+            if cached:
+                # the template side is ONE node: the staged class ids' cached rows into the Yo buffers (fp32 V stack) and the
+                # template points -- no second branch before the tail, so nothing to join
+                act.update(self._disengage_buffers("Yo", b * self.n_tmp, dev, fuse=None))
+                ops.template_rows(tcache.rows, tcache.lut, ent["cls"], self._template_blocks(act, ent["pts_tmp"]), tcache.miss)
+                stamp("template rows done", main)
+            else:
+                main.wait_stream(side_stream)                              # join
             out_ = self._dense_tail(f, act, b, dev, side=side_stream if par_dense else None)
             stamp("end", main)
             return out_
@@ -1244,7 +1455,7 @@ class Network(nn.Module):
         by launch.  So with a FULL cache a new size is only admitted (evicting the least recently used one) once it has been
         seen GRAPH_ADMIT times; until then its calls go launch by launch."""
         S = int(np.asarray(data["voxel_num_limit"]).astype(np.int64)[0])
-        key = (b, self.n_inp, self.n_tmp, S)
+        key = self._graph_key(b, S, "tmp_cls" in data)
         cache = self.__dict__.setdefault("_graphs", {})
         if key in cache or len(cache) < self.MAX_GRAPHS:
             return True
@@ -1267,7 +1478,13 @@ class Network(nn.Module):
 
     def forward(self, data):
         """eval(): the fused inference pipeline -- outputs carry no autograd graph, whether or not the caller wrapped the call
-        in torch.no_grad() (tools/test_LM.py:110 does not).  train() (or fused=False): the module path, differentiable."""
+        in torch.no_grad() (tools/test_LM.py:110 does not).  train() (or fused=False): the module path, differentiable.
+        data["tmp_cls"] -- (b,) class ids, a device tensor (taken as it is) or a host tensor / list (validated: ValueError names
+        an unknown class) -- selects the cached form of the eval pipeline (cache_templates): data["tmp"] is then neither needed
+        nor read, data["labels"]["points_tmp"] comes from the cache and pred["template_miss"] is its device-side miss flag.
+        Without a cache, in training mode or with fused=False it raises ValueError.  Routing is otherwise the same."""
+        if "tmp_cls" in data:
+            self._check_cached_call()
         if self.fused and not self.training:
             b = int(data["batch_offsets"].size(0)) - 1
             if self.replays_graph(b) and self._admit_graph(b, data):

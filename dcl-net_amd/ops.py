@@ -152,6 +152,78 @@ def pad_copy_many(jobs):
     N.check(N.lib().dcl_pad_copy_many(arr, len(jobs), N.stream()), "pad_copy_many")
 
 
+# ------------------------------------------------------------------------------------ per-class template cache
+TEMPLATE_MAX_BLOCKS = 8         # include/dclnet_hip.h: DCL_TEMPLATE_MAX_BLOCKS
+
+
+class _TemplateBlock(C.Structure):
+    _fields_ = [("src_col", C.c_int32), ("width", C.c_int32), ("dst", C.c_void_p), ("dst_pitch", C.c_int64)]
+
+
+def _template_rows(cache, lut, cls, blocks, miss, host):
+    what = "template_rows_host" if host else "template_rows"
+    dev = cache.device
+    if host:
+        if cache.is_cuda:
+            raise RuntimeError("%s is the host twin: pass CPU tensors" % what)
+    else:
+        N.need_cuda(cache)
+    if not (cache.dim() == 3 and cache.dtype == torch.float32 and cache.stride(2) == 1 and cache.shape[0] >= 1):
+        raise ValueError("%s: cache must be float32 (C, n_tmp, columns) with unit column stride" % what)
+    n_tmp, cols = int(cache.shape[1]), int(cache.shape[2])
+    row_floats = int(cache.stride(1)) if n_tmp > 1 else cols
+    class_floats = int(cache.stride(0)) if cache.shape[0] > 1 else n_tmp * row_floats
+    if not (lut.dim() == 1 and lut.dtype == torch.int32 and lut.is_contiguous() and lut.device == dev):
+        raise ValueError("%s: lut must be a contiguous int32 vector on the cache's device" % what)
+    if not torch.is_tensor(cls):
+        cls = torch.as_tensor(cls, dtype=torch.int64)
+    if cls.dim() != 1 or cls.dtype not in (torch.int32, torch.int64) or cls.numel() < 1:
+        raise ValueError("%s: cls must be a non-empty (b,) vector of int32 or int64 class ids" % what)
+    # (ids the caller keeps on the host, or as int64, are narrowed and uploaded here; device int32 ids are taken as they are)
+    cls = cls.to(device=dev, dtype=torch.int32).contiguous()
+    b = int(cls.numel())
+    if miss is None:
+        miss = torch.zeros(1, dtype=torch.int32, device=dev)
+    if not (miss.dtype == torch.int32 and miss.numel() == 1 and miss.device == dev):
+        raise ValueError("%s: miss must be a 1-element int32 tensor on the cache's device" % what)
+    if not 1 <= len(blocks) <= TEMPLATE_MAX_BLOCKS:
+        raise ValueError("%s: 1 .. %d column blocks" % (what, TEMPLATE_MAX_BLOCKS))
+    arr = (_TemplateBlock * len(blocks))()
+    for j, (src_col, dst) in enumerate(blocks):
+        if not (torch.is_tensor(dst) and dst.dim() == 2 and dst.dtype == torch.float32 and dst.device == dev and
+                dst.shape[0] == b * n_tmp and (dst.stride(1) == 1 or dst.shape[1] == 1)):
+            raise ValueError("%s: block %d: dst must be float32 (b * n_tmp, width) rows with unit column stride on the cache's "
+                             "device" % (what, j))
+        width = int(dst.shape[1])
+        if int(src_col) < 0 or int(src_col) + width > cols:
+            raise ValueError("%s: block %d: columns %d .. %d lie outside the cache's %d" % (what, j, src_col, src_col + width, cols))
+        q = arr[j]
+        q.src_col, q.width, q.dst = int(src_col), width, dst.data_ptr()
+        q.dst_pitch = int(dst.stride(0)) if dst.shape[0] > 1 else width
+    a = (N.ptr(cache), class_floats, row_floats, n_tmp, N.ptr(lut), int(lut.numel()), N.ptr(cls), b, arr, len(blocks), N.ptr(miss))
+    if host:
+        N.check(N.lib().dcl_template_rows_host(*a), what)
+    else:
+        N.check(N.lib().dcl_template_rows(*(a + (N.stream(),))), what)
+    return miss
+
+
+def template_rows(cache, lut, cls, blocks, miss=None):
+    """Deal cached class rows into a call's activation buffers, ONE launch (csrc/template_rows.hip; contract in
+    include/dclnet_hip.h at dcl_template_rows).  cache (C, n_tmp, columns) float32 CUDA, possibly a view with padded row / class
+    pitches; lut (lut_len,) int32 CUDA, class id -> cache slot or -1; cls (b,) class ids -- an int32 CUDA tensor is taken as it
+    is (nothing is read back), an int64 or host tensor or a list is narrowed and uploaded; blocks = [(src_col, dst), ...] with
+    dst a (b * n_tmp, width) float32 CUDA tensor, possibly a column block of a wider row-major buffer: dst[i * n_tmp + r, c] =
+    cache[lut[cls[i]], r, src_col + c].  Blocks must not overlap.  miss: a 1-element int32 CUDA tensor that is set to 1 when an
+    id is outside the table or not cached (that crop's rows are zeros); None makes a zeroed one.  Returns miss."""
+    return _template_rows(cache, lut, cls, blocks, miss, False)
+
+
+def template_rows_host(cache, lut, cls, blocks, miss=None):
+    """template_rows on CPU tensors: the same contract in plain C++ (dcl_template_rows_host; what the tests compare with)"""
+    return _template_rows(cache, lut, cls, blocks, miss, True)
+
+
 # ------------------------------------------------------------------------------------ rulebooks
 def grid_words(batch, S):
     return (batch * S * S * S + 31) // 32

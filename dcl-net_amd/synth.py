@@ -74,6 +74,22 @@ def class_template(cls, M):
     return pts.astype(np.float32), rgb
 
 
+def class_template_side(cls, M, unit=0.006, S=64, mode=4, voxelize_idx=None):
+    """the ONE-crop data["tmp"] of class_template(cls, M) -- feats (M, 7) [1, rgb, xyz], occupied_voxels, p2v_maps, v2p_maps of
+    crop index 0, exactly the template side make_batch gives a batch of that one class: an entry of the dict
+    Network.cache_templates takes"""
+    if voxelize_idx is None:
+        from . import ops
+        voxelize_idx = ops.voxelize_idx
+    half = 0.5 * unit * S
+    tmp, tmp_rgb = class_template(cls, M)
+    vox = ((tmp + np.float32(half)) / np.float32(unit)).astype(np.int64)
+    feats = np.concatenate([np.ones((M, 1), np.float32), tmp_rgb, tmp], 1)
+    coords = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.zeros((M, 1), np.int64), vox], 1)))
+    occ, p2v, v2p = voxelize_idx(coords, 1, mode)
+    return {"feats": torch.from_numpy(feats), "occupied_voxels": occ, "p2v_maps": p2v, "v2p_maps": v2p}
+
+
 def make_crop(i, N, M, unit=0.006, S=64):
     """crop i: class i % 21, seed 1000+i."""
     cls = i % N_CLASSES

@@ -1310,6 +1310,38 @@ int dcl_adam_step(int n_tensors, const dclOptimTensor *table, int n_chunks, cons
 int dcl_legacy_permutation_heads(uint32_t *key624, int32_t *pos_io, const int32_t *m, int k, int n, int64_t *out,
                                  int32_t *scratch);
 
+/* ---------------------------------------------------- per-class template cache ---
+ * Deals cached class rows into a call's activation buffers in ONE launch (csrc/template_rows.hip; models/DCL_Net.py:
+ * Network.cache_templates keeps, per object class, what the template half of an eval-mode forward leaves behind).
+ *   cache   device fp32, C classes of n_tmp rows: element (s, r, k) at cache[s * class_floats + r * row_floats + k].
+ *           row_floats is the row PITCH in floats (the network keeps 643 columns [p1 256 | m1 64 | p2 256 | m2 64 | xyz 3] in
+ *           rows of 644, so that rows stay 16-byte aligned); class_floats >= n_tmp * row_floats.
+ *   lut     device int32 (lut_len): class id -> cache slot, -1 where the class is absent.  A slot must be < C.
+ *   cls     device int32 (b): the crops' class ids.  They are read by the kernel only: no read-back on this path.
+ *   blocks  host array of nblocks <= DCL_TEMPLATE_MAX_BLOCKS column blocks: for crop i < b, row r < n_tmp and c < width
+ *               dst[(i * n_tmp + r) * dst_pitch + c] = cache[lut[cls[i]]][r][src_col + c].
+ *           A destination is a column block of a wider row-major buffer (dst_pitch floats per row); columns outside a block
+ *           are not touched.  Blocks must not overlap each other.
+ *   miss    device int32: a class id outside [0, lut_len) or with lut[id] < 0 is a MISS -- that crop's rows are written as +0
+ *           and *miss is set to 1 by an ordinary store (every writer stores the same value); nothing is read out of range.
+ *           A call without a miss does not write *miss (the caller zeroes it once).
+ * A block whose dst, src_col, width and dst_pitch -- and the cache's base, row_floats and class_floats -- are multiples of 16
+ * bytes moves 16 bytes per lane; any other block goes float by float, with the same result.  No atomics, no scratch, no LDS;
+ * the grid is sized from b * n_tmp * sum(width); capturable.  DCL_EINVAL before any GPU work for a NULL or misaligned (4-byte)
+ * pointer, b, n_tmp or nblocks < 1, nblocks > DCL_TEMPLATE_MAX_BLOCKS, lut_len < 0, row_floats < 1, class_floats < n_tmp *
+ * row_floats, and per block src_col < 0, width < 1, dst_pitch < width or src_col + width > row_floats.
+ * dcl_template_rows_host is the same contract in plain C++ on HOST pointers (what the tests compare with; no GPU call).      */
+#define DCL_TEMPLATE_MAX_BLOCKS 8
+typedef struct {
+  int32_t src_col, width;
+  float *dst;
+  int64_t dst_pitch;
+} DclTemplateBlock;
+int dcl_template_rows(const float *cache, int64_t class_floats, int row_floats, int n_tmp, const int32_t *lut, int lut_len,
+                      const int32_t *cls, int b, const DclTemplateBlock *blocks, int nblocks, int32_t *miss, dclStream_t stream);
+int dcl_template_rows_host(const float *cache, int64_t class_floats, int row_floats, int n_tmp, const int32_t *lut, int lut_len,
+                           const int32_t *cls, int b, const DclTemplateBlock *blocks, int nblocks, int32_t *miss);
+
 /* The ONE measurement facility of the product library (it selects nothing and changes no result; every tuning / A-B switch
  * lives in the diagnostic library below): between _begin and _end every sparse-conv call (runner or op API) is bracketed by
  * HIP events on its launch stream; _end waits for them and returns the summed device milliseconds and the number of calls.
