@@ -16,6 +16,7 @@
 #include "common.h"
 #include "mfma_tile.h"
 #include "ortho9d.h"
+#include "refine_pose.h"
 #include <atomic>
 #include <math.h>
 
@@ -1471,6 +1472,87 @@ DCL_API int dcl_affine3_relu(int64_t rows, int c, const float *xyz, const float 
   return 0;
 }
 
+// ---- the same layer with the canonicalisation as its prologue (refine_loop(compose="device")): the row's point is taken from
+// the observed cloud and the crop's CURRENT pose on the device, cur = R^T (p - t) (obj_rigid_point, the bits of
+// dcl_rigid_points), and never stored: the launch moves the 2 * rows * c * 4 bytes of term and out, 12 bytes of pts per row
+// and the crops' 48-byte poses.  Thread = (row, float4 of channels) as above.  UNIFORM_ROW (c4 % 64 == 0: a wave's 64 threads
+// share one row, every wave starts on a multiple of 64): the row index is made a scalar, so the point, R and t are loaded once
+// per wave through the scalar cache instead of once per lane.
+template <bool UNIFORM_ROW>
+__global__ __launch_bounds__(256) void k_refine_first(long long rows, int n, int c4, const float *__restrict__ pts,
+                                                      const float *__restrict__ R, const float *__restrict__ tr,
+                                                      const float *__restrict__ W, const float4 *__restrict__ term,
+                                                      float4 *__restrict__ out) {
+  const long long total = rows * c4;
+  for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
+    int row = (int)(t / c4);                               // (rows * 3 <= INT32_MAX: checked by the entry)
+    const int q = (int)(t - (long long)row * c4);
+    if constexpr (UNIFORM_ROW) row = __builtin_amdgcn_readfirstlane(row);
+    const int crop = row / n;
+    float cur[3];
+    obj_rigid_point(R + (size_t)crop * 9, tr + (size_t)crop * 3, 1, pts + (size_t)row * 3, cur);
+    const float4 wx = reinterpret_cast<const float4 *>(W)[q], wy = reinterpret_cast<const float4 *>(W)[c4 + q],
+                 wz = reinterpret_cast<const float4 *>(W)[2 * c4 + q];
+    const float4 a = term[t];
+    float4 o;
+    o.x = refine_first_channel(cur[0], cur[1], cur[2], wx.x, wy.x, wz.x, a.x);
+    o.y = refine_first_channel(cur[0], cur[1], cur[2], wx.y, wy.y, wz.y, a.y);
+    o.z = refine_first_channel(cur[0], cur[1], cur[2], wx.z, wy.z, wz.z, a.z);
+    o.w = refine_first_channel(cur[0], cur[1], cur[2], wx.w, wy.w, wz.w, a.w);
+    out[t] = o;
+  }
+}
+
+static int refine_first_check(int b, int n, int c, const void *pts, const void *R, const void *t, const void *W3,
+                              const void *term, const void *out) {
+  if (!(b >= 0 && n >= 1 && c > 0 && c % 4 == 0)) return 1;
+  if (b == 0) return 0;
+  if (!(pts && R && t && W3 && term && out)) return 1;
+  if ((long long)b * n * 3 > INT32_MAX) return 1;
+  if ((((uintptr_t)W3 | (uintptr_t)term | (uintptr_t)out) & 15) != 0) return 1;
+  return 0;
+}
+
+DCL_API int dcl_refine_first(int b, int n, int c, const float *pts, const float *R, const float *t, const float *W3,
+                             const float *term, float *out, dclStream_t stream) {
+  DCL_CHECK_ARG(refine_first_check(b, n, c, pts, R, t, W3, term, out) == 0);
+  if (b == 0) return 0;
+  const long long rows = (long long)b * n;
+  const int c4 = c / 4, grid = dcl_grid_1d(rows * c4, 256, 256 * 32);
+  if (c4 % 64 == 0)
+    hipLaunchKernelGGL(k_refine_first<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, rows, n, c4, pts, R, t, W3,
+                       reinterpret_cast<const float4 *>(term), reinterpret_cast<float4 *>(out));
+  else
+    hipLaunchKernelGGL(k_refine_first<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, rows, n, c4, pts, R, t, W3,
+                       reinterpret_cast<const float4 *>(term), reinterpret_cast<float4 *>(out));
+  DCL_LAUNCH_CHECK();
+  return 0;
+}
+
+DCL_API int dcl_refine_first_host(int b, int n, int c, const float *pts, const float *R, const float *t, const float *W3,
+                                  const float *term, float *out) {
+  DCL_CHECK_ARG(refine_first_check(b, n, c, pts, R, t, W3, term, out) == 0);
+  for (int crop = 0; crop < b; ++crop)
+    for (int i = 0; i < n; ++i) {
+      const size_t row = (size_t)crop * n + i;
+      for (int q = 0; q < c / 4; ++q)
+        refine_first_quad(R + (size_t)crop * 9, t + (size_t)crop * 3, pts + row * 3, W3, c, q, term + row * c + 4 * q,
+                          out + row * c + 4 * q);
+    }
+  return 0;
+}
+
+DCL_API int dcl_pose_compose_host(int b, const float *R_in, const float *t_in, const float *dR, const float *dt, float *R_out,
+                                  float *t_out) {
+  DCL_CHECK_ARG(b >= 0);
+  if (b == 0) return 0;
+  DCL_CHECK_ARG(R_in && t_in && dR && dt && R_out && t_out);
+  for (int crop = 0; crop < b; ++crop)
+    pose_compose(R_in + (size_t)crop * 9, t_in + (size_t)crop * 3, dR + (size_t)crop * 9, dt + (size_t)crop * 3,
+                 R_out + (size_t)crop * 9, t_out + (size_t)crop * 3);
+  return 0;
+}
+
 DCL_API int dcl_ortho9d_to_matrix(int b, const float *o9, float *R, dclStream_t stream) {
   DCL_CHECK_ARG(b >= 0);
   if (b == 0) return 0;
@@ -1534,20 +1616,13 @@ __device__ __forceinline__ float pool_finish_one(const PoolParts &P, int c, int 
   return ((P.sA[ch] * p1 + P.tA[ch] * w0) + P.sB[ch] * p2) + P.tB[ch] * w1;
 }
 
-template <bool FROM_PARTS>
-__global__ __launch_bounds__(1024) void k_heads_l1(int b, const float *__restrict__ x, const PoolParts P, HeadWeights hw,
-                                                   float *__restrict__ h1) {
-  __shared__ float part[kHeadSlices][64];
-  __shared__ float xs[FROM_PARTS ? 1024 : 1];
+// layer 1 of workgroup (64 outputs, crop, head), the body of every input form: xv = this thread's k-slice of the crop's 1024
+// inputs (global memory or the workgroup's LDS copy), part = the workgroup's slice sums
+__device__ __forceinline__ void heads_l1_body(int b, const float *xv, const HeadWeights &hw, float *__restrict__ h1,
+                                              float (*part)[64]) {
   const int head = blockIdx.z, crop = blockIdx.y, o0 = blockIdx.x * 64;
   const int o = threadIdx.x & 63, ks = threadIdx.x >> 6;                   // 16 slices of 64 terms
   const float *w = hw.w1[head] + (size_t)(ks * 64) * 512 + o0 + o;
-  const float *xv = x + (size_t)crop * 1024 + ks * 64;
-  if constexpr (FROM_PARTS) {
-    xs[threadIdx.x] = pool_finish_one(P, 1024, crop, (int)threadIdx.x);    // (every workgroup of the crop forms the 1024 inputs itself)
-    __syncthreads();
-    xv = xs + ks * 64;
-  }
   // (all 64 weight loads of the slice in flight: in rounds of 16 a call of one crop waited four round trips here)
   float wv[64];
 #pragma unroll
@@ -1563,8 +1638,45 @@ __global__ __launch_bounds__(1024) void k_heads_l1(int b, const float *__restric
   }
 }
 
-__global__ __launch_bounds__(1024) void k_heads_l23(int b, const float *__restrict__ h1, HeadWeights hw,
-                                                    float *__restrict__ o9, float *__restrict__ t3, float *__restrict__ R) {
+template <bool FROM_PARTS>
+__global__ __launch_bounds__(1024) void k_heads_l1(int b, const float *__restrict__ x, const PoolParts P, HeadWeights hw,
+                                                   float *__restrict__ h1) {
+  __shared__ float part[kHeadSlices][64];
+  __shared__ float xs[FROM_PARTS ? 1024 : 1];
+  const int crop = blockIdx.y, ks = threadIdx.x >> 6;
+  const float *xv = x + (size_t)crop * 1024 + ks * 64;
+  if constexpr (FROM_PARTS) {
+    xs[threadIdx.x] = pool_finish_one(P, 1024, crop, (int)threadIdx.x);    // (every workgroup of the crop forms the 1024 inputs itself)
+    __syncthreads();
+    xv = xs + ks * 64;
+  }
+  heads_l1_body(b, xv, hw, h1, part);
+}
+
+// third input form (dcl_refine_heads): the pooled feature still as dcl_linear_pool_fwd's T tile partials, part (b*T, 1024);
+// every workgroup of the crop adds them itself, one ascending chain from tile 0 (refine_pose.h: tile_chain)
+__global__ __launch_bounds__(1024) void k_heads_l1_tiles(int b, int T, const float *__restrict__ tiles, HeadWeights hw,
+                                                         float *__restrict__ h1) {
+  __shared__ float part[kHeadSlices][64];
+  __shared__ float xs[1024];
+  const int crop = blockIdx.y, ks = threadIdx.x >> 6;
+  xs[threadIdx.x] = tile_chain(tiles + (size_t)crop * T * 1024 + threadIdx.x, T, 1024);
+  __syncthreads();
+  heads_l1_body(b, xs + ks * 64, hw, h1, part);
+}
+
+// the pose a COMPOSE launch of layers 2 + 3 reads and writes (dcl_refine_heads); in and out never overlap
+struct PoseIO {
+  const float *R_in, *t_in;
+  float *R_out, *t_out;
+};
+
+// layers 2 + 3 of workgroup (crop, head).  COMPOSE: the pose composition as the epilogue -- the rotation workgroup writes
+// R_out = R_in dR, the translation workgroup t_out = R_in dt + t_in (refine_pose.h: pose_compose); R (the delta rotation) is
+// required then.
+template <bool COMPOSE>
+__device__ __forceinline__ void heads_l23_body(int b, const float *__restrict__ h1, const HeadWeights &hw, float *__restrict__ o9,
+                                               float *__restrict__ t3, float *__restrict__ R, const PoseIO &io) {
   __shared__ float xs[512], part[8][128], h2[128], part3[16][12], o9s[12];
   const int head = blockIdx.y, crop = blockIdx.x;
   const float *xin = h1 + ((size_t)head * b + crop) * 512;
@@ -1604,12 +1716,40 @@ __global__ __launch_bounds__(1024) void k_heads_l23(int b, const float *__restri
       for (int i = 0; i < 16; i += 2 * d) v[i] = v[i] + v[i + d];
     const float a = v[0] + hw.b3[head][threadIdx.x];
     if (head == 0) { o9[(size_t)crop * 9 + threadIdx.x] = a; o9s[threadIdx.x] = a; }
-    else t3[(size_t)crop * 3 + threadIdx.x] = a;
+    else {
+      t3[(size_t)crop * 3 + threadIdx.x] = a;
+      if constexpr (COMPOSE) o9s[threadIdx.x] = a;
+    }
   }
-  if (head == 0 && R != nullptr) {                     // ortho9d2matrix of this crop right here: one launch less on the path
+  if constexpr (COMPOSE) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const float *Rc = io.R_in + (size_t)crop * 9;
+      if (head == 0) {
+        float dRl[9];
+        ortho9d_one(o9s, dRl, 0);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[(size_t)crop * 9 + k] = dRl[k];
+        pose_compose(Rc, nullptr, dRl, nullptr, io.R_out + (size_t)crop * 9, nullptr);
+      } else {
+        pose_compose(Rc, io.t_in + (size_t)crop * 3, nullptr, o9s, nullptr, io.t_out + (size_t)crop * 3);
+      }
+    }
+  } else if (head == 0 && R != nullptr) {              // ortho9d2matrix of this crop right here: one launch less on the path
     __syncthreads();
     if (threadIdx.x == 0) ortho9d_one(o9s, R + (size_t)crop * 9, 0);
   }
+}
+
+__global__ __launch_bounds__(1024) void k_heads_l23(int b, const float *__restrict__ h1, HeadWeights hw,
+                                                    float *__restrict__ o9, float *__restrict__ t3, float *__restrict__ R) {
+  heads_l23_body<false>(b, h1, hw, o9, t3, R, PoseIO{});
+}
+
+__global__ __launch_bounds__(1024) void k_heads_l23_compose(int b, const float *__restrict__ h1, HeadWeights hw,
+                                                            float *__restrict__ o9, float *__restrict__ t3,
+                                                            float *__restrict__ R, PoseIO io) {
+  heads_l23_body<true>(b, h1, hw, o9, t3, R, io);
 }
 
 // ---- the confidence regressor as ONE launch (models/DCL_Net.py:115-126, 217-218: Head_MultiLayerPerceptron [128, 128, 128, 1],
@@ -1737,6 +1877,28 @@ DCL_API int dcl_pose_heads(int b, const float *pooled, const float *const *rot_l
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_heads_l1<false>, dim3(512 / 64, b, 2), dim3(1024), 0, s, b, pooled, PoolParts{}, hw, h1_scratch);
   hipLaunchKernelGGL(k_heads_l23, dim3(b, 2), dim3(1024), 0, s, b, h1_scratch, hw, o9, trans, R);
+  DCL_LAUNCH_CHECK();
+  return 0;
+}
+
+DCL_API int dcl_refine_heads(int b, int T, const float *part, const float *const *rot_layers, const float *const *trans_layers,
+                             float *h1_scratch, const float *R_in, const float *t_in, float *R_out, float *t_out, float *o9,
+                             float *dt, float *dR, dclStream_t stream) {
+  DCL_CHECK_ARG(b >= 0 && b <= 65535 && T >= 1);
+  if (b == 0) return 0;
+  DCL_CHECK_ARG(part && rot_layers && trans_layers && h1_scratch && R_in && t_in && R_out && t_out && o9 && dt && dR);
+  DCL_CHECK_ARG(R_out + (size_t)b * 9 <= R_in || R_in + (size_t)b * 9 <= R_out);      // in and out are different arrays
+  DCL_CHECK_ARG(t_out + (size_t)b * 3 <= t_in || t_in + (size_t)b * 3 <= t_out);
+  HeadWeights hw;
+  for (int h = 0; h < 2; ++h) {
+    const float *const *L = h == 0 ? rot_layers : trans_layers;         // {W1t, b1, W2t, b2, W3t, b3}
+    for (int i = 0; i < 6; ++i) DCL_CHECK_ARG(L[i] != nullptr);
+    hw.w1[h] = L[0]; hw.b1[h] = L[1]; hw.w2[h] = L[2]; hw.b2[h] = L[3]; hw.w3[h] = L[4]; hw.b3[h] = L[5];
+  }
+  const PoseIO io{R_in, t_in, R_out, t_out};
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_heads_l1_tiles, dim3(512 / 64, b, 2), dim3(1024), 0, s, b, T, part, hw, h1_scratch);
+  hipLaunchKernelGGL(k_heads_l23_compose, dim3(b, 2), dim3(1024), 0, s, b, h1_scratch, hw, o9, dt, dR, io);
   DCL_LAUNCH_CHECK();
   return 0;
 }

@@ -207,10 +207,28 @@ class Refiner(nn.Module):
         return {"trans_pred": dt, "rot_pred": dR}
 
 
-def refine_loop(refiner, pred, points_inp, iteration=2, graph=False):
+COMPOSE_MODES = ("host", "device")
+
+
+def refine_loop(refiner, pred, points_inp, iteration=2, graph=False, compose="host", trajectory=False):
     """Iterative refinement of tools/test_YCBV_stage2.py:204-225 on the outputs of Network.forward:
     pred {"rot_pred","trans_pred","F_Xo_p" (b,256,n),"conf"}, points_inp (b,n,3) -> (rot (b,3,3), trans (b,3)).
-    With graph=True the whole loop is captured once per shape into a hipGraph and replayed."""
+    With graph=True the whole loop is captured once per shape into a hipGraph and replayed.
+    compose: where the pose lives between the iterations.  "host" (default): torch expressions compose it (pts - t, bmm, R @ dR:
+    about a dozen launches per iteration, five of them vendor GEMMs on b x 3 x 3 operands).  "device": the current and the next
+    pose live in device arrays rots (iteration + 1, b, 3, 3) / transs (iteration + 1, b, 3), index 0 the incoming pose, and one
+    iteration is five launches of the library's own kernels -- ops.refine_first (canonicalisation + first shared layer),
+    ops.linear, ops.linear_pool, ops.refine_heads (the tile partials added in a pinned order, both heads, R <- R dR and
+    t <- R dt + t as the epilogue) -- no torch kernel, no vendor GEMM.  Needs n % ops.LINEAR_POOL_TILE == 0 and b <= 65535
+    (ValueError otherwise; never a silent fall-back).  Not the "host" form's bits: the same formulas in other association orders.
+    trajectory=True ("device" only): also returns (rots, transs), the pose after every iteration -- what the reference's script
+    can only get by running the loop again."""
+    if compose not in COMPOSE_MODES:
+        raise ValueError('compose must be "host" or "device", got %r' % (compose,))
+    if trajectory and compose != "device":
+        raise ValueError('trajectory=True needs compose="device" (the "host" form keeps no pose but the last)')
+    if compose == "device":
+        return _refine_loop_device(refiner, pred, points_inp, int(iteration), graph, trajectory)
     f = refiner._fold()
     rot0, trans0, conf = pred["rot_pred"], pred["trans_pred"], pred["conf"]
     F_pm = pred["F_Xo_p"].transpose(1, 2)                                 # (b,n,256) (a view when fused)
@@ -268,13 +286,93 @@ def refine_loop(refiner, pred, points_inp, iteration=2, graph=False):
         return rot, trans
 
 
-def stage2_chain(model, refiner, data, iteration=2, graph=True):
+def _refine_loop_device(refiner, pred, points_inp, iteration, graph, trajectory):
+    """refine_loop(compose="device"): see there"""
+    rot0, trans0, conf = pred["rot_pred"], pred["trans_pred"], pred["conf"]
+    F_pm = pred["F_Xo_p"].transpose(1, 2)                                 # (b,n,256) (a view when fused)
+    b, n, _ = F_pm.shape
+    if n % ops.LINEAR_POOL_TILE:
+        raise ValueError('compose="device" needs n %% %d == 0 (the pooling tile: a crop is a whole number of tile partials), '
+                         'got n = %d' % (ops.LINEAR_POOL_TILE, n))
+    if b > 65535:
+        raise ValueError('compose="device" needs b <= 65535 crops (one grid row per crop), got b = %d' % b)
+    if iteration < 0:
+        raise ValueError("iteration must be >= 0, got %d" % iteration)
+    if min(conf.shape[1], 1024) != n:
+        raise ValueError('compose="device" needs one confidence per point: conf[:, :1024] has %d columns for n = %d'
+                         % (min(conf.shape[1], 1024), n))
+    f = refiner._fold()
+    T = n // ops.LINEAR_POOL_TILE
+    dev = F_pm.device
+
+    def feature_term(out=None):
+        # the feature half of the first shared layer, once per call (refine_loop: feature_term)
+        bias, W = f["MLP_share"][0][1], f["share0_feat"]
+        if F_pm.stride(2) == 1 and F_pm.stride(0) == n * F_pm.stride(1):
+            rows = F_pm.as_strided((b * n, F_pm.shape[2]), (F_pm.stride(1), 1))
+            return ops.linear(rows, W, bias, False, out=out)
+        return ops.linear(F_pm.contiguous().view(b * n, -1), W, bias, False, out=out)
+
+    def set_pose(rots, transs):
+        ops.pad_copy_many([(rots[0].view(b, 9), rot0.reshape(b, 9)), (transs[0], trans0.reshape(b, 3))])
+
+    def body(rots, transs, feat_term, conf, pts):
+        conf_w = torch.softmax(conf.unsqueeze(1), dim=2)[:, 0, :1024].contiguous()
+        for i in range(iteration):
+            h = ops.refine_first(pts, rots[i], transs[i], f["share0_xyz"], feat_term)
+            h = ops.linear(h, f["MLP_share"][1][0], f["MLP_share"][1][1], True)
+            part = ops.linear_pool(h, f["MLP_share"][2][0], f["MLP_share"][2][1], conf_w.reshape(-1), relu=True)
+            ops.refine_heads(part, T, f["regressor_rot2"], f["regressor_trans2"], rots[i], transs[i], rots[i + 1], transs[i + 1])
+
+    def pose_arrays():
+        return (torch.empty((iteration + 1, b, 3, 3), dtype=torch.float32, device=dev),
+                torch.empty((iteration + 1, b, 3), dtype=torch.float32, device=dev))
+
+    with torch.no_grad():
+        if not graph:
+            rots, transs = pose_arrays()
+            set_pose(rots, transs)
+            body(rots, transs, feature_term(), conf, ops.N.f32c(points_inp))
+        else:
+            key = (b, n, iteration, conf.shape[1], "device")
+            cache = refiner.__dict__.setdefault("_graphs", {})
+            if key not in cache:
+                static = list(pose_arrays()) + [feature_term(), conf.clone(memory_format=torch.contiguous_format),
+                                                ops.N.f32c(points_inp).clone()]
+                set_pose(static[0], static[1])
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    for _ in range(2):                                    # warm-up (allocator, lazy inits)
+                        body(*static)
+                torch.cuda.current_stream().wait_stream(s)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    body(*static)
+                cache[key] = (g, static)
+            g, static = cache[key]
+            # as in the "host" form: the feature term's GEMM runs in front of the replay, the small inputs are copied in
+            feature_term(out=static[2])
+            ops.pad_copy_many([(static[0][0].view(b, 9), rot0.reshape(b, 9)), (static[1][0], trans0.reshape(b, 3)),
+                               (static[3], conf.reshape(b, -1)), (static[4].view(b * n, 3), points_inp.reshape(b * n, 3))])
+            g.replay()
+            rots, transs = torch.empty_like(static[0]), torch.empty_like(static[1])  # (the graph's own arrays are overwritten by the next replay)
+            rows = (iteration + 1) * b
+            ops.pad_copy_many([(rots.view(rows, 9), static[0].view(rows, 9)), (transs.view(rows, 3), static[1].view(rows, 3))])
+        if trajectory:
+            return rots[-1], transs[-1], (rots, transs)
+        return rots[-1], transs[-1]
+
+
+def stage2_chain(model, refiner, data, iteration=2, graph=True, compose="host", trajectory=False):
     """BASELINE configs[4] as one call: the body of the reference's stage-2 eval loop (tools/test_YCBV_stage2.py:204-225):
     `model(data)` -> canonicalised points (P - t) R -> cat[points, F_Xo_p] -> `iteration` x refiner with pose composition
     t <- R dt + t, R <- R dR.  -> (rot (b,3,3), trans (b,3), stage-1 prediction dict).  With graph=True the refine loop
-    replays its hipGraph (static shapes); the stage-1 forward keeps its own schedule (eager or forward_graphed)."""
+    replays its hipGraph (static shapes); the stage-1 forward keeps its own schedule (eager or forward_graphed).
+    compose / trajectory: handed to refine_loop; with trajectory=True (compose="device") the pose after every iteration,
+    (rots, transs), is returned as a fourth value."""
     with torch.no_grad():
         pred = model(data)
         points_inp = data["labels"]["points_inp"]
-        rot, trans = refine_loop(refiner, pred, points_inp, iteration, graph=graph)
-    return rot, trans, pred
+        out = refine_loop(refiner, pred, points_inp, iteration, graph=graph, compose=compose, trajectory=trajectory)
+    return (out[0], out[1], pred) + tuple(out[2:])

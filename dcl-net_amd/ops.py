@@ -1654,6 +1654,85 @@ def pose_heads_parts(parts, affine, rot_layers, trans_layers, with_rotation=Fals
     return (o9, trans, R) if with_rotation else (o9, trans)
 
 
+def _refine_first(pts, R, t, W3, term, host):
+    what = "refine_first_host" if host else "refine_first"
+    b, n, _ = _rigid_args(pts, R, t, True, host, what)
+    _same_side(host, what, W3, term)
+    assert term.dim() == 2 and term.shape[0] == b * n, tuple(term.shape)
+    c = term.shape[1]
+    if c % 4:
+        raise ValueError("%s needs c %% 4 == 0 (16-byte groups of channels), got c = %d" % (what, c))
+    _f32_like(term, (b * n, c), "term")
+    _f32_like(W3, (3, c), "W3")
+    out = torch.empty_like(term)
+    if host:
+        N.check(N.lib().dcl_refine_first_host(b, n, c, N.ptr(pts), N.ptr(R), N.ptr(t), N.ptr(W3), N.ptr(term), N.ptr(out)), what)
+    else:
+        N.check(N.lib().dcl_refine_first(b, n, c, N.ptr(pts), N.ptr(R), N.ptr(t), N.ptr(W3), N.ptr(term), N.ptr(out), N.stream()),
+                what)
+    return out
+
+
+def refine_first(pts, R, t, W3, term):
+    """relu(term + cur @ W3) with cur = R^T (p - t) formed on the way and never stored (csrc/dense.hip: k_refine_first): pts
+    (b,n,3) observed points, R (b,3,3) / t (b,3) the crops' current pose ON THE DEVICE, W3 (3,c), term (b*n,c) -> (b*n,c), one
+    launch.  Bit for bit affine3_relu(rigid_points(pts, R, t, inverse=True).view(b*n, 3), W3, term): the first shared layer of
+    the refine loop's device form (models/refiner.py: refine_loop(compose="device")).  c % 4 == 0 (ValueError otherwise)."""
+    return _refine_first(pts, R, t, W3, term, False)
+
+
+def refine_first_host(pts, R, t, W3, term):
+    """refine_first on CPU tensors (the kernel's routines compiled for the host).  For checking the arithmetic where there is
+    no GPU; no model path calls it."""
+    return _refine_first(pts, R, t, W3, term, True)
+
+
+def pose_compose_host(R, t, dR, dt):
+    """The pose composition refine_heads carries as its epilogue, on CPU tensors (the kernel's routine compiled for the host):
+    R (b,3,3), t (b,3), dR (b,3,3), dt (b,3) -> (R dR, R dt + t), every dot product as fmaf(R_i2, d_2, fmaf(R_i1, d_1, R_i0 * d_0))
+    (include/dclnet_hip.h).  No model path calls it."""
+    _same_side(True, "pose_compose_host", R, t, dR, dt)
+    assert R.dim() == 3, tuple(R.shape)
+    b = R.shape[0]
+    _f32_like(R, (b, 3, 3), "R")
+    _f32_like(t, (b, 3), "t")
+    _f32_like(dR, (b, 3, 3), "dR")
+    _f32_like(dt, (b, 3), "dt")
+    R_out, t_out = torch.empty_like(R), torch.empty_like(t)
+    N.check(N.lib().dcl_pose_compose_host(b, N.ptr(R), N.ptr(t), N.ptr(dR), N.ptr(dt), N.ptr(R_out), N.ptr(t_out)),
+            "pose_compose_host")
+    return R_out, t_out
+
+
+def refine_heads(part, T, rot_layers, trans_layers, R_in, t_in, R_out, t_out):
+    """pose_heads on the pooled feature still as linear_pool's tile partials, with the pose composition as its epilogue
+    (dcl_refine_heads, two launches): part (b*T, 1024), crop i's pooled feature = its T partials added in one ascending chain
+    from tile 0 by the first launch; the second launch WRITES R_out (b,3,3) = R_in dR and t_out (b,3) = R_in dt + t_in (views of
+    the loop's pose arrays; they must not overlap R_in / t_in, which are left as they are).  -> (o9 (b,9), dt (b,3), dR (b,3,3)),
+    the bits pose_heads(x, ..., with_rotation=True) gives.  b <= 65535 (ValueError otherwise)."""
+    N.need_cuda(part, R_in, t_in, R_out, t_out)
+    T = int(T)
+    if T < 1 or part.dim() != 2 or part.shape[0] % T:
+        raise ValueError("refine_heads needs part (b*T, 1024) with T >= 1, got %s for T = %d" % (tuple(part.shape), T))
+    b, dev = part.shape[0] // T, part.device
+    if b > 65535:
+        raise ValueError("refine_heads needs b <= 65535 crops (one grid row per crop), got b = %d" % b)
+    _f32_like(part, (b * T, 1024), "part")
+    assert tuple(rot_layers[0][0].shape) == (1024, 512) and tuple(rot_layers[2][0].shape) == (128, 9)
+    assert tuple(trans_layers[1][0].shape) == (512, 128) and tuple(trans_layers[2][0].shape) == (128, 3)
+    flat = lambda layers: _ptr_array([t for pair in layers for t in pair])                    # noqa: E731
+    assert all(t.is_contiguous() and t.dtype == torch.float32 for layers in (rot_layers, trans_layers) for p in layers for t in p)
+    for t, shape, what in ((R_in, (b, 3, 3), "R_in"), (t_in, (b, 3), "t_in"), (R_out, (b, 3, 3), "R_out"), (t_out, (b, 3), "t_out")):
+        _f32_like(t, shape, what)
+    h1 = torch.empty((2, b, 512), dtype=torch.float32, device=dev)
+    o9 = torch.empty((b, 9), dtype=torch.float32, device=dev)
+    dt = torch.empty((b, 3), dtype=torch.float32, device=dev)
+    dR = torch.empty((b, 3, 3), dtype=torch.float32, device=dev)
+    N.check(N.lib().dcl_refine_heads(b, T, N.ptr(part), flat(rot_layers), flat(trans_layers), N.ptr(h1), N.ptr(R_in), N.ptr(t_in),
+                                     N.ptr(R_out), N.ptr(t_out), N.ptr(o9), N.ptr(dt), N.ptr(dR), N.stream()), "refine_heads")
+    return o9, dt, dR
+
+
 VENDOR_GEMM = False           # tools / tests only: True sends linear() to the vendor library whatever the shape (A/B runs)
 
 

@@ -487,6 +487,40 @@ int dcl_pose_heads_parts(int b, int nslices, const float *part1, const float *pa
                          const float *const *rot_layers, const float *const *trans_layers, float *h1_scratch, float *o9,
                          float *trans, float *R, dclStream_t stream);
 
+/* ---- the eval refine loop with the pose on the device (models/refiner.py: refine_loop(compose="device"); the loop of
+ * tools/test_YCBV_stage2.py:204-225).  One pass of the loop is dcl_refine_first, two GEMMs of the own core (the second with the
+ * pooling epilogue, dcl_linear_pool_fwd) and dcl_refine_heads: five launches, the pose read from and written to device arrays.
+ * These entries join the ABI; the version stays.  Every order below is part of the contract (csrc/refine_pose.h holds the
+ * routines, host + device, built with -ffp-contract=off).
+ *
+ * dcl_refine_first: out (b*n, c) = relu(term (b*n, c) + cur @ W3 (3, c)), cur = R^T (p - t) of the row's crop (crop = row / n),
+ * never stored.  pts (b,n,3), R (b,3,3) row-major, t (b,3).  PINNED: q = p - t (three subtractions);
+ * cur_j = fmaf(R_2j, q_2, fmaf(R_1j, q_1, R_0j * q_0)) (dcl_rigid_points with inverse = 1);
+ * out = fmaxf(fmaf(cur_2, W_2k, fmaf(cur_1, W_1k, cur_0 * W_0k)) + term, 0) (dcl_affine3_relu).  One launch, one streaming pass.
+ * c % 4 == 0, any b, n >= 1 with b * n * 3 <= INT32_MAX, term / out / W3 16-B aligned.  dcl_refine_first_host: the same routine on
+ * HOST pointers (no GPU call).
+ *
+ * dcl_pose_compose_host (HOST pointers; the epilogue of dcl_refine_heads on its own), per crop, row-major:
+ *   R_out[i][j] = fmaf(R_in[i][2], dR[2][j], fmaf(R_in[i][1], dR[1][j], R_in[i][0] * dR[0][j]))
+ *   t_out[i]    = fmaf(R_in[i][2], dt[2],    fmaf(R_in[i][1], dt[1],    R_in[i][0] * dt[0])) + t_in[i]
+ *
+ * dcl_refine_heads: dcl_pose_heads (same weights, same h1_scratch of 2*b*512 floats, same bits of o9 / dt / dR) fed with the
+ * pooled feature still as dcl_linear_pool_fwd's tile partials part (b*T, 1024), and with the pose composition as its epilogue;
+ * two launches.  PINNED: x[crop][ch] = ((part[crop*T+0][ch] + part[crop*T+1][ch]) + ...) + part[crop*T+T-1][ch], one ascending
+ * fp32 chain from tile 0, formed by every workgroup of the crop's first launch.  The second launch's rotation workgroup writes
+ * R_out (b,3,3), its translation workgroup t_out (b,3), by the formulas above from R_in, t_in and the dR / dt just formed; o9
+ * (b,9), dt (b,3), dR (b,3,3) are written as dcl_pose_heads writes them.  R_out / t_out must not overlap R_in / t_in (a crop's
+ * two workgroups both read the inputs).  T >= 1, b <= 65535.                                                              */
+int dcl_refine_first(int b, int n, int c, const float *pts, const float *R, const float *t, const float *W3,
+                     const float *term, float *out, dclStream_t stream);
+int dcl_refine_first_host(int b, int n, int c, const float *pts, const float *R, const float *t, const float *W3,
+                          const float *term, float *out);
+int dcl_pose_compose_host(int b, const float *R_in, const float *t_in, const float *dR, const float *dt, float *R_out,
+                          float *t_out);
+int dcl_refine_heads(int b, int T, const float *part, const float *const *rot_layers, const float *const *trans_layers,
+                     float *h1_scratch, const float *R_in, const float *t_in, float *R_out, float *t_out, float *o9, float *dt,
+                     float *dR, dclStream_t stream);
+
 /* One per-point linear layer -- Conv1d(k=1) / 1x1x1 Conv3d with its BatchNorm folded in (models/Modules.py:58-97, 173-201;
  * the reference runs them as cuDNN pointwise convolutions): y[M x N] = act(x[M x K] Wt[K x N] + bias[N]), row-major, every
  * matrix with its own row pitch (ldx >= K, ldw >= N, ldy >= N floats) so that x, Wt and y can be column blocks of wider
