@@ -8,6 +8,11 @@ The sampling draws stay `np.random.choice` on the host, made in the reference's 
 a seeded run consumes the global numpy RNG stream exactly like the original loader and produces the same crops.  That
 needs the per-instance point counts on the host: the one read-back of the builder (plus the {V, maxActive} read-back of
 each voxelize_idx).  No CPU fallback: the arrays are uploaded and everything else happens on the device.
+
+CropBuilder(draws="device") is the opt-in form without that read-back: the draws are made on the GPU from a counter-based
+generator (ops.crop_draw; include/dclnet_hip.h pins it) -- NOT the loader's MT19937 stream, a different sample of the same
+distribution that repeats from (draw_seed, draw_frame).  With capacity=True a frame then goes from images to `data` without a
+host synchronisation; nothing is dropped from the batch, and data["valid"] says which crops are real.
 """
 import math
 import random
@@ -213,7 +218,7 @@ def _mark(label):
 
 class CropBuilder(object):
     def __init__(self, cfg, cad_points_mm, cad_colors, camera=YCBV_CAMERA, device="cuda", capacity=False, v2p_pitch=33,
-                 template_ids=False):
+                 template_ids=False, draws="host", draw_seed=0):
         """cfg: mapping with input_size, tmp_size, unit_voxel_extent, voxel_num_limit, voxelization_mode (the `test`
         block of configs/config_YCBV_bs32.yaml).  cad_points_mm / cad_colors: {class id: (tmp_size,3) float64}, the
         loader's list_pc_CAD / list_rgb_CAD (millimetres; colours already mean-subtracted, :57-58).
@@ -227,7 +232,23 @@ class CropBuilder(object):
         device tensor of the crops' class ids, and no data["tmp"]; build_lm / build_lmo return that one-element tensor and None
         in place of (feat_tmp, voxel_tmp).  For a Network with a per-class template cache: net.cache_templates(builder.templates(),
         voxel_num_limit) once, then every such call runs no template-side work (models/DCL_Net.py).  The training builders
-        (build_train, build_train_lm) do not read it."""
+        (build_train, build_train_lm) do not read it.
+        draws="host" (default): the loader's np.random.choice draws on the host, bit for bit, behind the read-back of the point
+        counts.  draws="device": the eval builders (build, build_lm, build_lmo) draw on the GPU with ops.crop_draw from
+        (draw_seed, self.draw_frame, instance row) and never read the counts back.  draw_frame starts at 0, goes up by one per
+        built frame / sample and may be read and set: the same (draw_seed, draw_frame) gives the same crops bit for bit, and a
+        CropPrefetcher (one thread, in order) makes the serial loop's draws.  These are NOT the loader's draws and consume
+        nothing of np.random.  The batch of build() is then EVERY candidate (an instance with an empty mask stays, as a lattice
+        dummy crop: ops.crop_sample_valid) and data["valid"] (b,) i32 on the device marks the real ones; build_lm / build_lmo
+        never return None and return `valid` (1,) as a sixth element.  Labels and centroid of a crop that is not valid are
+        unspecified: consumers mask by `valid`, read together with their results.  Zero host synchronisations per frame needs
+        capacity=True (the exact form keeps its {V, maxActive} read-back).  The training builders do not read the switch."""
+        if draws not in ("host", "device"):
+            raise ValueError("CropBuilder: draws must be 'host' or 'device', got %r" % (draws,))
+        self.draws, self.draw_seed, self.draw_frame = draws, int(draw_seed), 0
+        if draws == "device" and not 1 <= int(cfg["input_size"]) <= min(ops.CROP_DRAW_MAX_POINTS, int(cfg["voxel_num_limit"][0]) ** 3):
+            raise ValueError("CropBuilder(draws='device'): input_size must be 1 .. %d and at most voxel_num_limit^3"
+                             % ops.CROP_DRAW_MAX_POINTS)
         self.capacity, self.v2p_pitch = bool(capacity), int(v2p_pitch)
         self.template_ids = bool(template_ids)
         self.n_inp, self.n_tmp = int(cfg["input_size"]), int(cfg["tmp_size"])
@@ -323,7 +344,11 @@ class CropBuilder(object):
         None -- numpy arrays as the loader reads them, or the CUDA tensors of CropBuilder.resident().  Returns the loader's
         dict with CUDA tensors (instances without a detection or with an empty mask are dropped and flagged 0 in
         `all_flags`, :116,134).  Host synchronisations per frame: the per-instance point counts (the sampling draws are the
-        loader's own np.random.choice calls) and {V, maxActive} of the observed side's voxelisation; nothing else."""
+        loader's own np.random.choice calls) and {V, maxActive} of the observed side's voxelisation; nothing else.
+        draws="device" (see __init__): no read-back of the counts -- crop_points, crop_draw, crop_sample_valid, the voxelisation.
+        The batch is every candidate (b = the instances with a detection; `all_flags` marks them), data["valid"] (b,) i32,
+        data["counts"] (b,3) i32 and data["picks"] (b, input_size) i64 stay on the device.  "every object mask of this image is
+        empty" cannot be raised in this form (it would need the counts): such a frame is a batch of dummy crops with valid = 0."""
         _mark("start")
         H, W = depth.shape
         gt_obj = np.asarray(gt_obj).astype(np.int32)
@@ -376,6 +401,28 @@ class CropBuilder(object):
             return part
         part = count_free_part(list(range(len(cand))))
         _mark("count-free part issued")
+        if self.draws == "device":
+            frame, self.draw_frame = self.draw_frame, self.draw_frame + 1
+            picks, valid = ops.crop_draw(counts, self.n_inp, self.draw_seed, frame, MIN_VALID, keep_sparse=True)   # :134,163
+            feats_inp, coords_inp = ops.crop_sample_valid(xyz, col, picks, counts, valid, self.extent[0] * 0.5, self.unit,
+                                                          int(self.limit[0]), min_valid=MIN_VALID)
+            flags[cand] = 1
+            b = len(cand)
+            data = dict(part["host"], all_flags=torch.IntTensor(flags), all_centroids=part["centroid"], labels=part["labels"],
+                        counts=counts, valid=valid, picks=picks)
+            _mark("draw + sample + labels issued")
+            data["inp"] = self._inp_side(feats_inp, coords_inp, b)
+            _mark("voxelisation issued")
+            if self.template_ids:
+                data["tmp_cls"] = part["tmp_cls"]
+            else:
+                occ, p2v, v2p, coords_tmp = part["tmp_side"]
+                data["tmp"] = {"feats": part["feats_tmp"], "coords": coords_tmp, "occupied_voxels": occ, "p2v_maps": p2v,
+                               "v2p_maps": v2p}
+            data["ready_event"] = torch.cuda.Event()
+            data["ready_event"].record(torch.cuda.current_stream(dev))
+            _mark("end")
+            return data
         cnt = counts.cpu().numpy()                                                  # the builder's host read-back
         _mark("counts read back")
         keep = [k for k in range(len(cand)) if cnt[k, 0] > 0]
@@ -780,7 +827,8 @@ class CropBuilder(object):
         on the device from the uploaded mask (ops.mask_box) -- the box row never visits the host.  The builder must have
         been made with camera=LM_CAMERA.  Returns (feat_inp (N,7), voxel_inp (N,3) i64, feat_tmp (M,7), voxel_tmp (M,3) i64,
         centroid (3,)) as CUDA tensors, or None where the loader returns its all-zero dummy sample (empty mask; in test mode
-        also when at most 128 points fall inside the voxel grid)."""
+        also when at most 128 points fall inside the voxel grid).  draws="device" (see __init__): never None -- a sixth element
+        `valid` (1,) i32 on the device says, by the same rule, whether the sample is real (0: a lattice dummy crop)."""
         if obj is None:
             raise TypeError("build_lm: obj (the class id) is required")
         return self._lm_sample(img, depth, mask_label, obj_bb, obj, LM_MIN_VALID, eval_mode, eval_mode)
@@ -791,7 +839,8 @@ class CropBuilder(object):
         of an occluded object comes in pieces and the loader keeps the piece with the largest bounding rectangle), the
         voxel-grid filter is always applied (:261-264) and the dummy sample is returned when no masked pixel with depth lies
         inside the crop (:220-222) or no point lies inside the grid (:262,282-284) -> None.  camera=LM_CAMERA.  The pose
-        labels (the LineMOD -> Occlusion alignment included) are the caller's."""
+        labels (the LineMOD -> Occlusion alignment included) are the caller's.  draws="device": as build_lm, never None, with
+        `valid` as the sixth element."""
         return self._lm_sample(img, depth, mask_label, None, obj, LMO_MIN_VALID, True, False)
 
     def _lm_sample(self, img, depth, mask_label, obj_bb, obj, min_valid, always_filter, keep_sparse):
@@ -807,11 +856,22 @@ class CropBuilder(object):
             cap = H * W
         else:
             r0, r1, c0, c1 = lm_box(obj_bb, H, W)
-            b_t = torch.tensor([[max(r0, 0), min(r1, H), max(c0, 0), min(c1, W)]], dtype=torch.int32, device=dev)
-            cap = None
+            box = [max(r0, 0), min(r1, H), max(c0, 0), min(c1, W)]
+            b_t = torch.tensor([box], dtype=torch.int32, device=dev)
+            # (the device form knows the box on the host: crop_points need not read it back for its capacity)
+            cap = max(1, max(box[1] - box[0], 0) * max(box[3] - box[2], 0)) if self.draws == "device" else None
         o_t = torch.ones(1, dtype=torch.int32, device=dev)
         xyz, col, centroid, counts = ops.crop_points(d_t, l_t, i_t, b_t, o_t, self.camera, RGB_MEAN, self.extent * 0.5,
                                                      min_valid, always_filter=always_filter, cap=cap)
+        if self.draws == "device":
+            frame, self.draw_frame = self.draw_frame, self.draw_frame + 1
+            picks, valid = ops.crop_draw(counts, self.n_inp, self.draw_seed, frame, min_valid, keep_sparse=keep_sparse)
+            feats, coords = ops.crop_sample_valid(xyz, col, picks, None, valid, self.extent[0] * 0.5, self.unit, int(self.limit[0]))
+            if self.template_ids:
+                return (feats, coords[:, 1:].contiguous(), torch.tensor([int(obj)], dtype=torch.int32, device=dev), None,
+                        centroid[0], valid)
+            row = self.cls_row[int(obj)]
+            return feats, coords[:, 1:].contiguous(), self.tmp_feats[row], self.tmp_vox[row], centroid[0], valid
         n_mask, n_valid, m = counts.cpu().numpy()[0]
         if n_mask == 0 or not (n_valid > min_valid or keep_sparse):
             return None

@@ -70,16 +70,8 @@ __global__ void k_crop_sample(int n_inst, int npoint, int cap, const float *__re
     const int inst = (int)(e / npoint);
     const long long i = sample_idx ? sample_idx[e] : (e - (long long)inst * npoint);
     const float *p = xyz + ((size_t)inst * cap + i) * 3, *c = rgb + ((size_t)inst * cap + i) * 3;
-    const float x = p[0], y = p[1], z = p[2];
-    float *f = feats + e * 7;
-    f[0] = 1.0f; f[1] = c[0]; f[2] = c[1]; f[3] = c[2]; f[4] = x; f[5] = y; f[6] = z;
-    float vx = (x + half0) / ux, vy = (y + half0) / uy, vz = (z + half0) / uz;
-    if (counts && counts[inst * 3 + 1] <= min_valid) {
-      vx = fminf(fmaxf(vx, 0.0f), limit - 1.0f); vy = fminf(fmaxf(vy, 0.0f), limit - 1.0f);
-      vz = fminf(fmaxf(vz, 0.0f), limit - 1.0f);
-    }
-    int64_t *o = coords + e * 4;
-    o[0] = inst; o[1] = (int64_t)vx; o[2] = (int64_t)vy; o[3] = (int64_t)vz;
+    crop_sample_row(p, c, counts && counts[inst * 3 + 1] <= min_valid, inst, half0, ux, uy, uz, limit, feats + e * 7,
+                    coords + e * 4);
   }
 }
 

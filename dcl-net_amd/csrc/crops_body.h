@@ -382,4 +382,31 @@ __device__ __forceinline__ void crop_keep_body(int inst, int chunk, int cap, int
   }
 }
 
+// ---- 4. one sampled point -> its feats row [1, r, g, b, x, y, z] and voxel coordinate row [inst, ix, iy, iz] (:170-176,186-190):
+//   voxel = trunc((xyz + half_extent0) / unit) in float32, clamped to [0, limit - 1] first where `clamp` (the crop had at most
+//   min_valid points inside the grid).  p / c: the point's xyz and colour.  The body of k_crop_sample and k_crop_sample_valid
+//   and of the host twin.
+__host__ __device__ inline void crop_sample_row(const float *p, const float *c, bool clamp, int64_t inst, float half0, float ux,
+                                                float uy, float uz, float limit, float *f, int64_t *o) {
+  const float x = p[0], y = p[1], z = p[2];
+  f[0] = 1.0f; f[1] = c[0]; f[2] = c[1]; f[3] = c[2]; f[4] = x; f[5] = y; f[6] = z;
+  float vx = (x + half0) / ux, vy = (y + half0) / uy, vz = (z + half0) / uz;
+  if (clamp) {
+    vx = fminf(fmaxf(vx, 0.0f), limit - 1.0f); vy = fminf(fmaxf(vy, 0.0f), limit - 1.0f);
+    vz = fminf(fmaxf(vz, 0.0f), limit - 1.0f);
+  }
+  o[0] = inst; o[1] = (int64_t)vx; o[2] = (int64_t)vy; o[3] = (int64_t)vz;
+}
+
+// point j of the LATTICE DUMMY crop of an instance that gives no crop (dcl_crop_sample_valid): the centre of voxel
+// (j mod S, (j div S) mod S, j div S^2), colour 0 -- one point per voxel, npoint <= S^3
+inline bool crop_lattice_fits(int npoint, int S) { return S >= 2048 || (long long)npoint <= (long long)S * S * S; }
+__host__ __device__ inline void crop_lattice_row(int64_t j, int S, int64_t inst, float half0, float ux, float uy, float uz,
+                                                 float *f, int64_t *o) {
+  const int ix = (int)(j % S), iy = (int)((j / S) % S), iz = (int)(j / ((int64_t)S * S));
+  f[0] = 1.0f; f[1] = 0.0f; f[2] = 0.0f; f[3] = 0.0f;
+  f[4] = ((float)ix + 0.5f) * ux - half0; f[5] = ((float)iy + 0.5f) * uy - half0; f[6] = ((float)iz + 0.5f) * uz - half0;
+  o[0] = inst; o[1] = ix; o[2] = iy; o[3] = iz;
+}
+
 }  // namespace

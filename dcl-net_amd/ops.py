@@ -2210,6 +2210,90 @@ def crop_sample(xyz, rgb, sample_idx, counts, half_extent0, unit, voxel_limit, n
     return feats, coords
 
 
+CROP_DRAW_MAX_POINTS = 4096    # include/dclnet_hip.h: DCL_CROP_DRAW_MAX_POINTS
+_U64 = (1 << 64) - 1
+
+
+def crop_draw(counts, npoint, seed, frame, min_valid=32, keep_sparse=True):
+    """The sampling draws of every instance ON THE DEVICE (csrc/crop_draw.hip; the definition: include/dclnet_hip.h,
+    dcl_crop_draw): counts (n,3) i32 CUDA as crop_points returns it -> sample_idx (n,npoint) i64, valid (n) i32, both CUDA.
+    A pure function of (seed, frame, row, counts row) -- NOT the loader's np.random stream; no host synchronisation."""
+    N.need_cuda(counts)
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.dim() == 2 and counts.shape[1] == 3
+    n = counts.shape[0]
+    idx = torch.empty((n, max(int(npoint), 0)), dtype=torch.int64, device=counts.device)
+    valid = torch.empty((n,), dtype=torch.int32, device=counts.device)
+    N.check(N.lib().dcl_crop_draw(n, int(npoint), N.ptr(counts), int(min_valid), int(bool(keep_sparse)),
+                                  C.c_uint64(int(seed) & _U64), C.c_uint64(int(frame) & _U64), N.ptr(idx), N.ptr(valid),
+                                  N.stream()), "crop_draw")
+    return idx, valid
+
+
+def crop_draw_host(counts, npoint, seed, frame, min_valid=32, keep_sparse=True):
+    """the host twin of crop_draw (dcl_crop_draw_host, plain C++, no GPU call): counts (n,3) integer numpy array ->
+    (sample_idx (n,npoint) int64, valid (n) int32) numpy arrays."""
+    import numpy as np
+    cnt = np.ascontiguousarray(np.asarray(counts).astype(np.int32)).reshape(-1, 3)
+    n = cnt.shape[0]
+    idx = np.zeros((n, max(int(npoint), 0)), np.int64)
+    valid = np.zeros(n, np.int32)
+    N.check(N.lib().dcl_crop_draw_host(n, int(npoint), cnt.ctypes.data_as(C.c_void_p), int(min_valid), int(bool(keep_sparse)),
+                                       C.c_uint64(int(seed) & _U64), C.c_uint64(int(frame) & _U64),
+                                       idx.ctypes.data_as(C.c_void_p), valid.ctypes.data_as(C.c_void_p)), "crop_draw_host")
+    return idx, valid
+
+
+def crop_draw_keys_host(seed, frame, inst, s, n):
+    """base(seed, frame, inst, s) and key(0..n-1) of the draw's generator (dcl_crop_draw_keys_host) -> (int, uint64 array)"""
+    import numpy as np
+    base = C.c_uint64(0)
+    keys = np.zeros(int(n), np.uint64)
+    N.check(N.lib().dcl_crop_draw_keys_host(C.c_uint64(int(seed) & _U64), C.c_uint64(int(frame) & _U64), int(inst), int(s), int(n),
+                                            C.byref(base), keys.ctypes.data_as(C.c_void_p)), "crop_draw_keys_host")
+    return int(base.value), keys
+
+
+def crop_sample_valid(xyz, rgb, sample_idx, counts, valid, half_extent0, unit, voxel_limit, min_valid=32):
+    """crop_sample for the instances with valid != 0 (the same rows, bit for bit), a lattice dummy crop -- point j at the centre
+    of voxel (j mod S, (j div S) mod S, j div S^2), colour 0 -- for the others (csrc/crop_draw.hip).  sample_idx (n,npoint) i64,
+    valid (n) i32, counts (n,3) i32 or None, all CUDA.  -> feats (n*npoint,7), coords (n*npoint,4) i64."""
+    N.need_cuda(xyz, rgb, sample_idx, counts, valid)
+    assert xyz.is_contiguous() and rgb.is_contiguous() and xyz.dtype == torch.float32 and rgb.dtype == torch.float32
+    n, cap = xyz.shape[0], xyz.shape[1]
+    assert sample_idx.dtype == torch.int64 and sample_idx.is_contiguous() and sample_idx.shape[0] == n
+    assert valid.dtype == torch.int32 and valid.is_contiguous() and valid.shape[0] == n
+    assert counts is None or (counts.dtype == torch.int32 and counts.is_contiguous() and counts.shape[0] == n)
+    npoint = sample_idx.shape[1]
+    dev = xyz.device
+    feats = torch.empty((n * npoint, 7), dtype=torch.float32, device=dev)
+    coords = torch.empty((n * npoint, 4), dtype=torch.int64, device=dev)
+    unit_a = (C.c_float * 3)(*[float(v) for v in unit])
+    N.check(N.lib().dcl_crop_sample_valid(n, npoint, cap, N.ptr(xyz), N.ptr(rgb), N.ptr(sample_idx), N.ptr(counts), int(min_valid),
+                                          N.ptr(valid), _c_float(half_extent0), unit_a, int(voxel_limit), N.ptr(feats),
+                                          N.ptr(coords), N.stream()), "crop_sample_valid")
+    return feats, coords
+
+
+def crop_sample_valid_host(xyz, rgb, sample_idx, counts, valid, half_extent0, unit, voxel_limit, min_valid=32):
+    """the host twin of crop_sample_valid (dcl_crop_sample_valid_host, plain C++, no GPU call) on numpy arrays"""
+    import numpy as np
+    x = np.ascontiguousarray(np.asarray(xyz, np.float32))
+    c = np.ascontiguousarray(np.asarray(rgb, np.float32))
+    idx = np.ascontiguousarray(np.asarray(sample_idx).astype(np.int64))
+    val = np.ascontiguousarray(np.asarray(valid).astype(np.int32))
+    cnt = None if counts is None else np.ascontiguousarray(np.asarray(counts).astype(np.int32))
+    n, cap = x.shape[0], x.shape[1]
+    npoint = idx.shape[1]
+    feats = np.zeros((n * npoint, 7), np.float32)
+    coords = np.zeros((n * npoint, 4), np.int64)
+    unit_a = (C.c_float * 3)(*[float(v) for v in unit])
+    p = lambda a: C.c_void_p(0) if a is None else a.ctypes.data_as(C.c_void_p)
+    N.check(N.lib().dcl_crop_sample_valid_host(n, npoint, cap, p(x), p(c), p(idx), p(cnt), int(min_valid), p(val),
+                                               _c_float(half_extent0), unit_a, int(voxel_limit), p(feats), p(coords)),
+            "crop_sample_valid_host")
+    return feats, coords
+
+
 def mask_box(label, value=1, padding=0):
     """`get_bbox(mask_to_bbox(label == value, padding))` of the LineMOD / Occlusion-LineMOD loaders on the device
     (csrc/mask_box.hip).  label (H,W) or (n,H,W) i32 CUDA.  -> (n,10) i32 CUDA: box [x,y,w,h] of the 8-connected component

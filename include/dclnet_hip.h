@@ -803,6 +803,55 @@ int dcl_crop_points(const uint16_t *depth, const int32_t *label, const uint8_t *
 int dcl_crop_sample(int n_inst, int npoint, int cap, const float *xyz, const float *rgb, const int64_t *sample_idx,
                     const int32_t *counts, int min_valid, float half_extent0, const float *unit_host, int voxel_limit,
                     float *feats, int64_t *coords, dclStream_t stream);
+/* ---- the sampling draws ON THE DEVICE (csrc/crop_draw.hip, csrc/crop_draw.h; crops.py: CropBuilder(draws="device"))
+ * The loaders draw a crop's npoint points with np.random.choice on the host's MT19937 stream, which needs every instance's
+ * point count on the host.  dcl_crop_draw is a DIFFERENT, fully specified sample of the same distribution, a pure function of
+ * (seed, frame, instance row, counts row), made where the counts are.  All arithmetic is uint64, mod 2^64:
+ *     G = 0x9E3779B97F4A7C15
+ *     mix(z):  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *     base(seed, frame, inst, s) = mix( mix( mix(seed + G) ^ (frame + G) ) ^ (2*inst + s + G) )
+ *     key(j) = mix(base + (j + 1) * G)
+ * inst = the row of counts (n_inst,3) i32 as dcl_crop_points writes it, m = counts[inst][2] the rows written.
+ *   valid[inst] = counts[inst][0] > 0 && (keep_sparse || counts[inst][1] > min_valid) && m > 0      (the loaders' rule for "this
+ *       instance gives a crop"; dcl_crop_points writes m = 0 under that rule only for LineMOD's eval mode with no point inside
+ *       the grid, where the loader's own draw raises).  An instance that is not valid gets a row of zeros in sample_idx.
+ *   m > npoint, stream s = 0, WITHOUT replacement: the npoint indices j in [0, m) with the smallest (key(j), j), in ascending
+ *       (key, j) order -- the head of a uniform random permutation, np.argsort(keys, kind="stable")[:npoint].
+ *   0 < m <= npoint, stream s = 1, WITH replacement: idx[j] = floor(key(j) * m / 2^64), the high half of the 128-bit product,
+ *       for j in [0, npoint).
+ * Pinned: base(1,0,0,0) = 0x6df1421574b0d586 with key(0), key(1) = 0x96c9f513020798b9, 0xf7dd055ed9ec356f; base(2,7,3,1) =
+ * 0x9fb95fa8ca6188d9 with keys 0xc1bed6510d07ff6c, 0x3c33370239554870.
+ * sample_idx (n_inst, npoint) i64 and valid (n_inst) i32 are written; counts, sample_idx, valid are DEVICE pointers.  One
+ * workgroup per instance; keys are a function of the index, so the selection reads no memory: a guessed threshold, widened
+ * while fewer than npoint keys lie under it, a most-significant-digit-first radix select where more lie under it than the LDS
+ * list holds, a bitonic sort of the list.  The result is fixed by the definition above, not by the route; the kernel
+ * terminates for every m < 2^31.  No float arithmetic, no global atomic, no scratch, no workgroup waits for another, nothing is
+ * read back, no allocation: capturable.  DCL_EINVAL before any device work for npoint < 1 or > DCL_CROP_DRAW_MAX_POINTS,
+ * n_inst < 0, or a null pointer of a non-empty call; n_inst == 0 returns 0 and launches nothing.
+ *
+ * dcl_crop_sample_valid: dcl_crop_sample's rows (the same body, csrc/crops_body.h: the same bits) for every instance with
+ * valid[inst] != 0 (sample_idx required; an index is clamped to [0, cap - 1] before it addresses anything), and for the
+ * others a LATTICE DUMMY CROP, S = voxel_limit: point j lies at the centre of voxel (ix, iy, iz) = (j mod S, (j div S) mod S,
+ * j div S^2) -- feats row [1, 0, 0, 0, x, y, z] with x = (float(ix) + 0.5f) * unit[0] - half_extent0 (uncontracted; y, z alike),
+ * coords row [inst, ix, iy, iz].  Requires npoint <= S^3 (and <= DCL_CROP_DRAW_MAX_POINTS).  Why not zeros: an instance
+ * without a crop has no written xyz row to gather from, and npoint points in ONE voxel would raise the capacity form's pitch
+ * flag (dcl_voxelize_idx_crops: info[2]) for the whole frame; the lattice has one point per voxel.
+ *
+ * dcl_crop_draw_host / dcl_crop_sample_valid_host: the same contracts in plain C++ on HOST pointers (csrc/crop_draw_host.cpp:
+ * all m keys and a partial sort; the twins the tests compare the kernels with; no GPU call).  dcl_crop_draw_keys_host:
+ * *base = base(seed, frame, inst, s) and keys[0..n) = key(0..n-1). */
+#define DCL_CROP_DRAW_MAX_POINTS 4096
+int dcl_crop_draw(int n_inst, int npoint, const int32_t *counts, int min_valid, int keep_sparse, uint64_t seed, uint64_t frame,
+                  int64_t *sample_idx, int32_t *valid, dclStream_t stream);
+int dcl_crop_draw_host(int n_inst, int npoint, const int32_t *counts, int min_valid, int keep_sparse, uint64_t seed,
+                       uint64_t frame, int64_t *sample_idx, int32_t *valid);
+int dcl_crop_draw_keys_host(uint64_t seed, uint64_t frame, int inst, int s, int n, uint64_t *base, uint64_t *keys);
+int dcl_crop_sample_valid(int n_inst, int npoint, int cap, const float *xyz, const float *rgb, const int64_t *sample_idx,
+                          const int32_t *counts, int min_valid, const int32_t *valid, float half_extent0,
+                          const float *unit_host, int voxel_limit, float *feats, int64_t *coords, dclStream_t stream);
+int dcl_crop_sample_valid_host(int n_inst, int npoint, int cap, const float *xyz, const float *rgb, const int64_t *sample_idx,
+                               const int32_t *counts, int min_valid, const int32_t *valid, float half_extent0,
+                               const float *unit_host, int voxel_limit, float *feats, int64_t *coords);
 /* The loaders' `get_bbox(mask_to_bbox(mask_label, padding))` (LM/dataloader_test_LMO.py:26-42,215,360-402; the LineMOD loader's
  * eval mode, LM/dataloader_test_LM.py:144) for n label images (n,H,W) i32 (csrc/mask_box.hip; semantics: csrc/mask_box.h).
  * A pixel is set where label == value; components are 8-connected; the winner is the component whose bounding rectangle
@@ -1486,6 +1535,10 @@ int dcl_debug_order_stamps(unsigned long long *host16);
 void dcl_debug_conv_xcd_remap(int on);
 /* Tuning hook: output rows per tile of dcl_sparse_conv_fwd_compact, 64 or 128; 0 (default) = by the layer's width. */
 void dcl_debug_conv_fwd_compact_bm(int bm);
+/* Test hook, dcl_crop_draw's route to its (route-independent) result: 0 (default) = guessed threshold, widened or replaced by
+ * the radix select as needed; 1 = radix select from the start; 2 = a first guess 256 times too small (the widening loop);
+ * 3 = a first guess of 2^64 - 1 (the list overflows where m > 8192: the radix select behind a failed guess). */
+void dcl_debug_crop_draw_route(int route);
 /* Tuning hook for dcl_group_points' LDS-staged kernel: channel rows per workgroup, x-blocks, threads per workgroup,
  * store kind (2 = plain instead of nontemporal); 0 = built-in choice for each. */
 void dcl_debug_group_points_cfg(int cc, int xb, int threads, int nontemporal);
