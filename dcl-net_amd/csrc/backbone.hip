@@ -347,6 +347,7 @@ struct SideArgs {
   void *ws2;
   int64_t ws2_bytes;
   float *const *level_out;
+  const void *const *wpieces;    // per conv layer: the filter's bf16 pieces (dcl_conv_split_weight) or NULL; NULL = none at all
 };
 }  // namespace
 
@@ -431,7 +432,7 @@ static int backbone_features(const SideArgs *sd, int nsides, int batch, int S, c
           if (rc) return rc;
           Sd.feat = x[i]; Sd.out = x1; Sd.cap = nc; Sd.n_dev = nc_dev; Sd.n_host = nc_dev ? expect_rows(batch, m, nc) : nc;
           Sd.form_rows = expect_rows(batch, m, 0x7fffffff);
-          Sd.W = a.weights[2 * m]; Sd.scale = a.scales[2 * m]; Sd.shift = a.shifts[2 * m];
+          Sd.W = a.weights[2 * m]; Sd.Wp = a.wpieces ? a.wpieces[2 * m] : nullptr; Sd.scale = a.scales[2 * m]; Sd.shift = a.shifts[2 * m];
           Sd.ord = order_of(i, 0);
         } else if (stage == 1) {
           rc = source(i, at<int32_t>(a.ws, c.indices), nc_dev, nc, at<uint32_t>(a.ws, c.mask), at<int32_t>(a.ws, c.wprefix),
@@ -439,7 +440,7 @@ static int backbone_features(const SideArgs *sd, int nsides, int batch, int S, c
           if (rc) return rc;
           Sd.feat = x1; Sd.out = x2; Sd.cap = nc; Sd.n_dev = nc_dev; Sd.n_host = nc_dev ? expect_rows(batch, m, nc) : nc;
           Sd.form_rows = 0;
-          Sd.W = a.weights[2 * m + 1]; Sd.scale = a.scales[2 * m + 1]; Sd.shift = a.shifts[2 * m + 1];
+          Sd.W = a.weights[2 * m + 1]; Sd.Wp = a.wpieces ? a.wpieces[2 * m + 1] : nullptr; Sd.scale = a.scales[2 * m + 1]; Sd.shift = a.shifts[2 * m + 1];
           Sd.ord = order_of(i, 1);
         } else {
           rc = source(i, at<int32_t>(a.ws, p.indices), np_dev, np, at<uint32_t>(a.ws, c.mask), at<int32_t>(a.ws, c.wprefix),
@@ -471,14 +472,24 @@ static int backbone_features(const SideArgs *sd, int nsides, int batch, int S, c
   return 0;
 }
 
+// (the _split entry points: the same passes with prepared filter pieces per conv layer -- wpieces[8], NULL entries keep the
+// fp32 kernel -- for the layers that run the split-bf16 conv form; the caller picks them by shape, ops.CONV_SPLIT_WIDTHS)
+DCL_API int dcl_backbone_features_split(const int32_t *occ, int V0, int batch, int S, void *ws, const int32_t *counts_host,
+                                        const int32_t *channels_host, const float *vox_feats, const float *const *weights,
+                                        const void *const *wpieces, const float *const *scales, const float *const *shifts,
+                                        void *ws2, int64_t ws2_bytes, float *const *level_out, dclStream_t stream) {
+  (void)occ;
+  DCL_CHECK_ARG(counts_host);
+  const SideArgs a{V0, ws, counts_host, nullptr, vox_feats, weights, scales, shifts, ws2, ws2_bytes, level_out, wpieces};
+  return backbone_features(&a, 1, batch, S, channels_host, stream);
+}
+
 DCL_API int dcl_backbone_features(const int32_t *occ, int V0, int batch, int S, void *ws, const int32_t *counts_host,
                                   const int32_t *channels_host, const float *vox_feats, const float *const *weights,
                                   const float *const *scales, const float *const *shifts, void *ws2, int64_t ws2_bytes,
                                   float *const *level_out, dclStream_t stream) {
-  (void)occ;
-  DCL_CHECK_ARG(counts_host);
-  const SideArgs a{V0, ws, counts_host, nullptr, vox_feats, weights, scales, shifts, ws2, ws2_bytes, level_out};
-  return backbone_features(&a, 1, batch, S, channels_host, stream);
+  return dcl_backbone_features_split(occ, V0, batch, S, ws, counts_host, channels_host, vox_feats, weights, nullptr, scales, shifts,
+                                     ws2, ws2_bytes, level_out, stream);
 }
 
 // capacity mode: every buffer is sized by the layout's capacities (dcl_backbone_caps), the live row counts are read
@@ -495,12 +506,20 @@ DCL_API int dcl_backbone_features_cap(const int32_t *occ, int V0_cap, int batch,
                                       const float *const *weights, const float *const *scales,
                                       const float *const *shifts, void *ws2, int64_t ws2_bytes,
                                       float *const *level_out, dclStream_t stream) {
+  return dcl_backbone_features_cap_split(occ, V0_cap, batch, S, ws, counts_dev, channels_host, vox_feats, weights, nullptr, scales,
+                                         shifts, ws2, ws2_bytes, level_out, stream);
+}
+DCL_API int dcl_backbone_features_cap_split(const int32_t *occ, int V0_cap, int batch, int S, void *ws,
+                                            const int32_t *counts_dev, const int32_t *channels_host, const float *vox_feats,
+                                            const float *const *weights, const void *const *wpieces,
+                                            const float *const *scales, const float *const *shifts, void *ws2,
+                                            int64_t ws2_bytes, float *const *level_out, dclStream_t stream) {
   (void)occ;
   int32_t caps[8];
   DCL_CHECK_ARG(counts_dev);
   int rc = dcl_backbone_caps(batch, S, V0_cap, caps);
   if (rc) return rc;
-  const SideArgs a{V0_cap, ws, caps, counts_dev, vox_feats, weights, scales, shifts, ws2, ws2_bytes, level_out};
+  const SideArgs a{V0_cap, ws, caps, counts_dev, vox_feats, weights, scales, shifts, ws2, ws2_bytes, level_out, wpieces};
   return backbone_features(&a, 1, batch, S, channels_host, stream);
 }
 
@@ -511,6 +530,16 @@ DCL_API int dcl_backbone_features_pair(int batch, int S, const int32_t *channels
                                        const float *const *vox_feats, const float *const *const *weights,
                                        const float *const *const *scales, const float *const *const *shifts, void *const *ws2,
                                        const int64_t *ws2_bytes, float *const *const *level_out, dclStream_t stream) {
+  return dcl_backbone_features_pair_split(batch, S, channels_host, V0, ws, counts_host, counts_dev, vox_feats, weights, nullptr,
+                                          scales, shifts, ws2, ws2_bytes, level_out, stream);
+}
+// wpieces: NULL, or per side wpieces[i] as in dcl_backbone_features_split (NULL: that side has none)
+DCL_API int dcl_backbone_features_pair_split(int batch, int S, const int32_t *channels_host, const int32_t *V0, void *const *ws,
+                                             const int32_t *const *counts_host, const int32_t *const *counts_dev,
+                                             const float *const *vox_feats, const float *const *const *weights,
+                                             const void *const *const *wpieces, const float *const *const *scales,
+                                             const float *const *const *shifts, void *const *ws2, const int64_t *ws2_bytes,
+                                             float *const *const *level_out, dclStream_t stream) {
   DCL_CHECK_ARG(V0 && ws && vox_feats && weights && scales && shifts && ws2 && ws2_bytes && level_out &&
                 (counts_dev || counts_host));
   int32_t caps[2][8];
@@ -524,7 +553,8 @@ DCL_API int dcl_backbone_features_pair(int batch, int S, const int32_t *channels
       ch = caps[i];
     }
     DCL_CHECK_ARG(ch);
-    a[i] = SideArgs{V0[i], ws[i], ch, cd, vox_feats[i], weights[i], scales[i], shifts[i], ws2[i], ws2_bytes[i], level_out[i]};
+    a[i] = SideArgs{V0[i], ws[i], ch, cd, vox_feats[i], weights[i], scales[i], shifts[i], ws2[i], ws2_bytes[i], level_out[i],
+                    wpieces ? wpieces[i] : nullptr};
   }
   return backbone_features(a, 2, batch, S, channels_host, stream);
 }

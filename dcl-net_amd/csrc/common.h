@@ -124,6 +124,8 @@ struct DclConvSide {
                                 // four lanes per row): data-independent (crops x the per-crop mean of the level) inside the backbone
                                 // runner, so that the same batch takes the same form launch by launch and under graph capture;
                                 // 0 = none (op-level calls: the row count itself)
+  const void *Wp;               // the filter as three bf16 piece planes in the split conv kernel's chunk / tile order
+                                // (dcl_conv_split_weight), or nullptr: the launch takes the split-bf16 form when every side has one
 };
 // the problems of one dcl_linear_group_fwd launch (kernel argument)
 struct DclLinearJobs {

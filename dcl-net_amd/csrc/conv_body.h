@@ -352,19 +352,27 @@ __device__ __forceinline__ void conv_store16_wt(f32x4 *p, f32x4 v) {
 // ORD: the launch carries a row order (sides.s[].ord; the two deep levels of a batch of 14 crops or more) -- a
 // compile-time switch, because the natural-order instantiation must not pay registers for the order's bookkeeping (the
 // 8-wave variants sit at the 128-VGPR limit of two workgroups per CU)
+// SPLIT: the chunk's product runs on the bf16 matrix pipe as the six exact piece products of linear_split.hip (fp32 as three bf16
+// pieces; the fp32 MFMA runs at 1/16 of the bf16 one).  The gathered A rows arrive as fp32 exactly as above and each wave splits
+// its own fragments in registers (bf16_split2: four waves of 32 rows x 64 columns, so a value is split by one wave only); the
+// filter comes as three bf16 planes prepared once per layer (sparse_conv.hip: dcl_conv_split_weight), a chunk's 32 channels x BN
+// columns x 3 planes contiguous and already in MFMA-operand order -- [plane][k step s][lane half h][column][8 channels 16 s +
+// 8 h ..] -- so its DMA is a linear copy and a lane's B operand one ds_read_b128, lanes of a half 16 B apart (no swizzle needed).
+// Everything outside the product -- units, order, neighbour table, combine, epilogue -- is the code above.
 // wid_in = blockIdx.x of G = gridDim.x.
-template <int CIN, int WR, int WCW, int NT, bool ORD>
+template <int CIN, int WR, int WCW, int NT, bool ORD, bool SPLIT = false>
 __device__ __forceinline__ void conv_dma_body(
     const DclConvSides &sides, int nsides, int cout, int kvol, int subm, int relu, float *__restrict__ partial, int stream_k,
     int aligned_ns, int xcd_remap, int32_t *__restrict__ tile_counters, int use_bal_arg, float *conv_lds, int wid_in, int G) {
   const int use_bal = ORD ? use_bal_arg : 0;
   constexpr int NW = WR * WCW, NTHR = 64 * NW;
   constexpr int BM = 32 * WR, BN = 32 * NT * WCW, KC = 32;
-  constexpr int AT = BM * KC, BT = KC * BN, ST = AT + BT;      // floats per stage
+  constexpr int AT = BM * KC, BT = SPLIT ? 3 * KC * BN / 2 : KC * BN, ST = AT + BT;      // floats per stage (SPLIT: three bf16 planes)
   constexpr int A_INSTR = BM / 8;                              // 1-KiB DMA instructions per A tile (8 rows of 128 B each)
   constexpr int B_ROWS_PER = 256 / BN;                         // W rows per 1-KiB DMA instruction
-  constexpr int B_INSTR = KC / B_ROWS_PER;
+  constexpr int B_INSTR = SPLIT ? BT / 256 : KC / B_ROWS_PER;
   static_assert(A_INSTR % NW == 0 && B_INSTR % NW == 0 && (BN == 32 || BN == 64 || BN == 128), "tile shape");
+  static_assert(!SPLIT || (CIN >= KC && WCW == 1), "split form: whole chunks inside one offset, a row's values split by one wave");
   constexpr int BSWZ = BN >= 64 ? 1 : 0;                       // W-row half swap (rows 32 floats wide have no halves to swap)
   // conv_lds: [stage 0: A|B][stage 1: A|B][Ns 27*BM][kmask (8)][rows BM]
   int32_t *Ns = reinterpret_cast<int32_t *>(conv_lds + 2 * ST);
@@ -442,7 +450,7 @@ __device__ __forceinline__ void conv_dma_body(
     const float *__restrict__ feat = S.feat;
     const DclNbrSrc src = S.src;
     const int cap = S.cap;
-    const float *__restrict__ W = S.W;
+    const float *__restrict__ W = SPLIT ? reinterpret_cast<const float *>(S.Wp) : S.W;   // (SPLIT: the piece planes, counted in floats)
     const DclRowOrder ord = ORD ? S.ord : DclRowOrder{nullptr, nullptr, nullptr};
     const int32_t *__restrict__ bal = use_bal ? ord.bal : nullptr;
     const int n = second ? n1 : n0;
@@ -599,6 +607,11 @@ __device__ __forceinline__ void conv_dma_body(
 #pragma unroll
       for (int i = 0; i < B_PER; ++i) {
         const int g = iwave * B_PER + i;
+        if constexpr (SPLIT) {                           // piece g of the chunk's contiguous planes, this lane's 16 B of it
+          b_kk[i] = 0;
+          b_off[i] = g * 256 + lane * 4;
+          continue;
+        }
         b_kk[i] = g * B_ROWS_PER + lane / LPR;
         const int pcol = lane % LPR;
         const int bcol = col0 + ((BSWZ ? pcol ^ (((b_kk[i] >> 2) & 1) << 3) : pcol) << 2);
@@ -609,7 +622,7 @@ __device__ __forceinline__ void conv_dma_body(
     // by i KiB (glds16_group); fire_all(stage): the chunk's pieces go out, W first (their sources are ready first).
     constexpr int NPIECE = A_PER + B_PER;
     constexpr int AGRP = A_PER >= 4 ? 4 : A_PER, BGRP = B_PER >= 4 ? 4 : B_PER;
-    static_assert(A_PER % AGRP == 0 && B_PER % BGRP == 0 && (AGRP == 1 || AGRP == 2 || AGRP == 4) && (BGRP == 1 || BGRP == 2 || BGRP == 4), "DMA groups");
+    static_assert(A_PER % AGRP == 0 && B_PER % BGRP == 0 && (AGRP == 1 || AGRP == 2 || AGRP == 4) && BGRP >= 1 && BGRP <= 4, "DMA groups");
     const float *psrc[NPIECE];
     auto prep = [&](int j) {
       const float **asrc = psrc, **bsrc = psrc + A_PER;
@@ -622,7 +635,8 @@ __device__ __forceinline__ void conv_dma_body(
         int v[A_PER];
 #pragma unroll
         for (int i = 0; i < A_PER; ++i) v[i] = nrow[a_row[i]];
-        const float *wbase = W + ((size_t)k * CIN + chb) * cout;
+        // (SPLIT: the planes of (offset k, chunk, column tile by) are one block of BT floats)
+        const float *wbase = SPLIT ? W + ((size_t)(k * CPK + (j - sx * CPK)) * ncol + by) * BT : W + ((size_t)k * CIN + chb) * cout;
 #pragma unroll
         for (int i = 0; i < B_PER; ++i) bsrc[i] = wbase + b_off[i] - (i % BGRP) * 256;
         const float *fbase = feat + chb;
@@ -701,7 +715,39 @@ __device__ __forceinline__ void conv_dma_body(
       PH(ph_issue);
       // wave-level skip: none of this wave's 32 rows has a neighbour under any offset of the chunk
       const bool mine = SPC == 1 ? ((wsmask >> (j / CPK)) & 1u) != 0 : ((wsmask >> (j * SPC)) & ((1u << SPC) - 1u)) != 0;
-      if (mine) {
+      if constexpr (SPLIT) {
+        if (mine) {
+          // lane (r, h) holds row r's channels 16 s + 8 h .. + 7 of k step s (two swizzled 16-B blocks), split here into the three
+          // packed pieces of the MFMA's A operand; the B pieces of column 32 t + r, same channels, are one ds_read_b128 per plane.
+          // Six products per (s, t), smallest first, the column tiles interleaved (no two dependent MFMAs back to back).
+          const float *arow = conv_lds + cur * ST + (wr * 32 + r) * KC;
+          const u32x4 *bpl = reinterpret_cast<const u32x4 *>(conv_lds + cur * ST + AT);
+          const int sw = (r >> 1) & 7;
+          constexpr int PL = 4 * BN;                                          // 16-B units per plane: [s][h][BN]
+#pragma unroll
+          for (int s = 0; s < KC / 16; ++s) {
+            const float4 a0 = *reinterpret_cast<const float4 *>(arow + (((4 * s + 2 * h) ^ sw) << 2));
+            const float4 a1 = *reinterpret_cast<const float4 *>(arow + (((4 * s + 2 * h + 1) ^ sw) << 2));
+            u32x4 bw[NT][3];
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+              for (int p = 0; p < 3; ++p) bw[t][p] = bpl[p * PL + (2 * s + h) * BN + 32 * t + r];
+            unsigned ph[4], pm[4], pl[4];
+            bf16_split2(a0.x, a0.y, ph[0], pm[0], pl[0]);
+            bf16_split2(a0.z, a0.w, ph[1], pm[1], pl[1]);
+            bf16_split2(a1.x, a1.y, ph[2], pm[2], pl[2]);
+            bf16_split2(a1.z, a1.w, ph[3], pm[3], pl[3]);
+            const u32x4 xp[3] = {{ph[0], ph[1], ph[2], ph[3]}, {pm[0], pm[1], pm[2], pm[3]}, {pl[0], pl[1], pl[2], pl[3]}};
+            constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};   // xl wh, xh wl, xm wm, xm wh, xh wm, xh wh
+#pragma unroll
+            for (int q = 0; q < 6; ++q)
+#pragma unroll
+              for (int t = 0; t < NT; ++t)
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(xp[PA[q]]), as_bf16x8(bw[t][PB[q]]), acc[t], 0, 0, 0);
+          }
+        }
+      } else if (mine) {
         const float *arow = conv_lds + cur * ST + (wr * 32 + r) * KC;
         const float *bcol = nullptr;
         const int sw = (r >> 1) & 7;

@@ -46,7 +46,7 @@ __device__ __forceinline__ void glds16_s(unsigned voff, const void *sbase, unsig
 // piece (tools/ubench_glds.hip; four waves issuing at once: 83 against 119).
 template <int N>
 __device__ __forceinline__ void glds16_group(const float *const *gsrc, unsigned lds_byte_addr) {
-  static_assert(N == 1 || N == 2 || N == 4, "pieces per group");
+  static_assert(N >= 1 && N <= 4, "pieces per group");
   if constexpr (N == 1) {
     glds16(gsrc[0], lds_byte_addr);
   } else {
@@ -55,6 +55,10 @@ __device__ __forceinline__ void glds16_group(const float *const *gsrc, unsigned 
       asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
                    "global_load_lds_dwordx4 %2, off offset:1024\n\ts_mov_b32 m0, %0"
                    : "=&s"(keep) : "v"(gsrc[0]), "v"(gsrc[1]), "s"(lds_byte_addr) : "memory");
+    else if constexpr (N == 3)
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
+                   "global_load_lds_dwordx4 %2, off offset:1024\n\tglobal_load_lds_dwordx4 %3, off offset:2048\n\ts_mov_b32 m0, %0"
+                   : "=&s"(keep) : "v"(gsrc[0]), "v"(gsrc[1]), "v"(gsrc[2]), "s"(lds_byte_addr) : "memory");
     else
       asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
                    "global_load_lds_dwordx4 %2, off offset:1024\n\tglobal_load_lds_dwordx4 %3, off offset:2048\n\t"

@@ -333,6 +333,20 @@ __global__ __launch_bounds__(64 * WR * WCW, WR * WCW / 2) void k_sparse_conv_dma
   conv_dma_body<CIN, WR, WCW, NT, ORD>(sides, nsides, cout, kvol, subm, relu, partial, stream_k, aligned_ns, xcd_remap, tile_counters,
                                        use_bal_arg, conv_lds, blockIdx.x, gridDim.x);
 }
+// the split-bf16 form (conv_body.h, SPLIT): the chunk's product as six bf16 piece products, the filter from DclConvSide::Wp
+template <int CIN, int WR, int WCW, int NT, bool ORD>
+__global__ __launch_bounds__(64 * WR * WCW, WR * WCW / 2) void k_sparse_conv_dma_split(
+    const DclConvSides sides, int nsides, int cout, int kvol, int subm, int relu, float *__restrict__ partial, int stream_k,
+    int aligned_ns, int xcd_remap, int32_t *__restrict__ tile_counters, int use_bal_arg) {
+  extern __shared__ __attribute__((aligned(16))) float conv_lds[];   // [stage 0: A|pieces][stage 1: A|pieces][Ns 27*BM][kmask (4)][rows BM]
+  conv_dma_body<CIN, WR, WCW, NT, ORD, true>(sides, nsides, cout, kvol, subm, relu, partial, stream_k, aligned_ns, xcd_remap,
+                                             tile_counters, use_bal_arg, conv_lds, blockIdx.x, gridDim.x);
+}
+template <int CIN, int WR, int WCW, int NT, bool ORD, bool SPLIT>
+constexpr auto conv_dma_kernel() {
+  if constexpr (SPLIT) return &k_sparse_conv_dma_split<CIN, WR, WCW, NT, ORD>;
+  else return &k_sparse_conv_dma<CIN, WR, WCW, NT, ORD>;
+}
 
 
 #ifdef DCL_DIAG
@@ -527,19 +541,18 @@ static DclConvPlan plan_conv_dma(const DclConvSides &sides, int nsides, int CIN,
   return P;
 }
 
-template <int CIN, int WR, int WCW, int NT>
+template <int CIN, int WR, int WCW, int NT, bool SPLIT = false>
 static void launch_conv_dma(const DclConvSides &sides, int nsides, int cout, int kvol, int subm, int relu, float *scratch,
                             long long scratch_floats, int counters_ready, int *counters_state, hipStream_t s) {
   constexpr int BM = 32 * WR, BN = 32 * NT * WCW, KC = 32;
-  const size_t lds = (size_t)(2 * (BM * KC + KC * BN) + 27 * BM + 8 + BM) * sizeof(float);
-  (void)hipFuncSetAttribute((const void *)k_sparse_conv_dma<CIN, WR, WCW, NT, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds);
-  (void)hipFuncSetAttribute((const void *)k_sparse_conv_dma<CIN, WR, WCW, NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds);
+  const size_t lds = (size_t)(2 * (BM * KC + (SPLIT ? 3 * KC * BN / 2 : KC * BN)) + 27 * BM + 8 + BM) * sizeof(float);
+  const auto kern_nat = conv_dma_kernel<CIN, WR, WCW, NT, false, SPLIT>(), kern_ord = conv_dma_kernel<CIN, WR, WCW, NT, true, SPLIT>();
+  (void)hipFuncSetAttribute((const void *)kern_nat, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)hipFuncSetAttribute((const void *)kern_ord, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 #ifdef DCL_CONV_STAMPS
   {
     int occ = -1;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)k_sparse_conv_dma<CIN, WR, WCW, NT, true>, 64 * WR * WCW, lds);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)kern_ord, 64 * WR * WCW, lds);
     fprintf(stderr, "k_sparse_conv_dma<%d,%d,%d,%d>: dynamic LDS %zu B, occupancy API says %d workgroups per CU\n", CIN, WR, WCW, NT, lds, occ);
   }
 #endif
@@ -571,10 +584,10 @@ static void launch_conv_dma(const DclConvSides &sides, int nsides, int cout, int
   bool any_order = false;
   for (int i = 0; i < nsides; ++i) any_order = any_order || sd.s[i].ord.order != nullptr;
   if (any_order)
-    hipLaunchKernelGGL((k_sparse_conv_dma<CIN, WR, WCW, NT, true>), dim3(P.G), dim3(64 * WR * WCW), lds, s, sd, nsides, cout, kvol,
+    hipLaunchKernelGGL(kern_ord, dim3(P.G), dim3(64 * WR * WCW), lds, s, sd, nsides, cout, kvol,
                        subm, relu, partial, P.stream_k, P.aligned_ns, (int)g_conv_xcd_remap | stamp_bit, counters, P.use_bal);
   else
-    hipLaunchKernelGGL((k_sparse_conv_dma<CIN, WR, WCW, NT, false>), dim3(P.G), dim3(64 * WR * WCW), lds, s, sd, nsides, cout, kvol,
+    hipLaunchKernelGGL(kern_nat, dim3(P.G), dim3(64 * WR * WCW), lds, s, sd, nsides, cout, kvol,
                        subm, relu, partial, P.stream_k, P.aligned_ns, (int)g_conv_xcd_remap | stamp_bit, counters, 0);
   if (P.deferred)
     hipLaunchKernelGGL((k_conv_frag_reduce<WR, WCW, NT>), dim3(P.tiles, WR * WCW * NT), dim3(256), 0, s, partial, sd, nsides, cout,
@@ -723,6 +736,69 @@ DCL_API int dcl_sparse_conv_fwd_ordered(const float *feat, const int32_t *nbr, i
   const DclRowOrder ord{order, bal, smask};
   return dcl_internal_sparse_conv_fwd(feat, src, cap, n_out_dev, n_out_host, W, cin, cout, kvol, subm, scale, shift, relu,
                                       out, scratch, scratch_floats, stream, 0, &ord);
+}
+
+// ---- split-bf16 form: filter pieces, prepared once per layer -----------------------------------------------------------------
+// W (kvol, cin, cout) fp32 -> three bf16 planes h, m, l with W = h + m + l exactly (bf16_split2, the one split), in the order the
+// split kernel's DMA copies linearly: [offset k][32-channel chunk][64-column tile][plane][k step s][lane half h][column][8
+// channels 16 s + 8 h ..] -- 12 KiB per (k, chunk, column tile), kvol * cin * cout * 6 bytes in all.  Thread = one 16-B unit of
+// each plane.
+constexpr int kCsBN = 64, kCsKC = 32;
+__global__ __launch_bounds__(256) void k_conv_split_weight(const float *__restrict__ W, int kvol, int cin, int cout,
+                                                           u32x4 *__restrict__ planes) {
+  const int cpk = cin / kCsKC, ncol = cout / kCsBN;
+  const long long units = (long long)kvol * cpk * ncol * 4 * kCsBN;
+  for (long long u = (long long)blockIdx.x * 256 + threadIdx.x; u < units; u += (long long)gridDim.x * 256) {
+    const int col = (int)(u % kCsBN), sh = (int)((u / kCsBN) % 4);
+    const long long blk = u / (4 * kCsBN);
+    const int by = (int)(blk % ncol), chunk = (int)((blk / ncol) % cpk), k = (int)(blk / ((long long)ncol * cpk));
+    const float *src = W + ((size_t)k * cin + chunk * kCsKC + 8 * sh) * cout + by * kCsBN + col;   // 8 sh = 16 s + 8 h
+    unsigned h[4], m[4], l[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) bf16_split2(src[(size_t)(2 * i) * cout], src[(size_t)(2 * i + 1) * cout], h[i], m[i], l[i]);
+    u32x4 *dst = planes + blk * (3 * 4 * kCsBN) + sh * kCsBN + col;
+    dst[0] = u32x4{h[0], h[1], h[2], h[3]};
+    dst[4 * kCsBN] = u32x4{m[0], m[1], m[2], m[3]};
+    dst[8 * kCsBN] = u32x4{l[0], l[1], l[2], l[3]};
+  }
+}
+
+DCL_API int64_t dcl_conv_split_weight_bytes(int kvol, int cin, int cout) {
+  if (kvol <= 0 || cin <= 0 || cout <= 0 || cin % kCsKC != 0 || cout % kCsBN != 0) return 0;
+  return (int64_t)kvol * cin * cout * 6;
+}
+
+DCL_API int dcl_conv_split_weight(const float *W, int kvol, int cin, int cout, void *planes, dclStream_t stream) {
+  DCL_CHECK_ARG(W && planes && ((size_t)planes & 15) == 0 && dcl_conv_split_weight_bytes(kvol, cin, cout) > 0);
+  const long long units = (long long)kvol * (cin / kCsKC) * (cout / kCsBN) * 4 * kCsBN;
+  hipLaunchKernelGGL(k_conv_split_weight, dim3((unsigned)dcl_grid_1d(units, 256, 4096)), dim3(256), 0, (hipStream_t)stream, W, kvol,
+                     cin, cout, (u32x4 *)planes);
+  DCL_LAUNCH_CHECK();
+  return 0;
+}
+
+// One layer of up to two problems in one launch, from explicit gather tables: what the backbone runner issues for the two
+// backbones of a level, as an op.  pieces != NULL (and pieces[i] != NULL for every side): the split-bf16 form.  order / bal /
+// smask: NULL, or per side a row order as in dcl_sparse_conv_fwd_ordered.
+DCL_API int dcl_sparse_conv_fwd_sides(int nsides, const float *const *feat, const int32_t *const *nbr, const int32_t *cap,
+                                      const int32_t *n_out_host, const float *const *W, const void *const *pieces, int cin, int cout,
+                                      int kvol, int subm, const float *const *scale, const float *const *shift, int relu,
+                                      float *const *out, float *scratch, int64_t scratch_floats, const int32_t *const *order,
+                                      const int32_t *const *bal, const uint32_t *const *smask, dclStream_t stream) {
+  DCL_CHECK_ARG(nsides >= 1 && nsides <= 2 && feat && nbr && cap && n_out_host && W && out);
+  DCL_CHECK_ARG((order == nullptr || (bal == nullptr) == (smask == nullptr)) && (order != nullptr || (bal == nullptr && smask == nullptr)));
+  DCL_CHECK_ARG(pieces == nullptr || (kvol == 27 && dcl_conv_split_weight_bytes(kvol, cin, cout) > 0));
+  DclConvSides sides{};
+  for (int i = 0; i < nsides; ++i) {
+    DclConvSide &S = sides.s[i];
+    DCL_CHECK_ARG(nbr[i]);
+    S.feat = feat[i]; S.src = DclNbrSrc{nbr[i], nullptr, nullptr, nullptr, nullptr, 0, 1, 0}; S.cap = cap[i]; S.n_dev = nullptr;
+    S.n_host = n_out_host[i]; S.W = W[i]; S.scale = scale ? scale[i] : nullptr; S.shift = shift ? shift[i] : nullptr; S.out = out[i];
+    S.ord = order ? DclRowOrder{order[i], bal ? bal[i] : nullptr, smask ? smask[i] : nullptr} : DclRowOrder{nullptr, nullptr, nullptr};
+    S.Wp = pieces ? pieces[i] : nullptr;
+    DCL_CHECK_ARG(pieces == nullptr || S.Wp);
+  }
+  return dcl_internal_sparse_conv_fwd_sides(sides, nsides, cin, cout, kvol, subm, relu, scratch, scratch_floats, stream, 0);
 }
 
 // ---- measurement facility (bench.py's `roofline_sparse_conv`): while enabled, every sparse-conv call is bracketed by
@@ -912,6 +988,19 @@ static int conv_dispatch(const DclConvSides &sides_in, int nsides_in, int cin, i
   }
   if (ch.family == DCL_CONV_DMA) {
 #define DMA_ARGS sides, nsides, cout, kvol, subm, relu, scratch, (long long)scratch_floats, counters_ready, counters_state, s
+    // Split-bf16 form: every side carries prepared filter pieces (DclConvSide::Wp).  The caller decides by the layer's widths and
+    // its expected rows (ops.CONV_SPLIT_WIDTHS), never by the data; the form has one tile shape, 128 x 64 on four waves of 32 x 64.
+    bool split_form = kvol == 27 && cout % 64 == 0 && (cin == 32 || cin == 64 || cin == 128);
+    for (int i = 0; i < nsides; ++i) split_form = split_form && sides.s[i].Wp != nullptr;
+    if (split_form) {
+      switch (cin) {
+        case 32: launch_conv_dma<32, 4, 1, 2, true>(DMA_ARGS); break;
+        case 64: launch_conv_dma<64, 4, 1, 2, true>(DMA_ARGS); break;
+        default: launch_conv_dma<128, 4, 1, 2, true>(DMA_ARGS); break;
+      }
+      DCL_LAUNCH_CHECK();
+      return 0;
+    }
 #define DMA_CASE(WR_, WCW_, NT_)                                          \
     switch (cin) {                                                      \
       case 16: launch_conv_dma<16, WR_, WCW_, NT_>(DMA_ARGS); break;    \

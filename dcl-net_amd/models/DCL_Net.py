@@ -390,8 +390,10 @@ class Network(nn.Module):
                         W = conv.weight.reshape(-1, conv.in_channels, conv.out_channels).contiguous()
                         layers.append((W, s.contiguous(), t.contiguous(), conv.subm))
                 f[bb] = layers
+                # (fourth: the wide layers' filters as bf16 pieces for the split-bf16 conv form -- ops.ConvSplitPieces, prepared
+                # once per set of weights like the GEMM's planes below; which launches take them: ops.CONV_SPLIT_WIDTHS)
                 f[bb + "_ptrs"] = (ops._ptr_array([l[0] for l in layers]), ops._ptr_array([l[1] for l in layers]),
-                                   ops._ptr_array([l[2] for l in layers]))
+                                   ops._ptr_array([l[2] for l in layers]), ops.ConvSplitPieces(layers))
             for side in ("Xc", "Yo"):
                 W1, t1, second = [], [], []
                 for tag in ("p1", "m1", "p2", "m2"):

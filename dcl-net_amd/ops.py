@@ -439,6 +439,96 @@ def _ptr_array(tensors):
     return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
+# ---- split-bf16 form of the LDS-DMA conv kernel (csrc/conv_body.h, SPLIT): the chunk's product as six exact bf16 piece products on
+# the bf16 matrix pipe, the filter as three bf16 planes prepared once per layer.  Which launches take it is decided HERE, by shape
+# and never by data: a layer (cin, cout, subm) of the table, from its minimum EXPECTED row count on -- crops x the per-crop mean
+# of the layer's level (the runner's own expect_rows), the same number launch by launch and under graph capture, so both run the
+# same form.  Filled from profiles/conv_split.txt: a width is listed only where every split timing was below every fp32 timing.
+CONV_SPLIT = True                                      # False: the fp32-MFMA kernels everywhere (same-job A/B, like GEMM_SPLIT)
+# (cin, cout, subm) -> minimum expected rows of the launch.  Measured at 32 crops (both shapes, every split timing below every fp32
+# timing: 200 -> 150, 127 -> 110, 260 -> 203, 163 -> 132, 376 -> 278 us); smaller batches were not measured and keep the fp32 kernels,
+# so each threshold is the layer's expected rows at 32 crops.
+CONV_SPLIT_WIDTHS = {(32, 64, True): 57600, (64, 64, False): 28800, (64, 128, True): 28800,
+                     (128, 128, False): 14400, (128, 256, True): 14400}
+CONV_SPLIT_ROWS_PER_CROP = (3600, 1800, 900, 450)      # csrc/backbone.hip: expect_rows
+
+
+def conv_split_ok(kvol, cin, cout):
+    """the widths the split kernel is built for (one 128 x 64 tile shape on 32-channel chunks)"""
+    return int(kvol) == 27 and int(cin) in (32, 64, 128) and int(cout) % 64 == 0
+
+
+def conv_split_weight(W):
+    """W (27, cin, cout) fp32 -> uint8 tensor of three bf16 planes h + m + l == W exactly, in the split kernel's chunk / tile order:
+    [k][cin / 32][cout / 64][plane][k step][lane half][64 columns][8 channels] (csrc/sparse_conv.hip: dcl_conv_split_weight)"""
+    N.need_cuda(W)
+    kvol, cin, cout = W.shape
+    assert W.is_contiguous() and W.dtype == torch.float32 and conv_split_ok(kvol, cin, cout)
+    lib = N.lib()
+    lib.dcl_conv_split_weight_bytes.restype = C.c_int64
+    nbytes = int(lib.dcl_conv_split_weight_bytes(int(kvol), int(cin), int(cout)))
+    planes = torch.empty(nbytes, dtype=torch.uint8, device=W.device)
+    N.check(lib.dcl_conv_split_weight(N.ptr(W), int(kvol), int(cin), int(cout), N.ptr(planes), N.stream()), "conv_split_weight")
+    return planes
+
+
+def conv_split_planes(planes, cin, cout):
+    """the three planes of conv_split_weight back in filter order: (3, 27, cin, cout) float32 (tests)"""
+    v = planes.view(torch.bfloat16).view(27, cin // 32, cout // 64, 3, 2, 2, 64, 8).float()
+    # [k][chunk][by][plane][s][h][col][j] -> [plane][k][chunk][s][h][j][by][col]
+    return v.permute(3, 0, 1, 4, 5, 7, 2, 6).reshape(3, 27, cin, cout)
+
+
+class ConvSplitPieces(object):
+    """The prepared filter pieces of a backbone's conv layers (runner order: conv, subm conv per level) and, per batch size,
+    the pointer array the runner's _split entry points take: a layer's entry is its pieces where the table takes the split
+    form for that many crops, NULL where the fp32 kernel stays.  Built beside the folded weights (Network._fold) and dropped
+    with them."""
+
+    def __init__(self, layers):
+        self.meta = [(tuple(int(d) for d in W.shape), bool(subm)) for W, _, _, subm in layers]
+        # (weights still on the host -- a Network before .cuda(), which cannot run and folds again once it has moved: no pieces)
+        self.planes = [conv_split_weight(W) if W.is_cuda and conv_split_ok(*W.shape) else None for W, _, _, _ in layers]
+        self._arrs = {}
+
+    def ptrs(self, batch):
+        if not CONV_SPLIT or not CONV_SPLIT_WIDTHS:
+            return None
+        key = (int(batch), tuple(sorted(CONV_SPLIT_WIDTHS.items())))
+        if key not in self._arrs:
+            take = []
+            for i, ((kvol, cin, cout), subm) in enumerate(self.meta):
+                min_rows = CONV_SPLIT_WIDTHS.get((cin, cout, subm))
+                rows = int(batch) * CONV_SPLIT_ROWS_PER_CROP[i // 2]
+                take.append(self.planes[i] if min_rows is not None and rows >= min_rows else None)
+            self._arrs[key] = None if all(t is None for t in take) else \
+                (C.c_void_p * len(take))(*[None if t is None else t.data_ptr() for t in take])
+        return self._arrs[key]
+
+
+def sparse_conv_sides(feats, nbrs, n_outs, Ws, subm, pieces=None, scales=None, shifts=None, relu=False, orders=None):
+    """One conv layer of one or two problems in ONE launch (what the backbone runner issues for the two backbones of a level),
+    from explicit gather tables.  pieces: per side conv_split_weight(W) -- the launch takes the split-bf16 form -- or None: the
+    fp32 form of the same launch.  orders: per side the triple of order_rows.  -> list of outputs."""
+    ns = len(feats)
+    assert ns in (1, 2) and len(nbrs) == ns and len(Ws) == ns
+    N.need_cuda(*feats)
+    kvol, cin, cout = Ws[0].shape
+    outs = [torch.empty((int(n), cout), dtype=torch.float32, device=feats[0].device) for n in n_outs]
+    cap_sum = sum(int(nb.shape[1]) for nb in nbrs)
+    need = C.c_int64(0)
+    N.check(N.lib().dcl_sparse_conv_scratch_floats(int(cap_sum), int(cout), C.byref(need)), "sparse_conv_scratch_floats")
+    scratch = torch.empty(need.value, dtype=torch.float32, device=feats[0].device)
+    arr = lambda ts: None if ts is None else _ptr_array(ts)                                   # noqa: E731
+    N.check(N.lib().dcl_sparse_conv_fwd_sides(
+        ns, _ptr_array(feats), _ptr_array(nbrs), (C.c_int32 * ns)(*[int(nb.shape[1]) for nb in nbrs]),
+        (C.c_int32 * ns)(*[int(n) for n in n_outs]), _ptr_array(Ws), arr(pieces), int(cin), int(cout), int(kvol), int(bool(subm)),
+        arr(scales), arr(shifts), int(bool(relu)), _ptr_array(outs), N.ptr(scratch), C.c_int64(scratch.numel()),
+        arr(None if orders is None else [o[0] for o in orders]), arr(None if orders is None else [o[1] for o in orders]),
+        arr(None if orders is None else [o[2] for o in orders]), N.stream()), "sparse_conv_fwd_sides")
+    return outs
+
+
 class BackboneRun(object):
     """State of one backbone pass driven by the native runner (csrc/backbone.hip)."""
 
@@ -467,17 +557,19 @@ class BackboneRun(object):
         self.counts = [int(c) for c in counts]
         self.ccounts = (C.c_int32 * 8)(*self.counts)
 
-    def features(self, vox_feats, weights_arr, scales_arr, shifts_arr):
-        """-> list of 4 level feature tensors (n_pool_m, C_m)."""
+    def features(self, vox_feats, weights_arr, scales_arr, shifts_arr, split=None):
+        """-> list of 4 level feature tensors (n_pool_m, C_m).  split: the backbone's ConvSplitPieces (the layers CONV_SPLIT_WIDTHS
+        lists for this many crops then run the split-bf16 conv form) or None."""
         dev = vox_feats.device
         nbytes = C.c_int64(0)
         N.check(N.lib().dcl_backbone_ws2_bytes(self.ccounts, self.chan, C.byref(nbytes)), "backbone_ws2_bytes")
         ws2 = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
         self.levels = [torch.empty((self.counts[2 * m + 1], BACKBONE_CHANNELS[2 * m + 2]), dtype=torch.float32,
                                    device=dev) for m in range(4)]
-        N.check(N.lib().dcl_backbone_features(N.ptr(self.occ), self.V0, self.batch, self.S, N.ptr(self.ws), self.ccounts,
-                                              self.chan, N.ptr(vox_feats), weights_arr, scales_arr, shifts_arr,
-                                              N.ptr(ws2), nbytes.value, _ptr_array(self.levels), N.stream()),
+        N.check(N.lib().dcl_backbone_features_split(N.ptr(self.occ), self.V0, self.batch, self.S, N.ptr(self.ws), self.ccounts,
+                                                    self.chan, N.ptr(vox_feats), weights_arr,
+                                                    None if split is None else split.ptrs(self.batch), scales_arr, shifts_arr,
+                                                    N.ptr(ws2), nbytes.value, _ptr_array(self.levels), N.stream()),
                 "backbone_features")
         return self.levels
 
@@ -530,7 +622,7 @@ def backbone_features_pair(run_a, vox_a, ptrs_a, run_b, vox_b, ptrs_b):
     """The feature stage of BOTH backbones of a forward (observed / template side; two BackboneRun or two BackboneRunCap of
     the same batch and grid): every layer is one launch over both sides' tiles (dcl_backbone_features_pair), so the fixed
     part of a launch is paid once per layer, not once per layer and side.  ptrs_*: (weights, scales, shifts) pointer
-    arrays of a side.  Fills run_*.levels like run.features()."""
+    arrays of a side, optionally followed by the side's ConvSplitPieces.  Fills run_*.levels like run.features()."""
     cap_mode = isinstance(run_a, BackboneRunCap)
     assert isinstance(run_b, type(run_a)) and run_a.batch == run_b.batch and run_a.S == run_b.S
     dev = vox_a.device
@@ -552,10 +644,12 @@ def backbone_features_pair(run_a, vox_a, ptrs_a, run_b, vox_b, ptrs_b):
         counts_dev = None
     level_ptrs = [r.level_ptrs if cap_mode else _ptr_array(r.levels) for r in runs]
     pp = lambda arrs: (C.c_void_p * 2)(*[C.cast(a, C.c_void_p) for a in arrs])                # noqa: E731
-    N.check(N.lib().dcl_backbone_features_pair(
+    pieces = [p[3].ptrs(run_a.batch) if len(p) > 3 and p[3] is not None else None for p in ptrs]
+    N.check(N.lib().dcl_backbone_features_pair_split(
         run_a.batch, run_a.S, run_a.chan, (C.c_int32 * 2)(run_a.V0, run_b.V0),
         (C.c_void_p * 2)(*[r.ws.data_ptr() for r in runs]), counts_host, counts_dev,
-        (C.c_void_p * 2)(*[v.data_ptr() for v in voxs]), pp([p[0] for p in ptrs]), pp([p[1] for p in ptrs]),
+        (C.c_void_p * 2)(*[v.data_ptr() for v in voxs]), pp([p[0] for p in ptrs]),
+        None if all(q is None for q in pieces) else pp(pieces), pp([p[1] for p in ptrs]),
         pp([p[2] for p in ptrs]), (C.c_void_p * 2)(*[w.data_ptr() for w in ws2]), (C.c_int64 * 2)(*ws2_bytes),
         pp(level_ptrs), N.stream()), "backbone_features_pair")
     if not cap_mode:
@@ -608,11 +702,12 @@ class BackboneRunCap(object):
                                                       int(mode == 4), N.stream()), "backbone_geometry_cap_vox")
         return out
 
-    def features(self, vox_feats, weights_arr, scales_arr, shifts_arr):
-        N.check(N.lib().dcl_backbone_features_cap(N.ptr(self.occ), self.V0, self.batch, self.S, N.ptr(self.ws),
-                                                  N.ptr(self.counts_dev), self.chan, N.ptr(vox_feats), weights_arr,
-                                                  scales_arr, shifts_arr, N.ptr(self.ws2), self.ws2_bytes,
-                                                  self.level_ptrs, N.stream()), "backbone_features_cap")
+    def features(self, vox_feats, weights_arr, scales_arr, shifts_arr, split=None):
+        N.check(N.lib().dcl_backbone_features_cap_split(N.ptr(self.occ), self.V0, self.batch, self.S, N.ptr(self.ws),
+                                                        N.ptr(self.counts_dev), self.chan, N.ptr(vox_feats), weights_arr,
+                                                        None if split is None else split.ptrs(self.batch), scales_arr,
+                                                        shifts_arr, N.ptr(self.ws2), self.ws2_bytes, self.level_ptrs,
+                                                        N.stream()), "backbone_features_cap")
         return self.levels
 
     def point_features(self, points_b4, voxel_extents, offset, out, tmp):

@@ -36,7 +36,8 @@ const char *dcl_last_error(void);
  *      dcl_backbone_stage_ws_bytes and DCL_ESTAGE_UNSUPPORTED are gone; dcl_linear_fwd ignores its workspace arguments;
  *      new: dcl_linear_dma_fwd, dcl_linear_pool_fwd, dcl_linear_rowdot_fwd, dcl_conf_softmax, dcl_pool_finish2,
  *      dcl_linear_split_weight(_bytes), dcl_linear_split_fwd / _pool_fwd / _rowdot_fwd / _vpieces_fwd, dcl_cross_attention_ws3
- *      (+ _planes_bytes, _split_crops)                         */
+ *      (+ _planes_bytes, _split_crops); later additions (no change to existing entries): dcl_conv_split_weight(_bytes),
+ *      dcl_sparse_conv_fwd_sides, dcl_backbone_features_split / _cap_split / _pair_split */
 #define DCL_ABI_VERSION 2
 int dcl_abi_version(void);
 
@@ -205,6 +206,23 @@ int dcl_sparse_conv_fwd_ordered(const float *feat, const int32_t *nbr, int cap, 
                                 const int32_t *order, const int32_t *bal, const uint32_t *smask, dclStream_t stream);
 int dcl_sparse_conv_scratch_floats(int rows_cap, int cout, int64_t *floats_host);
 
+/* Split-bf16 form of the LDS-DMA conv kernel (csrc/conv_body.h): the product of a 32-channel chunk as six exact bf16 piece
+ * products on the bf16 matrix pipe (the scheme of dcl_linear_split_fwd), for kvol = 27, cin in {32, 64, 128}, cout % 64 == 0.
+ * dcl_conv_split_weight writes W (27, cin, cout) as three bf16 planes h + m + l == W (exactly) in the kernel's chunk / tile
+ * order -- [k][cin / 32][cout / 64][plane][k step][lane half][64 columns][8 channels] -- into `planes` (16-byte aligned,
+ * dcl_conv_split_weight_bytes = 6 * 27 * cin * cout bytes; 0 for widths the kernel does not take): once per layer.
+ * dcl_sparse_conv_fwd_sides: one layer of one or two problems (per-side HOST arrays) in ONE launch, from explicit gather
+ * tables; pieces != NULL: every side's prepared planes, the launch takes the split form; NULL: the fp32 form of the same
+ * launch.  order / bal / smask: NULL or per-side arrays as in dcl_sparse_conv_fwd_ordered.  Same rows, same epilogue; the
+ * two forms differ by fp32-sized rounding only and agree bit for bit where all piece products and partial sums are exact. */
+int64_t dcl_conv_split_weight_bytes(int kvol, int cin, int cout);
+int dcl_conv_split_weight(const float *W, int kvol, int cin, int cout, void *planes, dclStream_t stream);
+int dcl_sparse_conv_fwd_sides(int nsides, const float *const *feat, const int32_t *const *nbr, const int32_t *cap,
+                              const int32_t *n_out_host, const float *const *W, const void *const *pieces, int cin, int cout,
+                              int kvol, int subm, const float *const *scale, const float *const *shift, int relu,
+                              float *const *out, float *scratch, int64_t scratch_floats, const int32_t *const *order,
+                              const int32_t *const *bal, const uint32_t *const *smask, dclStream_t stream);
+
 /* indiceSummaryRF + indice_avgpool_fp32 (use_gs=False): rf[o] = #valid offsets,
  * out[o] = sum_k asc feat[nbr[k][o]] / (float)rf[o].  rf may be NULL.          */
 int dcl_sparse_avgpool_fwd(const float *feat, const int32_t *nbr, int cap, const int32_t *n_out_dev,
@@ -280,6 +298,25 @@ int dcl_backbone_features_pair(int batch, int S, const int32_t *channels_host, c
                                const float *const *vox_feats, const float *const *const *weights,
                                const float *const *const *scales, const float *const *const *shifts, void *const *ws2,
                                const int64_t *ws2_bytes, float *const *const *level_out, dclStream_t stream);
+/* The three feature calls with prepared filter pieces (dcl_conv_split_weight): wpieces_host[8] per side, entry i = conv layer
+ * i's planes -- that layer runs the split-bf16 conv form -- or NULL -- it keeps the fp32 kernel; wpieces == NULL: none.  The
+ * caller chooses by shape (layer widths, number of crops), never by data.                                                  */
+int dcl_backbone_features_split(const int32_t *occ, int V0, int batch, int S, void *ws, const int32_t *counts_host,
+                                const int32_t *channels_host, const float *vox_feats, const float *const *weights_host,
+                                const void *const *wpieces_host, const float *const *scales_host,
+                                const float *const *shifts_host, void *ws2, int64_t ws2_bytes, float *const *level_out_host,
+                                dclStream_t stream);
+int dcl_backbone_features_cap_split(const int32_t *occ, int V0_cap, int batch, int S, void *ws, const int32_t *counts_dev,
+                                    const int32_t *channels_host, const float *vox_feats, const float *const *weights_host,
+                                    const void *const *wpieces_host, const float *const *scales_host,
+                                    const float *const *shifts_host, void *ws2, int64_t ws2_bytes,
+                                    float *const *level_out_host, dclStream_t stream);
+int dcl_backbone_features_pair_split(int batch, int S, const int32_t *channels_host, const int32_t *V0, void *const *ws,
+                                     const int32_t *const *counts_host, const int32_t *const *counts_dev,
+                                     const float *const *vox_feats, const float *const *const *weights,
+                                     const void *const *const *wpieces, const float *const *const *scales,
+                                     const float *const *const *shifts, void *const *ws2, const int64_t *ws2_bytes,
+                                     float *const *const *level_out, dclStream_t stream);
 int dcl_point_features_cap(int n, const float *points_b4, int batch, int S, int V0_cap, void *ws,
                            const int32_t *counts_dev, const int32_t *channels_host,
                            const float *const *level_feats_host, const float *voxel_extent_host, float offset,
