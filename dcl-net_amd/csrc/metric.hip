@@ -10,17 +10,10 @@
 // per-point minima are reduced in the workgroup and accumulated per object in fixed slice order by a second tiny
 // kernel (deterministic).  sqrt is applied to the minimum squared distance (monotone, same argmin as min of norms).
 #include "common.h"
+#include "metric_table.h"
 #include <math.h>
 
 namespace {
-
-__device__ __forceinline__ void pose_point(const float *R, const float *t, float x, float y, float z, float &ox,
-                                           float &oy, float &oz) {
-  // row-vector form of bmm(cld, R^T) + t: out[c] = x*R[c][0] + y*R[c][1] + z*R[c][2] + t[c]
-  ox = __fmaf_rn(z, R[2], __fmaf_rn(y, R[1], x * R[0])) + t[0];
-  oy = __fmaf_rn(z, R[5], __fmaf_rn(y, R[4], x * R[3])) + t[1];
-  oz = __fmaf_rn(z, R[8], __fmaf_rn(y, R[7], x * R[6])) + t[2];
-}
 
 __global__ __launch_bounds__(256) void k_adds_partial(int P, const float *__restrict__ cld, const int32_t *__restrict__ cls,
                                                       const float *__restrict__ Rp, const float *__restrict__ tp,
@@ -31,36 +24,13 @@ __global__ __launch_bounds__(256) void k_adds_partial(int P, const float *__rest
   __shared__ float red[4];
   const int obj = blockIdx.y, slice = blockIdx.x, tid = threadIdx.x;
   const float *C = cld + (size_t)(cls ? cls[obj] : obj) * P * 3;
-  const float *R1 = Rp + obj * 9, *t1 = tp + obj * 3, *R2 = Rg + obj * 9, *t2 = tg + obj * 3;
-  for (int j = tid; j < P; j += 256) {
-    float x, y, z;
-    pose_point(R2, t2, C[j * 3], C[j * 3 + 1], C[j * 3 + 2], x, y, z);
-    gt[j * 3] = x; gt[j * 3 + 1] = y; gt[j * 3 + 2] = z;
-  }
+  // (the slice's arithmetic lives in metric_table.h: the trajectory kernel of metric_table.hip calls the same functions)
+  adds_stage_gt(P, C, Rg + obj * 9, tg + obj * 3, gt, tid);
   __syncthreads();
-  const int i = slice * 256 + tid;
-  float best = 0.0f;
-  if (i < P) {
-    float px, py, pz;
-    pose_point(R1, t1, C[i * 3], C[i * 3 + 1], C[i * 3 + 2], px, py, pz);
-    const bool nearest = sym ? sym[obj] != 0 : all_mode != 0;     // ADD-S: nearest gt point; ADD: the corresponding one
-    float m = INFINITY;
-    if (nearest) {
-      for (int j = 0; j < P; ++j) {
-        const float dx = px - gt[j * 3], dy = py - gt[j * 3 + 1], dz = pz - gt[j * 3 + 2];
-        m = fminf(m, __fmaf_rn(dz, dz, __fmaf_rn(dy, dy, dx * dx)));
-      }
-    } else {
-      const float dx = px - gt[i * 3], dy = py - gt[i * 3 + 1], dz = pz - gt[i * 3 + 2];
-      m = __fmaf_rn(dz, dz, __fmaf_rn(dy, dy, dx * dx));
-    }
-    best = sqrtf(m);
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) best += __shfl_xor(best, d, 64);
-  if ((tid & 63) == 0) red[tid >> 6] = best;
-  __syncthreads();
-  if (tid == 0) partial[(size_t)obj * nslices + slice] = (red[0] + red[1]) + (red[2] + red[3]);
+  const bool nearest = sym ? sym[obj] != 0 : all_mode != 0;
+  float sum[1];
+  adds_slice_sums<1>(P, slice * 256 + tid, C, Rp + obj * 9, tp + obj * 3, 0, 0, gt, nearest, red, tid, sum);
+  if (tid == 0) partial[(size_t)obj * nslices + slice] = sum[0];
 }
 
 __global__ void k_adds_finish(int b, int P, int nslices, const float *__restrict__ partial, float *__restrict__ out) {

@@ -2226,6 +2226,145 @@ def add(cld, R_pred, t_pred, R_gt, t_gt, cls=None):
     return add_s(cld, R_pred, t_pred, R_gt, t_gt, cls, mode="add")
 
 
+# ------------------------------------------------------------------------------------ device-resident evaluation tables
+TABLE_MODES = {"adds": 0, "lm": 1, "lmo": 2}          # include/dclnet_hip.h: DCL_TABLE_ADDS / _LM / _LMO
+
+
+def metric_table_arrays(mode, steps=1, n_classes=21, device="cpu"):
+    """the zeroed arrays of one table (include/dclnet_hip.h, "device-resident eval tables"): sums (T,C,4) f64 and maxd (T,C) f64
+    for "adds", counts (T,C,2) i64 for "lm" / "lmo", bad (1) i32 -- a dict; the arrays the mode does not use are None."""
+    T, C = int(steps), int(n_classes)
+    if mode not in TABLE_MODES or T < 1 or C < 1:
+        raise ValueError("metric table: mode must be one of %s, steps and n_classes >= 1" % sorted(TABLE_MODES))
+    adds = mode == "adds"
+    return {"sums": torch.zeros((T, C, 4), dtype=torch.float64, device=device) if adds else None,
+            "maxd": torch.zeros((T, C), dtype=torch.float64, device=device) if adds else None,
+            "counts": None if adds else torch.zeros((T, C, 2), dtype=torch.int64, device=device),
+            "bad": torch.zeros(1, dtype=torch.int32, device=device)}
+
+
+def _table_shape(table, mode, diameter, cuda):
+    """(T, C) of a table dict after checking dtypes, contiguity and the side (CUDA for the kernels, CPU for the twin)"""
+    if mode not in TABLE_MODES:
+        raise ValueError("metric table: mode must be one of %s" % sorted(TABLE_MODES))
+    lead = table["sums"] if mode == "adds" else table["counts"]
+    used = [("bad", table["bad"], torch.int32)]
+    used += [("sums", table["sums"], torch.float64), ("maxd", table["maxd"], torch.float64)] if mode == "adds" else \
+        [("counts", table["counts"], torch.int64), ("diameter", diameter, torch.float64)]
+    for name, t, dt in used:
+        if t is None or t.dtype != dt or not t.is_contiguous() or t.is_cuda != cuda:
+            raise RuntimeError("metric table: %s must be a contiguous %s %s tensor" % (name, "CUDA" if cuda else "CPU", dt))
+    T, C = int(lead.shape[0]), int(lead.shape[1])
+    assert tuple(lead.shape) == ((T, C, 4) if mode == "adds" else (T, C, 2)) and table["bad"].numel() == 1
+    assert mode != "adds" or tuple(table["maxd"].shape) == (T, C)
+    assert mode == "adds" or diameter.numel() == C
+    return T, C
+
+
+def _steps_of(R_pred, t_pred):
+    """R_pred (b,3,3) / (T,b,3,3) and t_pred (b,3) / (T,b,3), float32 contiguous -> (R, t, T, b, squeeze)"""
+    R_pred, t_pred = N.f32c(R_pred), N.f32c(t_pred)
+    squeeze = R_pred.dim() == 3
+    if squeeze:
+        R_pred, t_pred = R_pred.unsqueeze(0), t_pred.unsqueeze(0)
+    T, b = int(R_pred.shape[0]), int(R_pred.shape[1])
+    assert tuple(R_pred.shape) == (T, b, 3, 3) and tuple(t_pred.shape) == (T, b, 3)
+    return R_pred, t_pred, T, b, squeeze
+
+
+def _traj_buffers(T, b, P, dev, out, scratch):
+    ns = (P + 255) // 256
+    if scratch is None:
+        scratch = torch.empty((T, b, ns), dtype=torch.float32, device=dev)
+    assert scratch.dtype == torch.float32 and scratch.is_contiguous() and scratch.numel() >= T * b * ns and scratch.is_cuda
+    if out is not None:
+        assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (T, b) and out.is_cuda
+    return out, scratch
+
+
+def add_traj(cld, R_pred, t_pred, R_gt, t_gt, cls=None, sym_flag=None, mode="adds", valid=None, out=None, scratch=None):
+    """add_s for the T poses of a trajectory against one ground truth (dcl_add_traj): R_pred (T,b,3,3), t_pred (T,b,3) ->
+    dis (T,b) f32 with dis[t] == add_s(cld, R_pred[t], t_pred[t], ...) bit for bit, the ground-truth cloud posed once.
+    valid (b,) i32 or None: a crop with valid == 0 does no work and gets +inf.  out (T,b) / scratch (T,b,ceil(P/256)) f32:
+    buffers to reuse.  A (b,3,3) R_pred is one step and returns (b,)."""
+    N.need_cuda(cld, R_pred, t_pred, R_gt, t_gt, cls, sym_flag, valid)
+    cld, R_gt, t_gt = N.f32c(cld), N.f32c(R_gt), N.f32c(t_gt)
+    R_pred, t_pred, T, b, squeeze = _steps_of(R_pred, t_pred)
+    P = cld.shape[1]
+    cls = None if cls is None else N.i32c(cls)
+    sym = None if sym_flag is None else N.i32c(sym_flag)
+    valid = None if valid is None else N.i32c(valid)
+    assert all(t is None or t.numel() == b for t in (cls, sym, valid)) and R_gt.shape[0] == b
+    out, scratch = _traj_buffers(T, b, P, cld.device, out, scratch)
+    if out is None:
+        out = torch.empty((T, b), dtype=torch.float32, device=cld.device)
+    N.check(N.lib().dcl_add_traj(T, b, P, cld.shape[0], N.ptr(cld), N.ptr(cls), N.ptr(sym), {"adds": 1, "add": 0}[mode],
+                                 N.ptr(R_pred), N.ptr(t_pred), N.ptr(R_gt), N.ptr(t_gt), N.ptr(valid), N.ptr(scratch),
+                                 N.ptr(out), N.stream()), "add_traj")
+    return out[0] if squeeze else out
+
+
+def _tabulate(table, dis, cls, valid, mode, diameter, host):
+    T, C = _table_shape(table, mode, diameter, not host)
+    if host and any(t is not None and t.is_cuda for t in (dis, cls, valid)):
+        raise RuntimeError("metric_tabulate_host is the host twin: pass CPU tensors (metric_tabulate takes the GPU's)")
+    if not host:
+        N.need_cuda(dis, cls, valid)
+    dis, cls = N.f32c(dis), N.i32c(cls)
+    if dis.dim() == 1:
+        dis = dis.unsqueeze(0)
+    b = int(cls.numel())
+    assert tuple(dis.shape) == (T, b), "dis must be (steps, b) = %s, got %s" % ((T, b), tuple(dis.shape))
+    valid = None if valid is None else N.i32c(valid)
+    assert valid is None or valid.numel() == b
+    args = (TABLE_MODES[mode], T, b, C, N.ptr(dis), N.ptr(cls), N.ptr(valid), N.ptr(diameter), N.ptr(table["sums"]),
+            N.ptr(table["maxd"]), N.ptr(table["counts"]), N.ptr(table["bad"]))
+    if host:
+        N.check(N.lib().dcl_metric_tabulate_host(*args), "metric_tabulate_host")
+    else:
+        N.check(N.lib().dcl_metric_tabulate(*(args + (N.stream(),))), "metric_tabulate")
+    return table
+
+
+def metric_tabulate(table, dis, cls, valid=None, mode="adds", diameter=None):
+    """adds the crops (dis (T,b) f32, cls (b,) i32, valid (b,) i32 or None) to a device-resident table IN PLACE
+    (dcl_metric_tabulate: one launch, lane c owns class c and walks the crops in ascending order; no atomics, no read-back).
+    table: metric_table_arrays(...)'s dict; diameter (C,) f64 CUDA for "lm" / "lmo".  The semantics are the host classes'
+    (sharding.AddsTable / LmTable / LmoTable), comparisons in double on the fp32 distance."""
+    return _tabulate(table, dis, cls, valid, mode, diameter, False)
+
+
+def metric_tabulate_host(table, dis, cls, valid=None, mode="adds", diameter=None):
+    """the host twin of metric_tabulate (dcl_metric_tabulate_host, plain C++, no GPU call) on CPU tensors"""
+    return _tabulate(table, dis, cls, valid, mode, diameter, True)
+
+
+def add_tabulate(table, cld, cls, R_pred, t_pred, R_gt, t_gt, valid=None, cloud=None, sym_flag=None, metric="adds", mode="adds",
+                 diameter=None, out=None, scratch=None):
+    """one frame from poses to table in TWO launches (dcl_add_tabulate): add_traj's slice launch, then one launch that finishes
+    the distances and tabulates them -- the bits of add_traj followed by metric_tabulate.  cls (b,) i32: the table's class
+    ids; cloud (b,) i32 picks each crop's cloud of cld (n_clouds,P,3) (None: cloud i for crop i).  metric / sym_flag as
+    add_traj's mode / sym_flag.  out (T,b) f32, if given, also receives the distances."""
+    N.need_cuda(cld, cls, R_pred, t_pred, R_gt, t_gt, valid, cloud, sym_flag)
+    Tt, C = _table_shape(table, mode, diameter, True)
+    cld, R_gt, t_gt = N.f32c(cld), N.f32c(R_gt), N.f32c(t_gt)
+    R_pred, t_pred, T, b, _ = _steps_of(R_pred, t_pred)
+    assert T == Tt, "the table holds %d steps, the poses %d" % (Tt, T)
+    P = cld.shape[1]
+    cls = N.i32c(cls)
+    cloud = None if cloud is None else N.i32c(cloud)
+    sym = None if sym_flag is None else N.i32c(sym_flag)
+    valid = None if valid is None else N.i32c(valid)
+    assert all(t is None or t.numel() == b for t in (cls, cloud, sym, valid)) and R_gt.shape[0] == b
+    out, scratch = _traj_buffers(T, b, P, cld.device, out, scratch)
+    N.check(N.lib().dcl_add_tabulate(TABLE_MODES[mode], T, b, P, cld.shape[0], C, N.ptr(cld), N.ptr(cloud), N.ptr(cls),
+                                     N.ptr(sym), {"adds": 1, "add": 0}[metric], N.ptr(R_pred), N.ptr(t_pred), N.ptr(R_gt),
+                                     N.ptr(t_gt), N.ptr(valid), N.ptr(diameter), N.ptr(scratch), N.ptr(out),
+                                     N.ptr(table["sums"]), N.ptr(table["maxd"]), N.ptr(table["counts"]), N.ptr(table["bad"]),
+                                     N.stream()), "add_tabulate")
+    return table
+
+
 # ------------------------------------------------------------------------------------ crop builder
 def legacy_choice_heads(ms, n):
     """[np.random.choice(m, n, replace=False) for m in ms] on the GLOBAL legacy generator, bit for bit and with the same

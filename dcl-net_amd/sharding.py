@@ -160,6 +160,164 @@ class AddsTable(object):
         return round(float(np.mean(auc)), 2), round(float(np.mean(acc)), 2), auc, acc
 
 
+# ------------------------------------------------------------------------------------------ device-resident tables
+class _DeviceTable(object):
+    """The sufficient statistics of a host table above as tensors on `device`, one set per step (pose of a trajectory), updated
+    by ONE call per frame from device-side poses / distances, class ids and the crop builder's `valid` -- nothing is read
+    back until to_host() / finalize() (csrc/metric_table.hip; the rules: include/dclnet_hip.h, "device-resident eval tables").
+    The update is the host class's, crop by crop in ascending order with its comparisons in double, so to_host() returns the
+    table the host class would hold had it been fed `float(d)` of every fp32 distance in the same order.
+
+    OWNERSHIP: one table belongs to ONE stream.  Every call enqueues on the current stream and the update is not atomic across
+    launches: calls on a table are ordered by that stream (or by events the caller places), never issued from two streams at
+    once.  With device="cpu" the tensors are CPU tensors and the update is the library's host twin (no GPU call)."""
+    MODE = None
+    HOST = None
+
+    def __init__(self, n_classes, steps=1, device=None, diameter=None):
+        from . import ops
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        self.device = torch.device(device)
+        self.steps, self.n_classes = int(steps), int(n_classes)
+        self.arrays = ops.metric_table_arrays(self.MODE, self.steps, self.n_classes, self.device)
+        self.diameter_host = None if diameter is None else np.asarray(diameter, np.float64).copy()
+        self.diameter = None if diameter is None else torch.from_numpy(self.diameter_host).to(self.device)
+        self._buffers = {}
+
+    # the arrays by name, as the host classes name them
+    sums = property(lambda self: self.arrays["sums"])
+    maxd = property(lambda self: self.arrays["maxd"])
+    counts = property(lambda self: self.arrays["counts"])
+    bad = property(lambda self: self.arrays["bad"])
+
+    def _poses(self, rots, transs):
+        if rots.dim() == 3:
+            rots, transs = rots.unsqueeze(0), transs.unsqueeze(0)
+        if rots.shape[0] != self.steps:
+            raise ValueError("the table holds %d step(s), the poses %d" % (self.steps, rots.shape[0]))
+        return rots, transs
+
+    def add_frame(self, cld, cls, rots, transs, R_gt, t_gt, valid=None, sym_flag=None, per_crop=False):
+        """one frame from poses: rots (b,3,3) / (steps,b,3,3), transs (b,3) / (steps,b,3), one ground truth (b,3,3), (b,3);
+        cls (b,) int32 the class ids; cld (n_clouds,P,3) with crop i's cloud cld[cls[i]], or, per_crop=True, (b,P,3) with
+        crop i's cloud cld[i]; valid (b,) int32 or None (the crop builder's data["valid"]); sym_flag (b,) as add_lm's.
+        The distance is ADD-S for the YCB-V table; for the LineMOD tables ADD where sym_flag == 0 (or None), ADD-S elsewhere.
+        On the GPU: two launches, no read-back, and no allocation after the first call of a (b, P) when the tensors are
+        float32 / int32 and contiguous."""
+        from . import ops
+        rots, transs = self._poses(rots, transs)
+        T, b, P = self.steps, int(rots.shape[1]), int(cld.shape[1])
+        metric = "adds" if self.MODE == "adds" else "add"
+        if not self.device.type == "cuda":
+            pick = cld if per_crop else cld[cls.long()]
+            rows = []
+            for t in range(T):
+                d = add_s(pick, rots[t], transs[t], R_gt, t_gt) if (metric == "adds" and sym_flag is None) else \
+                    add_lm(pick, rots[t], transs[t], R_gt, t_gt, torch.zeros(b, dtype=torch.int32) if sym_flag is None else sym_flag)
+                rows.append(d.float())
+            return self.add_distances(cls, torch.stack(rows) if b else torch.zeros((T, 0)), valid)
+        key = (b, P)
+        if key not in self._buffers:
+            self._buffers[key] = torch.empty((T, b, (P + 255) // 256), dtype=torch.float32, device=self.device)
+        ops.add_tabulate(self.arrays, cld, cls, rots, transs, R_gt, t_gt, valid=valid, cloud=None if per_crop else cls,
+                         sym_flag=sym_flag, metric=metric, mode=self.MODE, diameter=self.diameter, scratch=self._buffers[key])
+        return self
+
+    def add_distances(self, cls, dis, valid=None):
+        """distances computed elsewhere: dis (b,) / (steps,b) float32, cls (b,) int32, valid (b,) int32 or None.  One launch."""
+        from . import ops
+        if dis.dim() == 1:
+            dis = dis.unsqueeze(0)
+        if dis.shape[0] != self.steps:
+            raise ValueError("the table holds %d step(s), the distances %d" % (self.steps, dis.shape[0]))
+        fn = ops.metric_tabulate if self.device.type == "cuda" else ops.metric_tabulate_host
+        fn(self.arrays, dis, cls, valid, mode=self.MODE, diameter=self.diameter)
+        return self
+
+    def add_lost(self, cls_ids):
+        """lost detections a loader reports on the HOST (the reference loaders' all_flags == 0 / flag -1): the same update
+        with an all-invalid batch, at every step -- AddsTable.add(c, inf), dropped by the LineMOD table, counted by the
+        Occlusion-LineMOD one.  Uploads the ids; reads nothing back."""
+        ids = torch.as_tensor(np.asarray(cls_ids, np.int32).reshape(-1)).to(self.device)
+        n = int(ids.numel())
+        return self.add_distances(ids, torch.zeros((self.steps, n), dtype=torch.float32, device=self.device),
+                                  torch.zeros(n, dtype=torch.int32, device=self.device))
+
+    def reduce(self, group=None):
+        """all_reduce of the tensors where they live (SUM for sums / counts, MAX for maxd and bad); a no-op when
+        torch.distributed is not initialised."""
+        if not (dist.is_available() and dist.is_initialized()):
+            return self
+        for name, op in (("sums", dist.ReduceOp.SUM), ("counts", dist.ReduceOp.SUM), ("maxd", dist.ReduceOp.MAX),
+                         ("bad", dist.ReduceOp.MAX)):
+            if self.arrays[name] is not None:
+                dist.all_reduce(self.arrays[name], op=op, group=group)
+        return self
+
+    def _read_back(self):
+        live = [(k, v) for k, v in self.arrays.items() if v is not None]
+        packed = torch.cat([v.reshape(-1).to(live[0][1].dtype) for _, v in live]).cpu().numpy()      # ONE read-back
+        host, at = {}, 0
+        for k, v in live:
+            host[k] = packed[at:at + v.numel()].reshape(tuple(v.shape)).astype(np.int32 if k == "bad" else packed.dtype)
+            at += v.numel()
+        if int(host["bad"][0]) != 0:
+            raise ValueError("a class id outside [0, %d) was fed to this table (it updated nothing)" % self.n_classes)
+        return host
+
+    def to_host(self, step=-1):
+        """the host table of one step (one read-back).  ValueError if a class id outside [0, n_classes) was ever fed."""
+        return self._host_table(self._read_back(), step)
+
+    def to_host_all(self):
+        """the host tables of every step, from one read-back"""
+        host = self._read_back()
+        return [self._host_table(host, t) for t in range(self.steps)]
+
+    def finalize(self, step=-1):
+        """to_host(step).finalize(): the reported numbers come from the host class's own code"""
+        return self.to_host(step).finalize()
+
+
+class DeviceAddsTable(_DeviceTable):
+    """AddsTable on the device (see _DeviceTable): sums (steps,C,4) / maxd (steps,C) float64, bad (1) int32."""
+    MODE = "adds"
+
+    def __init__(self, n_classes=N_CLASSES, steps=1, device=None):
+        _DeviceTable.__init__(self, n_classes, steps, device)
+
+    def _host_table(self, host, step):
+        t = AddsTable(self.n_classes)
+        t.sums, t.maxd = host["sums"][step].copy(), host["maxd"][step].copy()
+        return t
+
+
+class DeviceLmTable(_DeviceTable):
+    """LmTable on the device (see _DeviceTable): counts (steps,C,2) int64; a crop with valid == 0 is dropped."""
+    MODE = "lm"
+    HOST = LmTable
+
+    def __init__(self, diameter, steps=1, device=None):
+        _DeviceTable.__init__(self, len(diameter), steps, device, diameter)
+
+    def _host_table(self, host, step):
+        t = self.HOST(self.diameter_host)
+        t.counts = host["counts"][step].copy()
+        return t
+
+
+class DeviceLmoTable(DeviceLmTable):
+    """LmoTable on the device: DeviceLmTable, except that a crop with valid == 0 (and add_lost) counts as an attempt."""
+    MODE = "lmo"
+    HOST = LmoTable
+
+
+for _cls in (DeviceAddsTable, DeviceLmTable, DeviceLmoTable):
+    _cls.__doc__ += "\n\n" + _DeviceTable.__doc__
+del _cls
+
+
 # ------------------------------------------------------------------------------------------ rank placement on the host
 def _parse_cpulist(text):
     cpus = set()

@@ -1047,6 +1047,62 @@ int dcl_add_by_symmetry(int b, int P, const float *cld, const int32_t *cls, cons
                         const float *R_pred, const float *t_pred, const float *R_gt, const float *t_gt,
                         float *partial_scratch, float *out, dclStream_t stream);
 
+/* ------------------------------------------------- device-resident eval tables ---
+ * The sufficient statistics of the three benchmarks' tables (dcl-net_amd/sharding.py: AddsTable, LmTable, LmoTable) as plain
+ * device arrays, updated from device-side distances, class ids and the crop builder's `valid` -- nothing is read back
+ * (csrc/metric_table.hip; the shared arithmetic: csrc/metric_table.h).
+ *
+ * dcl_add_traj: the distances of T poses per crop against ONE ground truth.  R_pred (T,b,3,3), t_pred (T,b,3), R_gt (b,3,3),
+ * t_gt (b,3); cld (n_clouds,P,3); cls i32[b] picks crop i's cloud (NULL: cloud i, then n_clouds >= b); sym i32[b] / all_mode
+ * as dcl_add_by_symmetry / dcl_add_s / dcl_add: sym given -> ADD where sym[i] == 0, ADD-S elsewhere; sym NULL -> all_mode 1 =
+ * ADD-S, 0 = ADD.  partial_scratch: T * b * ceil(P/256) floats.  -> dis (T,b) fp32.  One workgroup per (crop, 256-point
+ * slice) stages the ground-truth-posed cloud once and walks the T poses (three per scan of the staged cloud, as independent
+ * minimum chains); per (pose, crop) the arithmetic is dcl_add_s's own (one shared device function, the one-pose order whatever
+ * the grouping) and the slices are added in ascending order, so dis[t] has the bits of dcl_add_s / dcl_add /
+ * dcl_add_by_symmetry called with pose t.  valid i32[b] or NULL: a crop with valid[i] == 0 does no work, its poses are not
+ * read, dis[t,i] = +inf.  A cls[i] outside [0, n_clouds) reads no cloud and gives +inf as well.  Two launches.
+ * P * 12 <= 150 KiB, b <= 65535, T >= 1; b == 0 returns 0 without a launch; anything else, a NULL required pointer or
+ * all_mode outside 0 / 1 returns DCL_EINVAL before any GPU work.
+ *
+ * The table of one benchmark, T steps (poses per crop), C classes -- the arrays a mode does not use may be NULL:
+ *     sums   f64 (T,C,4)  [n, m, sum D, #(D < 0.02)]      DCL_TABLE_ADDS
+ *     maxd   f64 (T,C)    max D over the valid D           DCL_TABLE_ADDS
+ *     counts i64 (T,C,2)  [num, success]                   DCL_TABLE_LM, DCL_TABLE_LMO   (+ diameter f64 (C), device)
+ *     bad    i32 (1)      raised (set to 1) by a class id outside [0, C); never cleared, never read by an update
+ * dcl_metric_tabulate adds the crops of dis (T,b) fp32, cls i32[b], valid i32[b] or NULL to it.  PINNED: one launch, the grid
+ * spans T, lane c owns class c and walks the crops i = 0 .. b-1 in ASCENDING order, updating its own entries only -- no
+ * atomics, the same bits on every run.  Every comparison is made in DOUBLE on the exactly converted fp32 distance:
+ * (double)d <= 0.1, (double)d < 0.02, (double)d < diameter[c]  (0.1f > 0.1 but 0.02f < 0.02 in double).  Per crop of class c:
+ *     DCL_TABLE_ADDS  AddsTable.add:  n += 1;  if d <= 0.1: m += 1, sum D += d (float64), maxd = max(maxd, d);
+ *                     if d < 0.02: that count += 1.  valid[i] == 0 is add(c, inf): n += 1 only.
+ *     DCL_TABLE_LM    LmTable.add:    num += 1, success += d < diameter[c].  valid[i] == 0: dropped (a lost detection).
+ *     DCL_TABLE_LMO   LmoTable:       as LM, but valid[i] == 0 is add_lost: num += 1.
+ * NaN and +-inf take the branches these comparisons take (misses); they are never skipped and never reach sum D.  A class id
+ * outside [0, C) updates nothing and raises bad[0].  b == 0 returns 0 without a launch; T < 1, C < 1, b < 0, an unknown mode
+ * or a NULL required pointer (dis, cls, bad, the mode's arrays) returns DCL_EINVAL before any GPU work.
+ * dcl_metric_tabulate_host: the same contract in plain C++ on HOST pointers (csrc/metric_table_host.cpp; no GPU call).
+ *
+ * dcl_add_tabulate: one frame from poses to table in TWO launches -- dcl_add_traj's slice launch, then one launch that
+ * finishes the distances and tabulates them (the same bits as dcl_add_traj followed by dcl_metric_tabulate).  cloud i32[b] or
+ * NULL picks the clouds as dcl_add_traj's cls does; cls i32[b] is the table's class id; dis (T,b) or NULL also receives the
+ * distances.  A cloud index outside [0, n_clouds) is tabulated as d = +inf and raises bad[0].                              */
+#define DCL_TABLE_ADDS 0
+#define DCL_TABLE_LM 1
+#define DCL_TABLE_LMO 2
+int dcl_add_traj(int T, int b, int P, int n_clouds, const float *cld, const int32_t *cls, const int32_t *sym, int all_mode,
+                 const float *R_pred, const float *t_pred, const float *R_gt, const float *t_gt, const int32_t *valid,
+                 float *partial_scratch, float *dis, dclStream_t stream);
+int dcl_metric_tabulate(int mode, int T, int b, int C, const float *dis, const int32_t *cls, const int32_t *valid,
+                        const double *diameter, double *sums, double *maxd, int64_t *counts, int32_t *bad,
+                        dclStream_t stream);
+int dcl_metric_tabulate_host(int mode, int T, int b, int C, const float *dis, const int32_t *cls, const int32_t *valid,
+                             const double *diameter, double *sums, double *maxd, int64_t *counts, int32_t *bad);
+int dcl_add_tabulate(int mode, int T, int b, int P, int n_clouds, int C, const float *cld, const int32_t *cloud,
+                     const int32_t *cls, const int32_t *sym, int all_mode, const float *R_pred, const float *t_pred,
+                     const float *R_gt, const float *t_gt, const int32_t *valid, const double *diameter,
+                     float *partial_scratch, float *dis, double *sums, double *maxd, int64_t *counts, int32_t *bad,
+                     dclStream_t stream);
+
 /* ------------------------------------------------------ training objective ---
  * Both-direction nearest-neighbour (Chamfer) distances of the point-set losses (models/DCL_Net.py:306-312 `CD_Dis`) without
  * the pairwise matrix (csrc/chamfer.hip).  pred (b,n,3), target (b,m,3) fp32 contiguous, any n, m >= 1.  One launch writes

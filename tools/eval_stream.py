@@ -3,7 +3,11 @@
 the per-class template cache -- CropBuilder(template_ids=True) names the template side, Network.cache_templates(builder.
 templates()) holds it -- beside the plain form in the same process: serial schedule and builder thread, images per second, and
 whether both forms give the same ADD-S distances to 1e-6 m.  The metric's template cloud is data["labels"]["points_tmp"], which
-the cached forward fills from the cache."""
+the cached forward fills from the cache.
+--device-table: that regime with draws="device" and stage2_chain(compose="device", trajectory=True), every refine iteration scored,
+under three tabulation forms alternating block by block in one process -- (1) a read-back per frame into the host table, (2) the
+distances kept and read back once at the end, (3) sharding.DeviceAddsTable -- ms per image as median and range over the blocks,
+whether (2) and (3) give the same tables bit for bit, and the metric kernels' own times from device events."""
 import importlib, json, os, sys, time
 import numpy as np
 import torch
@@ -68,7 +72,106 @@ def cached_eval_stream(dev, images=40, n_obj=6):
     return out
 
 
-if "--template-cache" in sys.argv[1:]:
+def device_table_stream(dev, images=24, blocks=6, n_obj=6, iteration=2):
+    n = 1024
+    cfg_b = dict(input_size=n, tmp_size=n, unit_voxel_extent=[0.006] * 3, voxel_num_limit=[64] * 3, voxelization_mode=4)
+    frames = [dcl.synth.make_frame(500 + i, n_obj=n_obj, tmp_size=n, empty=(i % n_obj if i % 2 else None)) for i in range(4)]
+    res = [dcl.crops.CropBuilder.resident(f["img"], f["depth"], f["label"], dev) for f in frames]
+    net = dcl.DCL_Net.Network(dcl.synth.default_cfg(n, n), mode="test")
+    net.load_state_dict(dcl.synth.synth_state_dict(net, 1))
+    net = net.to(dev).eval()
+    ref = dcl.refiner.Refiner()
+    ref.load_state_dict(dcl.synth.synth_state_dict(ref, 2))
+    ref = ref.to(dev).eval()
+    builder = dcl.crops.CropBuilder(cfg_b, frames[0]["cad_pts"], frames[0]["cad_col"], device=dev, capacity=True, template_ids=True,
+                                    draws="device", draw_seed=1)
+    net.cache_templates(builder.templates(), cfg_b["voxel_num_limit"])
+    T, C = iteration + 1, 22                                             # (class ids 1 .. 21)
+    S = dcl.sharding
+
+    def frame(i):
+        f, (im, de, la) = frames[i % 4], res[i % 4]
+        d = builder.build(im, de, la, f["rois"], f["gt_obj"], poses=f["poses"])
+        _, _, _, (rots, transs) = dcl.refiner.stage2_chain(net, ref, d, iteration, graph=True, compose="device", trajectory=True)
+        b = rots.shape[1]
+        return d["labels"]["points_tmp"].reshape(b, n, 3), d["tmp_cls"], rots, transs, d["labels"]["rot_gt"], d["labels"]["trans_gt"], d["valid"]
+
+    def distances(cld, rots, transs, Rg, tg):
+        return torch.stack([dcl.ops.add_s(cld, rots[t], transs[t], Rg, tg) for t in range(T)])
+
+    def tabulate(hosts, rows):                                           # rows (T + 2, b) on the host: distances, valid, class
+        b = rows.shape[1]
+        for t in range(T):
+            for k in range(b):
+                hosts[t].add(int(rows[T + 1, k]), float(rows[t, k]) if rows[T, k] else float("inf"))
+
+    def run(form, first):
+        hosts = [S.AddsTable(C) for _ in range(T)]
+        table, kept = S.DeviceAddsTable(C, steps=T, device=dev), []
+        for i in range(first, first + images):
+            cld, cls, rots, transs, Rg, tg, valid = frame(i)
+            if form == "device_table":
+                table.add_frame(cld, cls, rots, transs, Rg, tg, valid=valid, per_crop=True)
+                continue
+            rows = torch.cat([distances(cld, rots, transs, Rg, tg), valid.float().unsqueeze(0), cls.float().unsqueeze(0)])
+            if form == "read_back_per_frame":
+                tabulate(hosts, rows.cpu().numpy())
+            else:
+                kept.append(rows)
+        if form == "device_table":
+            return table.to_host_all()                                    # the one read-back
+        if form == "read_back_at_the_end":
+            tabulate(hosts, torch.cat(kept, dim=1).cpu().numpy())
+        return hosts
+
+    forms = ("read_back_per_frame", "read_back_at_the_end", "device_table")
+    ms = {f: [] for f in forms}
+    equal = True
+    with torch.no_grad():
+        for f in forms:                                                  # warm-up: graph captures, builder caches, scratch
+            run(f, 0)
+        for blk in range(blocks):
+            tables = {}
+            for f in (forms if blk % 2 == 0 else forms[::-1]):           # alternate the order inside the blocks
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                tables[f] = run(f, blk * images)
+                torch.cuda.synchronize()
+                ms[f].append((time.perf_counter() - t0) / images * 1e3)
+            a, b = tables["read_back_at_the_end"], tables["device_table"]
+            equal = equal and all(x.sums.tobytes() == y.sums.tobytes() and x.maxd.tobytes() == y.maxd.tobytes() for x, y in zip(a, b))
+            last = b[-1].finalize()[:2]
+        # the metric kernels alone, from device events
+        cld, cls, rots, transs, Rg, tg, valid = frame(0)
+        table = S.DeviceAddsTable(C, steps=T, device=dev)
+        dis = dcl.ops.add_traj(cld, rots, transs, Rg, tg, valid=valid)
+        ev = {}
+        for name, call in (("add_frame_two_launches", lambda: table.add_frame(cld, cls, rots, transs, Rg, tg, valid=valid, per_crop=True)),
+                           ("tabulate_one_launch", lambda: table.add_distances(cls, dis, valid)),
+                           ("add_s_per_step_%d_calls" % T, lambda: distances(cld, rots, transs, Rg, tg))):
+            for _ in range(10):
+                call()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(200):
+                call()
+            e1.record()
+            torch.cuda.synchronize()
+            ev[name] = round(e0.elapsed_time(e1) / 200 * 1e3, 2)
+    out = {"workload": "%d objects per 480x640 frame (every other frame: one empty mask), N=M=1024, template cache, draws on the "
+                       "device, stage-2 chain with %d refine iterations, all %d poses scored; %d blocks of %d images"
+                       % (n_obj, iteration, T, blocks, images),
+           "ms_per_image": {f: {"median": round(float(np.median(v)), 3), "min": round(min(v), 3), "max": round(max(v), 3)}
+                            for f, v in ms.items()},
+           "device_table_equals_read_back_at_the_end": bool(equal),
+           "last_block_mean_auc_acc": list(last),
+           "metric_kernels_us_per_call_back_to_back": ev}
+    return out
+
+
+if "--device-table" in sys.argv[1:]:
+    print(json.dumps(device_table_stream(torch.device("cuda:0")), indent=1))
+elif "--template-cache" in sys.argv[1:]:
     print(json.dumps(cached_eval_stream(torch.device("cuda:0")), indent=1))
 else:
     print(json.dumps(bench.eval_stream_bench(dcl, torch.device("cuda:0")), indent=1))
