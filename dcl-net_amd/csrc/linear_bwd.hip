@@ -16,8 +16,9 @@
 //     128 x 32 (4 x 1 waves of 32 x 32) for Q <= 32 (the xyz block, Q = 3).
 // dcl_relu_bwd: dz = h > 0 ? g : 0 (or the pooled last layer's roww[j] * gpool[crop][p]) with db[p] = sum_j dz[j][p]: lanes run
 //   over columns (a row's loads are coalesced); a workgroup owns 64 columns of one split, its four waves stream the rows through
-//   LDS in chunks and one lane per column adds them in ascending order with one accumulator; k_split_sum adds the splits
-//   ascending.
+//   LDS in chunks and one lane per column adds them in ascending order with one FLOAT64 accumulator that is rounded to fp32 once
+//   per split (a single fp32 chain over 512 masked gradients of mixed sign missed the project's float64 rule on the network's own
+//   operands, tests/test_gpu_step_replay.py); k_split_sum adds the splits ascending.
 #include "common.h"
 #include "mfma_tile.h"
 
@@ -176,7 +177,7 @@ __device__ __forceinline__ bool rb_vec_ok(const void *p, int64_t ld) { return ((
 
 // One workgroup per (strip of 64 columns, split); g == nullptr: the pooled form.  All four waves load, mask and store chunks of
 // 64 rows (coalesced 256-byte row pieces, many in flight) and leave the chunk's dz in LDS; wave 0, one lane per column, then
-// adds the chunk's rows to its accumulator in ascending order -- the bias gradient's pinned chain -- while the other waves are
+// adds the chunk's rows to its float64 accumulator in ascending order -- the bias gradient's pinned chain -- while the other waves are
 // already loading the next chunk (two LDS buffers, one barrier per chunk).  dz may be g (first form) or h (pooled form): a
 // thread reads an element before it writes it and touches no other thread's, so no pointer here is __restrict__.
 __global__ __launch_bounds__(kRbThreads) void k_relu_bwd(const float *h, int64_t ldh, const float *g, int64_t ldg,
@@ -190,7 +191,7 @@ __global__ __launch_bounds__(kRbThreads) void k_relu_bwd(const float *h, int64_t
   const int64_t row_hi = row_lo + DCL_WGRAD_ROWS < (int64_t)M ? row_lo + DCL_WGRAD_ROWS : (int64_t)M;
   const bool vh = rb_vec_ok(h, ldh), vg = g ? rb_vec_ok(g, ldg) : rb_vec_ok(gpool, ldgp), vz = rb_vec_ok(dz, lddz);
   const int nchunks = (int)((row_hi - row_lo + kRbRows - 1) / kRbRows);
-  float acc = 0.0f;
+  double acc = 0.0;
   for (int ch = 0; ch < nchunks; ++ch) {
     const int64_t j0 = row_lo + (int64_t)ch * kRbRows;
     float4 hv[kRbRows / 16], gv[kRbRows / 16];
@@ -223,10 +224,10 @@ __global__ __launch_bounds__(kRbThreads) void k_relu_bwd(const float *h, int64_t
     if (t < kRbCols) {
       const int n = row_hi - j0 < kRbRows ? (int)(row_hi - j0) : kRbRows;
 #pragma unroll 8
-      for (int r = 0; r < n; ++r) acc = acc + T[r * kRbCols + t];      // rows ascending, one accumulator
+      for (int r = 0; r < n; ++r) acc = acc + (double)T[r * kRbCols + t];      // rows ascending, one float64 accumulator
     }
   }
-  if (t < kRbCols && p0 + t < P) partial[(size_t)split * P + p0 + t] = acc;
+  if (t < kRbCols && p0 + t < P) partial[(size_t)split * P + p0 + t] = (float)acc;      // one rounding per split
 }
 
 bool aligned4(const void *p) { return ((size_t)p & 3) == 0; }

@@ -84,6 +84,18 @@ def check_train_heads(train_heads, train_dense):
     return train_heads
 
 
+TRAIN_KERNELS = dict(train_attention="fused", train_rotation="device", train_conv_wgrad="pairs", train_conv_dgrad="direct",
+                     train_pool="fused", train_norm="fused", train_dense="point_major", train_heads="kernels",
+                     train_conv_fwd="compact")
+"""Every train_* argument of Network at its own-kernel value: Network(cfg, mode="train", **TRAIN_KERNELS) is the configuration
+in which a training step runs on the library's kernels throughout (tools/train_step.py --kernels; tests/test_gpu_step_replay.py
+replays every autograd node of it).  The constraints are the constructor's: train_dense="point_major" needs
+train_attention="fused" (check_train_dense), train_heads="kernels" needs train_dense="point_major" (check_train_heads), and
+point_major does not read train_pool (its pooling is always ConfPoolPmFn).  train_conv_dgrad and train_conv_fwd go by the width
+tables ops.CONV_DGRAD_DIRECT_WIDTHS / ops.CONV_FWD_COMPACT_WIDTHS: a layer outside them keeps the default form.  Same
+parameters, buffers and state_dict keys as a default instance; eval mode reads none of it."""
+
+
 def pose_head_params(rot, trans):
     """the twelve registered tensors of two pose heads in autograd.PoseHeadsFn's order: rot W0, b0, W1, b1, W2, b2, then trans"""
     out = []

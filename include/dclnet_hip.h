@@ -802,9 +802,10 @@ int dcl_linear_wgrad(const float *a, int64_t lda, const float *b, int64_t ldb, i
  *   g == NULL:  dz[j][p] = h[j][p] > 0 ? roww[j] * gpool[j / rows_per_crop][p] : 0   (the pooled last layer: its output went
  *               into out[crop] = sum_j roww[j] h[j]; roww (M), gpool (crops x P, pitch ldgp) = the pooled gradient; the product
  *               is one rounded multiply; dz may be h),
- * and db[p] = sum_j dz[j][p] in the order of dcl_linear_wgrad: rows ascending inside a split of DCL_WGRAD_ROWS rows from +0,
- * then the splits ascending (off by at most (DCL_WGRAD_ROWS + splits) * 2^-24 * sum_j |dz_jp|); bit-identical call after call
- * and in place or not.  h == 0 and NaN give 0.  partial: scratch of dcl_linear_wgrad_splits(M) * P floats; db (P).  Lanes run
+ * and db[p] = sum_j dz[j][p] in the order of dcl_linear_wgrad: rows ascending inside a split of DCL_WGRAD_ROWS rows from +0 in
+ * ONE FLOAT64 accumulator that is rounded to fp32 once per split, then the splits ascending, one rounded fp32 add each (off by
+ * at most (splits + 1) * 2^-24 * sum_j |dz_jp|, far inside the (DCL_WGRAD_ROWS + splits) * 2^-24 * sum_j |dz_jp| of an fp32
+ * chain); bit-identical call after call and in place or not.  h == 0 and NaN give 0.  partial: scratch of dcl_linear_wgrad_splits(M) * P floats; db (P).  Lanes run
  * over columns.  M == 0 zero-fills db.  DCL_EINVAL as above (the unused form's arguments are ignored). */
 int dcl_relu_bwd(const float *h, int64_t ldh, const float *g, int64_t ldg, const float *roww, const float *gpool,
                  int64_t ldgp, int rows_per_crop, int M, int P, float *dz, int64_t lddz, float *partial, float *db,

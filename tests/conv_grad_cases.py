@@ -174,3 +174,53 @@ def fp32_oracle_error(oracle, case):
                                              c["geo"]["num"], case[3])
         _E32[case] = (float(np.abs(dx32 - c["dX"]).max()), float(np.abs(dw32.reshape(c["dW"].shape) - c["dW"]).max()))
     return _E32[case]
+
+
+# ---- operands from outside (tests/test_gpu_step_replay.py: a call recorded inside the network) ---------------------------------
+def pairs_of_table(nbr, n_out, n_in):
+    """a device-style neighbour table nbr (kvol, cap), nbr[k][o] = input row of output row o at offset k (an entry names a
+    neighbour iff it is one of the n_in rows), as the pair lists of `geometry`: (pairs (kvol, 2, cap) i64, num (kvol,))"""
+    nbr = np.asarray(nbr)[:, :int(n_out)]
+    kvol = nbr.shape[0]
+    pairs, num = np.full((kvol, 2, max(nbr.shape[1], 1)), -1, np.int64), np.zeros(kvol, np.int64)
+    for k in range(kvol):
+        o = np.nonzero((nbr[k] >= 0) & (nbr[k] < int(n_in)))[0]
+        num[k] = o.size
+        pairs[k, 0, :o.size], pairs[k, 1, :o.size] = nbr[k][o], o
+    return pairs, num
+
+
+def conv_form(X, W, G, pairs, num, n_out, dtype):
+    """forward_ref of tests/conv_fwd_cases.py and conv_backward_ref above with every array and sum in `dtype`: float64 is the
+    reference, float32 the module form (the reference's per-offset gather - GEMM - scatter) -> (out, dX, dW (kvol, cin, cout))"""
+    cin, cout = W.shape[-2], W.shape[-1]
+    X, G, W = np.asarray(X, dtype), np.asarray(G, dtype), np.asarray(W, dtype).reshape(-1, cin, cout)
+    out, dX, dW = np.zeros((int(n_out), cout), dtype), np.zeros((X.shape[0], cin), dtype), np.zeros(W.shape, dtype)
+    for k in range(W.shape[0]):
+        n = int(num[k])
+        if n <= 0:
+            continue
+        rows_in, rows_out = pairs[k, 0, :n], pairs[k, 1, :n]
+        out[rows_out] += X[rows_in] @ W[k]
+        g = G[rows_out]
+        dW[k] = X[rows_in].T @ g
+        dX[rows_in] += g @ W[k].T
+    return out, dX, dW
+
+
+def avgpool_form(X, G, pairs, num, n_out, dtype):
+    """the average pool over the same pair lists in `dtype` (avgpool_backward_ref above is its gradient in float64): rf[o] = the
+    number of pairs that name output row o, out[o] = (sum of its input rows) / rf[o], din[i] += G[o] / rf[o] -> (out, din, rf)"""
+    X, G = np.asarray(X, dtype), np.asarray(G, dtype)
+    rf = np.zeros(int(n_out), np.int64)
+    for k in range(pairs.shape[0]):
+        np.add.at(rf, pairs[k, 1, :int(num[k])], 1)
+    div = np.maximum(rf, 1).astype(dtype)[:, None]
+    out, din = np.zeros((int(n_out), X.shape[1]), dtype), np.zeros(X.shape, dtype)
+    for k in range(pairs.shape[0]):
+        n = int(num[k])
+        if n > 0:
+            rows_in, rows_out = pairs[k, 0, :n], pairs[k, 1, :n]
+            out[rows_out] += X[rows_in]
+            din[rows_in] += G[rows_out] / div[rows_out]
+    return out / div, din, rf

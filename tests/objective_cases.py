@@ -232,3 +232,31 @@ def nearest_gap(pred, target):
 
 def gap_ok(which, seed):
     return all(nearest_gap(p, t)[0] >= GAP for p, t in chamfer_pairs64(which, module_case(which, seed)))
+
+
+# ---- the same formulas in a dtype (tests/test_gpu_step_replay.py: the operands of a call recorded inside the network) -----------
+def objective_form(c, g_packed, dtype):
+    """forward64 / backward64 with every array in `dtype` (full form): float64 is the reference, float32 the module form, the
+    torch composition of models/losses.py on the Chamfer halves as given -> dict(packed, posed, Xo, Yc, conf, cd_pose, cd_Xo,
+    cd_Yc), the last seven the gradients of <g_packed, packed>, the cd_* as (pt, tp) pairs"""
+    v = {k: (x.to(dtype) if torch.is_tensor(x) else tuple(y.to(dtype) for y in x)) for k, x in c.items()}
+    leaves = {k: v[k].clone().requires_grad_() for k in ("posed", "Xo", "Yc", "conf")}
+    for k in ("cd_pose", "cd_Xo", "cd_Yc"):
+        leaves[k] = tuple(h.clone().requires_grad_() for h in v[k])
+    v.update(leaves)
+    b, n = v["posed"].shape[:2]
+    s = v["sym"].unsqueeze(1)
+    L2 = lambda a, d: torch.norm(a - d, dim=2)                                               # noqa: E731
+    cd = lambda h: 0.5 * (h[0] + h[1])                                                       # noqa: E731
+    pose = (1 - s) * L2(v["posed"], v["posed_gt"]) + s * cd(v["cd_pose"])
+    LXo = (1 - s) * L2(v["Xo"], v["cano_gt"]) + 0.5 * s * (cd(v["cd_Xo"]) + L2(v["Xo"], v["cano_pred"]))
+    LYc = (1 - s) * L2(v["Yc"], v["posed_gt"]) + 0.5 * s * (cd(v["cd_Yc"]) + L2(v["Yc"], v["posed"].detach()))
+    L = torch.cat([LXo, LYc], dim=1)
+    loss_conf = (L.detach() * v["conf"] - 0.01 * torch.log(v["conf"])).sum() / (2 * b * n)
+    loss_pose, loss_Xo, loss_Yc = pose.sum() / (b * n), LXo.sum() / (b * n), LYc.sum() / (b * n)
+    packed = torch.stack([loss_pose, loss_Xo, loss_Yc, loss_conf, loss_pose + 5 * loss_Xo + loss_Yc + loss_conf])
+    (packed * g_packed.to(dtype)).sum().backward()
+    z = lambda x: torch.zeros_like(x) if x.grad is None else x.grad                          # noqa: E731
+    out = {k: (z(x) if torch.is_tensor(x) else tuple(z(h) for h in x)) for k, x in leaves.items()}
+    out["packed"] = packed.detach()
+    return out

@@ -138,7 +138,9 @@ def test_an_empty_batch_is_not_an_error(dcl):
 
 def test_g_pts_is_optional_on_the_host_twin(dcl):
     """the one optional pointer of the rigid-points gradient: NULL is accepted (here on the host twin, with real buffers)"""
-    pts, R, t, g = torch.randn(2, 5, 3), torch.eye(3).repeat(2, 1, 1), torch.zeros(2, 3), torch.randn(2, 5, 3)
+    gen = torch.Generator().manual_seed(0)      # (unseeded draws made one sum in 230 cancel below allclose's relative bound)
+    pts, g = torch.randn(2, 5, 3, generator=gen), torch.randn(2, 5, 3, generator=gen)
+    R, t = torch.eye(3).repeat(2, 1, 1), torch.zeros(2, 3)
     g_R, g_t, g_p = dcl.ops.rigid_points_backward_host(pts, R, t, False, g, need_pts=False)
     assert g_p is None and torch.allclose(g_t, g.sum(dim=1))
 

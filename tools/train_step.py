@@ -3,6 +3,9 @@
 tools/train_step.py [b] [N] [--optim torch|fused] [--autoclip] [--chamfer chunked|fused] [--objective module|fused]
 [--conv-wgrad rows|pairs] [--conv-dgrad conv|direct] [--pool modules|fused] [--norm modules|fused]
 [--attention materialised|fused] [--dense modules|point_major] [--heads modules|kernels] [--conv-fwd tiles|compact] [--conv-fwd-all]
+[--rotation host|device] [--kernels]
+--kernels: the all-kernels configuration in one flag -- Network(**DCL_Net.TRAIN_KERNELS) with --chamfer fused --objective fused
+--optim fused --autoclip; it overrides the single switches.  --rotation: Network(train_rotation=).
 --optim fused: dcl.optim.Adam (csrc/optim.hip) instead of torch.optim.Adam; --autoclip: AutoClip(50) in front of the step, as
 the reference's training scripts run it -- the per-tensor .item() form with --optim torch, dcl.optim.AutoClip with fused.
 --chamfer / --objective: the loss module's switches (models/losses.py); --objective fused evaluates the objective on
@@ -36,14 +39,19 @@ ap.add_argument("--dense", choices=("modules", "point_major"), default="modules"
 ap.add_argument("--heads", choices=("modules", "kernels"), default="modules")
 ap.add_argument("--conv-fwd", choices=("tiles", "compact"), default="tiles")
 ap.add_argument("--conv-fwd-all", action="store_true")
+ap.add_argument("--rotation", choices=("host", "device"), default="host")
+ap.add_argument("--kernels", action="store_true")
 args = ap.parse_args()
 b, n = args.b, args.n
+switches = dict(train_conv_wgrad=args.conv_wgrad, train_conv_dgrad=args.conv_dgrad, train_pool=args.pool, train_norm=args.norm,
+                train_attention=args.attention, train_dense=args.dense, train_heads=args.heads, train_conv_fwd=args.conv_fwd,
+                train_rotation=args.rotation)
+if args.kernels:
+    switches = dict(dcl.DCL_Net.TRAIN_KERNELS)
+    args.chamfer, args.objective, args.optim, args.autoclip = "fused", "fused", "fused", True
 if args.conv_fwd_all:
     dcl.ops.CONV_FWD_COMPACT_WIDTHS = frozenset(((32, 32), (64, 64), (128, 128)))
-net = dcl.DCL_Net.Network(dcl.synth.default_cfg(n, n), mode="train", train_conv_wgrad=args.conv_wgrad,
-                          train_conv_dgrad=args.conv_dgrad, train_pool=args.pool, train_norm=args.norm,
-                          train_attention=args.attention, train_dense=args.dense, train_heads=args.heads,
-                          train_conv_fwd=args.conv_fwd)
+net = dcl.DCL_Net.Network(dcl.synth.default_cfg(n, n), mode="train", **switches)
 net.load_state_dict(dcl.synth.synth_state_dict(net, 1))
 net = net.cuda().train()
 crit = dcl.DCL_Net.losses(None, chamfer=args.chamfer, objective=args.objective)
@@ -71,6 +79,6 @@ for _ in range(3): step()
 torch.cuda.synchronize(); t0 = time.perf_counter()
 for _ in range(10): l = step()
 torch.cuda.synchronize()
-print("train step b=%d N=M=%d (optim %s%s, chamfer %s, objective %s, conv fwd %s%s, wgrad %s, dgrad %s, pool %s, norm %s, attention %s, dense %s, heads %s): %.1f ms (loss %.4f), peak mem %.2f GB" % (b, n, args.optim, " + autoclip" if clip is not None else "", args.chamfer, args.objective, args.conv_fwd, " on %s" % sorted(dcl.ops.CONV_FWD_COMPACT_WIDTHS) if args.conv_fwd == "compact" else "", args.conv_wgrad, args.conv_dgrad, args.pool, args.norm, args.attention, args.dense, args.heads, (time.perf_counter() - t0) / 10 * 1e3, float(l.detach()), torch.cuda.max_memory_allocated() / 1e9))
+print("train step b=%d N=M=%d (optim %s%s, chamfer %s, objective %s, conv fwd %s%s, wgrad %s, dgrad %s, pool %s, norm %s, attention %s, dense %s, heads %s): %.1f ms (loss %.4f), peak mem %.2f GB" % (b, n, args.optim, " + autoclip" if clip is not None else "", args.chamfer, args.objective, switches["train_conv_fwd"], " on %s" % sorted(dcl.ops.CONV_FWD_COMPACT_WIDTHS) if switches["train_conv_fwd"] == "compact" else "", switches["train_conv_wgrad"], switches["train_conv_dgrad"], switches["train_pool"], switches["train_norm"], switches["train_attention"], switches["train_dense"], switches["train_heads"], (time.perf_counter() - t0) / 10 * 1e3, float(l.detach()), torch.cuda.max_memory_allocated() / 1e9))
 if args.objective == "fused":
     print("  [loss_pose, loss_Xo, loss_Yc, loss_conf, loss_all] from one read-back: %s" % (["%.5f" % v for v in crit.packed.tolist()],))
