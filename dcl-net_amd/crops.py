@@ -13,6 +13,10 @@ CropBuilder(draws="device") is the opt-in form without that read-back: the draws
 generator (ops.crop_draw; include/dclnet_hip.h pins it) -- NOT the loader's MT19937 stream, a different sample of the same
 distribution that repeats from (draw_seed, draw_frame).  With capacity=True a frame then goes from images to `data` without a
 host synchronisation; nothing is dropped from the batch, and data["valid"] says which crops are real.
+
+build_frames / build_lm_frames / build_lmo_frames build the crops of SEVERAL frames in one call (the same crops, bit for bit, as
+the per-frame calls), and pad_to=k pads the batch to a multiple of k with rows of valid == -1 that the metric kernels skip, so
+that one captured graph serves a run whose crop count changes from call to call.
 """
 import math
 import random
@@ -475,6 +479,212 @@ class CropBuilder(object):
         _mark("end")
         return data
 
+    # ------------------------------------------------------------------------------ several frames per call
+    def _pad_rows(self, n_live, pad_to):
+        """rows of a batch of n_live crops padded to the next multiple of pad_to (None: no padding)"""
+        if pad_to is None:
+            return n_live
+        if self.draws != "device":
+            raise ValueError("pad_to needs CropBuilder(draws='device'): the host form has no `valid` to mark padding rows with")
+        k = int(pad_to)
+        if k < 1:
+            raise ValueError("pad_to must be a positive integer, got %r" % (pad_to,))
+        return -(-n_live // k) * k
+
+    def _check_capacity_rows(self, rows, what):
+        if self.capacity and rows > ops.VI_CROPS_MAX_BATCH:
+            raise ValueError("%s: %d crops in one call, the capacity form holds at most %d (ops.VI_CROPS_MAX_BATCH): pass fewer "
+                             "frames per call" % (what, rows, ops.VI_CROPS_MAX_BATCH))
+
+    def _device_rows(self, stack, src_t, fidx, cap, keys, rows, min_valid, always_filter, keep_sparse, clamp_sparse):
+        """crop_points_frames -> crop_draw_keyed -> crop_sample_valid for the n live crops of src_t, in groups of instances whose
+        four (n, cap, 3) float buffers stay under FRAMES_SCRATCH_BYTES; the last group carries the rows - n padding rows (valid -1,
+        lattice rows, counts / picks / centroid zero).  Nothing is read back.  -> feats, coords, centroid, counts, picks, valid"""
+        i_t, d_t, l_t = stack                                                      # _stack_frames' order
+        n = src_t.shape[0]
+        per = max(1, int(self.FRAMES_SCRATCH_BYTES // (48 * cap)))
+        out = []
+        for g0 in range(0, n, per):
+            g1 = min(n, g0 + per)
+            g_rows = g1 - g0 + (rows - n if g1 == n else 0)
+            xyz, col, cen, cnt = ops.crop_points_frames(d_t, l_t, i_t, fidx[g0:g1], src_t[g0:g1], self.camera, RGB_MEAN,
+                                                        self.extent * 0.5, min_valid, always_filter=always_filter, cap=cap, rows=g_rows)
+            picks, valid = ops.crop_draw_keyed(cnt, self.n_inp, self.draw_seed, keys[g0:g1], min_valid, keep_sparse=keep_sparse,
+                                               rows=g_rows)
+            feats, coords = ops.crop_sample_valid(xyz, col, picks, cnt if clamp_sparse else None, valid, self.extent[0] * 0.5,
+                                                  self.unit, int(self.limit[0]), min_valid=min_valid)
+            if g0:
+                coords[:, 0] += g0                                                 # the crop column: the group's first row
+            out.append((feats, coords, cen, cnt, picks, valid))
+        if len(out) == 1:
+            return out[0]
+        return tuple(torch.cat([o[k] for o in out]) for k in range(6))
+
+    FRAMES_SCRATCH_BYTES = 512 << 20      # budget of crop_points_frames' four (n, cap, 3) float buffers per group of instances
+
+    def build_frames(self, frames, pad_to=None):
+        """build() for SEVERAL frames in one call: frames = [(img, depth, label, rois, gt_obj[, poses]), ...] -- numpy arrays or
+        resident() tensors, one channel count, poses for every frame or for none.  Returns the dict build() would return for the
+        crops of all frames, in frame order and then instance order: every per-crop tensor (inp feats / coords with the crop
+        column counting through the batch, labels, all_centroids, tmp / tmp_cls; counts, picks, valid in the device form) is bit
+        for bit the concatenation of the per-frame build() results, obj_idx and all_flags are the per-frame tensors
+        concatenated, and the observed side is voxelised in ONE call over all crops.  New keys: frame_offsets (F+1) i32 host,
+        the crop rows of each frame; frame_objects (F+1) i32 host, each frame's range of obj_idx / all_flags; n_live, the
+        number of rows that are not padding.  Frames of different sizes are stacked as _stack_frames stacks them (depth 0,
+        label -1 outside a frame); every frame's boxes are clipped to its own size.
+        draws="device": frame f draws with the key (draw_frame + f, instance row inside its frame) -- the crops of F serial
+        build() calls -- and draw_frame advances by F; with capacity=True nothing is read back.
+        draws="host": ONE read-back of all counts; the loader's np.random calls are made frame by frame in the order of serial
+        build() calls and leave the generator in the same state; instances with an empty mask are dropped.
+        pad_to=k (device draws only): the batch is extended to the next multiple of k with PADDING rows -- valid == -1 ("not a
+        crop": the metric kernels skip such a row, include/dclnet_hip.h), the lattice dummy crop of the row's own crop index,
+        counts and picks zero, rot_gt = I, trans_gt = 0, centroid 0, the class of the first live crop (so that a template cache
+        is not missed and template_ids=False has a real template side).  The live rows are those of the unpadded call, so one
+        captured graph per multiple of k serves a run whose crop count changes from call to call.
+        ValueError: an empty list, a frame without a detected instance (before any device work, with its index), mixed channel
+        counts, more than ops.VI_CROPS_MAX_BATCH crops with capacity=True (never a silent fall-back); host form: a frame whose
+        masks are all empty (with its index)."""
+        _mark("start")
+        F = len(frames)
+        if F == 0:
+            raise ValueError("build_frames: at least one frame")
+        dev = self.dev
+        chans = set(int(fr[0].shape[2]) for fr in frames)
+        if len(chans) != 1:
+            raise ValueError("build_frames: every frame has the same number of colour channels, got %s" % sorted(chans))
+        with_poses = [len(fr) > 5 and fr[5] is not None for fr in frames]
+        if any(with_poses) != all(with_poses):
+            raise ValueError("build_frames: poses for every frame or for none")
+        src, cls_of, pose_cols, flags, objs, cand_of = [], [], [], [], [], []
+        frame_offsets, frame_objects = [0], [0]
+        for f, fr in enumerate(frames):
+            H, W = fr[1].shape
+            rois, gt_obj = np.asarray(fr[3]), np.asarray(fr[4]).astype(np.int32)
+            cand = []
+            for i, cls in enumerate(gt_obj):
+                hit = np.where(rois[:, 1] == cls)[0]
+                if hit.size:
+                    r0, r1, c0, c1 = snap_box(rois, hit[0], H, W)
+                    cand.append(i)
+                    src.append((max(r0, 0), min(r1, H), max(c0, 0), min(c1, W), int(cls), f))   # numpy slice clipping (:132)
+            if not cand:
+                raise ValueError("build_frames: no object instance of frame %d has a detection" % f)
+            if with_poses[f]:
+                pose_cols.append(np.asarray(fr[5], np.float64)[:, :, cand])
+            cand_of.append(cand)
+            flags.append(np.zeros(len(gt_obj), np.int8))
+            objs.append(gt_obj)
+            frame_offsets.append(len(src))
+            frame_objects.append(frame_objects[-1] + len(gt_obj))
+        n_live = len(src)
+        rows_total = self._pad_rows(n_live, pad_to)
+        self._check_capacity_rows(rows_total, "build_frames")
+        src_a = np.asarray(src, np.int32)
+        stack = self._stack_frames([fr[:3] for fr in frames])
+        cap = max(1, int(((src_a[:, 1] - src_a[:, 0]).clip(0) * (src_a[:, 3] - src_a[:, 2]).clip(0)).max()))
+        host = {"voxel_num_limit": torch.tensor(self.limit), "obj_idx": torch.IntTensor(np.concatenate(objs) - 1),
+                "flags": torch.IntTensor([-1]), "frame_objects": torch.IntTensor(frame_objects)}
+
+        def count_free_part(keep, rows, centroid):
+            """what does not depend on the point counts, for the live crops `keep` (indices into src) and rows - len(keep)
+            padding rows behind them (as in build(): issued while the crop kernels run)"""
+            pad = rows - len(keep)
+            cls = [int(src_a[k, 4]) for k in keep] + [int(src_a[keep[0], 4])] * pad
+            trows = [self.cls_row[c] for c in cls]
+            part = {"labels": {}}
+            if self.template_ids:
+                part["tmp_cls"] = _upload(np.asarray(cls, np.int32), dev)
+            else:
+                cls_rows = _upload(np.asarray(trows, np.int64), dev)
+                part["feats_tmp"] = self.tmp_feats[cls_rows].reshape(rows * self.n_tmp, 7)
+                part["tmp_side"] = self._template_side(trows)
+            if pose_cols:
+                P = np.concatenate(pose_cols, 2)[:, :, keep]
+                if pad:
+                    P = np.concatenate([P, np.tile(np.eye(3, 4)[:, :, None], (1, 1, pad))], 2)
+                P = _upload(P, dev)
+                # build()'s arithmetic row by row: the float64 difference, rounded to float32 once
+                part["labels"] = {"rot_gt": P[:, 0:3, :].permute(2, 0, 1).float().contiguous(),
+                                  "trans_gt": (P[:, 3, :].t() - centroid.double()).float().contiguous()}
+            part["batch_offsets"] = (torch.arange(rows + 1) * 1024).int()
+            return part
+
+        def finish(part, data, feats_inp, coords_inp, rows):
+            data["inp"] = self._inp_side(feats_inp, coords_inp, rows)
+            _mark("voxelisation issued")
+            if self.template_ids:
+                data["tmp_cls"] = part["tmp_cls"]
+            else:
+                occ, p2v, v2p, coords_tmp = part["tmp_side"]
+                data["tmp"] = {"feats": part["feats_tmp"], "coords": coords_tmp, "occupied_voxels": occ, "p2v_maps": p2v,
+                               "v2p_maps": v2p}
+            data["ready_event"] = torch.cuda.Event()
+            data["ready_event"].record(torch.cuda.current_stream(dev))
+            _mark("end")
+            return data
+
+        if self.draws == "device":
+            frame0, self.draw_frame = self.draw_frame, self.draw_frame + F
+            keys = np.stack([frame0 + src_a[:, 5].astype(np.int64),
+                             np.concatenate([np.arange(frame_offsets[f + 1] - frame_offsets[f]) for f in range(F)])], 1)
+            src_t, keys_t = _upload(src_a, dev), _upload(keys.astype(np.int64), dev)
+            feats_inp, coords_inp, centroid, counts, picks, valid = self._device_rows(
+                stack, src_t, src_a[:, 5], cap, keys_t, rows_total, MIN_VALID, False, True, True)
+            _mark("crop_points + draw + sample issued")
+            part = count_free_part(list(range(n_live)), rows_total, centroid)
+            for f in range(F):
+                flags[f][cand_of[f]] = 1
+            data = dict(host, batch_offsets=part["batch_offsets"], all_flags=torch.IntTensor(np.concatenate(flags)),
+                        all_centroids=centroid, labels=part["labels"], counts=counts, valid=valid, picks=picks,
+                        frame_offsets=torch.IntTensor(frame_offsets), n_live=n_live)
+            return finish(part, data, feats_inp, coords_inp, rows_total)
+
+        src_t = _upload(src_a, dev)
+        xyz, col, centroid, counts = ops.crop_points_frames(stack[1], stack[2], stack[0], src_a[:, 5], src_t, self.camera, RGB_MEAN,
+                                                            self.extent * 0.5, MIN_VALID, cap=cap)
+        _mark("crop_points issued")
+        cnt = counts.cpu().numpy()                                                  # the call's ONE host read-back
+        _mark("counts read back")
+        keep, kept_offsets = [], [0]
+        for f in range(F):
+            mine = [k for k in range(frame_offsets[f], frame_offsets[f + 1]) if cnt[k, 0] > 0]
+            if not mine:
+                raise ValueError("build_frames: every object mask of frame %d is empty" % f)
+            keep.extend(mine)
+            kept_offsets.append(len(keep))
+        picks = []
+        t_draw = time.perf_counter()
+        for f in range(F):                        # the loader's draws, frame by frame as serial build() calls make them
+            run = []
+
+            def flush():
+                if run:
+                    picks.extend(ops.legacy_choice_heads([int(cnt[k, 2]) for k in run], self.n_inp))
+                    del run[:]
+            for k in keep[kept_offsets[f]:kept_offsets[f + 1]]:
+                m = int(cnt[k, 2])
+                if m > self.n_inp:
+                    run.append(k)
+                else:
+                    flush()
+                    picks.append(np.random.choice(m, self.n_inp))
+                flags[f][cand_of[f][k - frame_offsets[f]]] = 1
+            flush()
+        self.draw_seconds += time.perf_counter() - t_draw
+        _mark("draws done")
+        if len(keep) != n_live:
+            kt = _upload(np.asarray(keep, np.int64), dev)
+            xyz, col, counts, centroid = xyz[kt].contiguous(), col[kt].contiguous(), counts[kt].contiguous(), centroid[kt]
+        part = count_free_part(keep, len(keep), centroid)
+        pick_t = _upload(np.stack(picks).astype(np.int64), dev)
+        feats_inp, coords_inp = ops.crop_sample(xyz, col, pick_t, counts, self.extent[0] * 0.5, self.unit, int(self.limit[0]),
+                                                min_valid=MIN_VALID)
+        data = dict(host, batch_offsets=part["batch_offsets"], all_flags=torch.IntTensor(np.concatenate(flags)),
+                    all_centroids=centroid, labels=part["labels"], counts=cnt[keep], frame_offsets=torch.IntTensor(kept_offsets),
+                    n_live=len(keep))
+        _mark("sample + labels issued")
+        return finish(part, data, feats_inp, coords_inp, len(keep))
+
     def _stack_frames(self, frames):
         """frames -> (rgb (f,H,W,C) u8, depth (f,H,W) 16-bit storage, label (f,H,W) i32) on the device.  Frames of different
         sizes are padded at the bottom and the right to the largest one with depth 0 and label -1 (a label outside every
@@ -883,6 +1093,117 @@ class CropBuilder(object):
             return feats, coords[:, 1:].contiguous(), torch.tensor([int(obj)], dtype=torch.int32, device=dev), None, centroid[0]
         return feats, coords[:, 1:].contiguous(), self.tmp_feats[row], self.tmp_vox[row], centroid[0]
 
+    def build_lm_frames(self, samples, eval_mode=False, pad_to=None):
+        """build_lm for SEVERAL samples in one call: samples = [(img, depth, mask_label, obj_bb or None, obj), ...] of one size
+        and channel count, obj_bb given for every sample or for none (None: the boxes come from ONE ops.mask_box call over the
+        stacked masks).  One crop per sample.  Returns a dict of build_frames' kind, not tuples: inp (feats, coords and the
+        voxelisation of all crops in one call), tmp or tmp_cls, all_centroids (b,3), obj (host, the class ids), all_flags,
+        frame_offsets / frame_objects (one crop, one object per sample), n_live, batch_offsets, voxel_num_limit, labels = {}
+        (the pose labels are the caller's) -- and counts, picks, valid on the device in the device form, counts on the host
+        in the host form.  Row i of every per-crop tensor is bit for bit what build_lm returns for sample i (feat_inp =
+        inp.feats rows, voxel_inp = inp.coords[:, 1:], feat_tmp / voxel_tmp likewise, centroid).
+        draws="device": every sample stays (valid == 0 where build_lm's device form says so), sample i draws with the key
+        (draw_frame + i, 0), draw_frame advances by len(samples); pad_to as in build_frames.  draws="host": the samples for
+        which build_lm returns None are dropped and flagged 0 in all_flags; one read-back of the counts per group.
+        Mask-derived boxes are device tensors, so crop_points_frames' capacity is H * W per instance: the instances are issued in
+        groups whose four (n, cap, 3) float buffers stay under FRAMES_SCRATCH_BYTES (512 MB: 34 instances of 480 x 640)."""
+        return self._lm_frames(samples, LM_MIN_VALID, eval_mode, eval_mode, pad_to, "build_lm_frames", True)
+
+    def build_lmo_frames(self, samples, pad_to=None):
+        """build_lmo for several samples in one call; samples as build_lm_frames takes them (obj_bb is not read: the box always
+        comes from the mask).  The dict of build_lm_frames."""
+        return self._lm_frames(samples, LMO_MIN_VALID, True, False, pad_to, "build_lmo_frames", False)
+
+    def _lm_frames(self, samples, min_valid, always_filter, keep_sparse, pad_to, what, read_boxes):
+        n = len(samples)
+        if n == 0:
+            raise ValueError("%s: at least one sample" % what)
+        dev = self.dev
+        if len(set(tuple(s[1].shape) for s in samples)) != 1 or len(set(int(s[0].shape[2]) for s in samples)) != 1:
+            raise ValueError("%s: every sample has the same size and channel count" % what)
+        given = [read_boxes and s[3] is not None for s in samples]
+        if any(given) != all(given):
+            raise ValueError("%s: obj_bb for every sample or for none" % what)
+        if any(s[4] is None for s in samples):
+            raise TypeError("%s: obj (the class id) is required" % what)
+        objs = [int(s[4]) for s in samples]
+        rows_total = self._pad_rows(n, pad_to)
+        self._check_capacity_rows(rows_total, what)
+        H, W = samples[0][1].shape
+        i_t = torch.from_numpy(np.stack([np.ascontiguousarray(s[0]) for s in samples])).to(dev)
+        d_t = torch.from_numpy(np.stack([np.ascontiguousarray(s[1]).astype(np.uint16) for s in samples]).view(np.int16)).to(dev)
+        l_t = torch.from_numpy(np.stack([np.ascontiguousarray(s[2]).astype(np.int32) for s in samples])).to(dev)
+        fidx = np.arange(n, dtype=np.int32)
+        if all(given):
+            src = []
+            for k, s in enumerate(samples):
+                r0, r1, c0, c1 = lm_box(s[3], H, W)
+                src.append((max(r0, 0), min(r1, H), max(c0, 0), min(c1, W), 1, k))
+            src_a = np.asarray(src, np.int32)
+            src_t = _upload(src_a, dev)
+            cap = max(1, int(((src_a[:, 1] - src_a[:, 0]).clip(0) * (src_a[:, 3] - src_a[:, 2]).clip(0)).max()))
+        else:
+            tail = _upload(np.stack([np.ones(n, np.int32), fidx], 1), dev)
+            src_t = torch.cat([ops.mask_box(l_t, 1, 0)[:, 4:8], tail], 1).contiguous()      # device rows: no host round trip
+            cap = H * W
+        stack = (i_t, d_t, l_t)
+        host = {"voxel_num_limit": torch.tensor(self.limit), "obj": torch.IntTensor(objs), "flags": torch.IntTensor([-1]),
+                "frame_objects": torch.arange(n + 1).int(), "labels": {}}
+
+        def finish(data, keep, rows, feats_inp, coords_inp):
+            cls = [objs[k] for k in keep] + [objs[keep[0]]] * (rows - len(keep))
+            data["batch_offsets"] = (torch.arange(rows + 1) * 1024).int()
+            data["inp"] = self._inp_side(feats_inp, coords_inp, rows)
+            if self.template_ids:
+                data["tmp_cls"] = _upload(np.asarray(cls, np.int32), dev)
+            else:
+                trows = [self.cls_row[c] for c in cls]
+                occ, p2v, v2p, coords_tmp = self._template_side(trows)
+                feats_tmp = self.tmp_feats[_upload(np.asarray(trows, np.int64), dev)].reshape(rows * self.n_tmp, 7)
+                data["tmp"] = {"feats": feats_tmp, "coords": coords_tmp, "occupied_voxels": occ, "p2v_maps": p2v, "v2p_maps": v2p}
+            data["ready_event"] = torch.cuda.Event()
+            data["ready_event"].record(torch.cuda.current_stream(dev))
+            return data
+
+        if self.draws == "device":
+            frame0, self.draw_frame = self.draw_frame, self.draw_frame + n
+            keys_t = _upload(np.stack([frame0 + np.arange(n, dtype=np.int64), np.zeros(n, np.int64)], 1), dev)
+            feats_inp, coords_inp, centroid, counts, picks, valid = self._device_rows(
+                stack, src_t, fidx, cap, keys_t, rows_total, min_valid, always_filter, keep_sparse, False)
+            data = dict(host, all_flags=torch.ones(n, dtype=torch.int32), all_centroids=centroid, counts=counts, valid=valid,
+                        picks=picks, frame_offsets=torch.arange(n + 1).int(), n_live=n)
+            return finish(data, list(range(n)), rows_total, feats_inp, coords_inp)
+
+        per = max(1, int(self.FRAMES_SCRATCH_BYTES // (48 * cap)))
+        keep, feats_g, coords_g, cen_g, cnt_g = [], [], [], [], []
+        for g0 in range(0, n, per):
+            g1 = min(n, g0 + per)
+            xyz, col, cen, counts = ops.crop_points_frames(d_t, l_t, i_t, fidx[g0:g1], src_t[g0:g1], self.camera, RGB_MEAN,
+                                                           self.extent * 0.5, min_valid, always_filter=always_filter, cap=cap)
+            cnt = counts.cpu().numpy()                                              # the group's host read-back
+            mine = [k for k in range(g1 - g0) if cnt[k, 0] != 0 and (cnt[k, 1] > min_valid or keep_sparse)]
+            if not mine:
+                continue
+            picks = [ops.legacy_choice_heads([int(cnt[k, 2])], self.n_inp)[0] if cnt[k, 2] > self.n_inp
+                     else np.random.choice(int(cnt[k, 2]), self.n_inp) for k in mine]     # build_lm's draw, sample by sample
+            if len(mine) != g1 - g0:
+                kt = _upload(np.asarray(mine, np.int64), dev)
+                xyz, col, cen = xyz[kt].contiguous(), col[kt].contiguous(), cen[kt]
+            pick_t = _upload(np.stack(picks).astype(np.int64), dev)
+            feats, coords = ops.crop_sample(xyz, col, pick_t, None, self.extent[0] * 0.5, self.unit, int(self.limit[0]))
+            if keep:
+                coords[:, 0] += len(keep)
+            keep.extend(g0 + k for k in mine)
+            feats_g.append(feats), coords_g.append(coords), cen_g.append(cen), cnt_g.append(cnt[mine])
+        if not keep:
+            raise ValueError("%s: every sample of this call is the loader's dummy sample" % what)
+        cat = lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts)  # noqa: E731
+        flags = np.zeros(n, np.int32)
+        flags[keep] = 1
+        data = dict(host, all_flags=torch.IntTensor(flags), all_centroids=cat(cen_g), counts=np.concatenate(cnt_g),
+                    frame_offsets=torch.IntTensor(np.concatenate([[0], np.cumsum(flags)])), n_live=len(keep))
+        return finish(data, keep, len(keep), cat(feats_g), cat(coords_g))
+
 
 class CropPrefetcher(object):
     """The role of the reference's loader workers (torch.utils.data.DataLoader(num_workers=...), tools/test_YCBV_stage1.py:133-
@@ -891,16 +1212,21 @@ class CropPrefetcher(object):
     CropBuilder.build (a trailing dict = keyword arguments).  The frames are built strictly in order by that one thread, so
     a seeded run consumes the global np.random stream exactly like a serial loop; the caller must not draw from np.random
     while iterating.  Iterating yields build()'s dicts: the caller's current stream already waits for the builder's
-    ready_event, and every tensor is marked as used on that stream (allocator hand-over between streams).  priority: of the
+    ready_event, and every tensor is marked as used on that stream (allocator hand-over between streams).  frames_per_call=k
+    (or pad_to): the frame iterator is taken k frames at a time (the last call: what is left) and iterating yields
+    build_frames(group, pad_to=pad_to)'s dicts; frames_per_call=1 with pad_to=None keeps calling build().  priority: of the
     builder's stream (0 = default; a high-priority builder stream (-1) was measured slower on 6-object frames: its kernels then
     cut into the network's); stream: an existing stream to build on (a long-lived process that has made many streams may
     want to reuse one it knows not to share a hardware queue with the network's)."""
     _END = object()
 
-    def __init__(self, builder, frames, depth=2, priority=0, stream=None):
+    def __init__(self, builder, frames, depth=2, priority=0, stream=None, frames_per_call=1, pad_to=None):
         import queue
         import threading
         self.builder, self.dev = builder, builder.dev
+        self._per_call, self._pad_to = int(frames_per_call), pad_to
+        if self._per_call < 1:
+            raise ValueError("CropPrefetcher: frames_per_call must be at least 1")
         self._q = queue.Queue(maxsize=max(1, int(depth)))
         self._stop = threading.Event()
         self._priority = int(priority)
@@ -923,6 +1249,7 @@ class CropPrefetcher(object):
             with torch.cuda.device(self.dev):
                 stream = self._stream if self._stream is not None else torch.cuda.Stream(self.dev, priority=self._priority)
                 with torch.cuda.stream(stream):
+                    group = []
                     for args in frames:
                         if self._stop.is_set():
                             return
@@ -930,8 +1257,20 @@ class CropPrefetcher(object):
                         kw = args[-1] if args and isinstance(args[-1], dict) else {}
                         if kw:
                             args = args[:-1]
-                        if not self._put(self.builder.build(*args, **kw)):
-                            return
+                        if self._per_call == 1 and self._pad_to is None:
+                            if not self._put(self.builder.build(*args, **kw)):
+                                return
+                            continue
+                        extra = set(kw) - {"poses"}
+                        if extra or len(args) > 6:
+                            raise TypeError("CropPrefetcher: build_frames takes (img, depth, label, rois, gt_obj[, poses]) per frame")
+                        group.append(args[:5] + ((kw["poses"],) if "poses" in kw else args[5:]))
+                        if len(group) == self._per_call:
+                            if not self._put(self.builder.build_frames(group, pad_to=self._pad_to)):
+                                return
+                            group = []
+                    if group and not self._put(self.builder.build_frames(group, pad_to=self._pad_to)):   # the last, shorter call
+                        return
             self._put(self._END)
         except BaseException as e:                      # handed to the consumer, raised from its next()
             self._put(e)

@@ -7,6 +7,8 @@
 //   dcl_crop_draw          m = counts[inst][2] > npoint: the npoint indices j < m with the smallest key(j), in ascending key
 //                          order -- the head of a uniform random permutation; 0 < m <= npoint: idx[j] = floor(key(j) m / 2^64),
 //                          with replacement; an instance that gives no crop: a row of zeros and valid = 0
+//   dcl_crop_draw_keyed    the same kernel with a (frame, inst) key per row: a batch of several frames draws what the frames
+//                          draw one by one (CropBuilder.build_frames)
 //   dcl_crop_sample_valid  dcl_crop_sample's rows for the valid instances (crops_body.h: crop_sample_row), a lattice dummy crop
 //                          (one point per voxel) for the others, so that nothing uninitialised is read and the capacity form's
 //                          pitch flag stays down
@@ -37,14 +39,19 @@ static_assert((kDrawList & (kDrawList - 1)) == 0, "the bitonic sort wants a powe
 DCL_HOOK_INT(g_draw_route, 0);
 
 __global__ __launch_bounds__(kDrawThreads) void k_crop_draw(int npoint, const int32_t *__restrict__ counts, int min_valid,
-                                                            int keep_sparse, uint64_t seed, uint64_t frame, int route,
-                                                            int64_t *__restrict__ sample_idx, int32_t *__restrict__ valid) {
+                                                            int keep_sparse, uint64_t seed, uint64_t frame,
+                                                            const uint64_t *__restrict__ keys /* (n,2) frame, inst or null */,
+                                                            int route, int64_t *__restrict__ sample_idx,
+                                                            int32_t *__restrict__ valid) {
   __shared__ uint64_t s_key[kDrawList];
   __shared__ int32_t s_j[kDrawList];
   __shared__ int s_hist[256];
   __shared__ int s_cnt;
   const int t = threadIdx.x, lane = t & 63, inst = blockIdx.x;
   const int32_t *c = counts + (size_t)inst * 3;
+  // dcl_crop_draw_keyed: the row's own (frame, inst) key; everything else -- counts row, output row -- stays the row's
+  const int kinst = keys ? (int)keys[(size_t)inst * 2 + 1] : inst;
+  if (keys) frame = keys[(size_t)inst * 2];
   const int ok = draw_valid(c, min_valid, keep_sparse);
   const uint32_t m = ok ? (uint32_t)c[2] : 0u;
   int64_t *out = sample_idx + (size_t)inst * npoint;
@@ -54,11 +61,11 @@ __global__ __launch_bounds__(kDrawThreads) void k_crop_draw(int npoint, const in
     return;
   }
   if (m <= (uint32_t)npoint) {                                         // with replacement
-    const uint64_t base = draw_base(seed, frame, inst, kDrawWithReplacement);
+    const uint64_t base = draw_base(seed, frame, kinst, kDrawWithReplacement);
     for (int j = t; j < npoint; j += kDrawThreads) out[j] = (int64_t)draw_mulhi(draw_key(base, (uint64_t)j), (uint64_t)m);
     return;
   }
-  const uint64_t base = draw_base(seed, frame, inst, kDrawWithoutReplacement);
+  const uint64_t base = draw_base(seed, frame, kinst, kDrawWithoutReplacement);
   const uint64_t kAll = ~0ull;
 
   // every (key, j) with key <= T -> the list, as far as it holds them; returns how many there are
@@ -149,7 +156,8 @@ __global__ __launch_bounds__(kDrawThreads) void k_crop_draw(int npoint, const in
   for (int j = t; j < npoint; j += kDrawThreads) out[j] = (int64_t)s_j[j];
 }
 
-// dcl_crop_sample's rows for the instances with valid != 0, the lattice dummy crop for the others
+// dcl_crop_sample's rows for the instances with valid > 0, the lattice dummy crop for the others (valid == 0: no crop; valid < 0:
+// a padding row of build_frames(pad_to=...), which has no xyz row at all -- it must not become an address)
 __global__ void k_crop_sample_valid(int n_inst, int npoint, int cap, const float *__restrict__ xyz, const float *__restrict__ rgb,
                                     const int64_t *__restrict__ sample_idx, const int32_t *__restrict__ counts, int min_valid,
                                     const int32_t *__restrict__ valid, float half0, float ux, float uy, float uz, int S,
@@ -158,7 +166,7 @@ __global__ void k_crop_sample_valid(int n_inst, int npoint, int cap, const float
   for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
     const int inst = (int)(e / npoint);
     const long long j = e - (long long)inst * npoint;
-    if (valid[inst]) {
+    if (valid[inst] > 0) {
       const long long i = min(max(sample_idx[e], 0ll), (long long)cap - 1);     // a draw lies in [0, m), m <= cap: nothing outside is read
       crop_sample_row(xyz + ((size_t)inst * cap + i) * 3, rgb + ((size_t)inst * cap + i) * 3,
                       counts && counts[inst * 3 + 1] <= min_valid, inst, half0, ux, uy, uz, (float)S, feats + e * 7, coords + e * 4);
@@ -181,7 +189,19 @@ DCL_API int dcl_crop_draw(int n_inst, int npoint, const int32_t *counts, int min
   DCL_CHECK_ARG(counts && sample_idx && valid);
   const int route = g_draw_route;
   hipLaunchKernelGGL(k_crop_draw, dim3(n_inst), dim3(kDrawThreads), 0, (hipStream_t)stream, npoint, counts, min_valid,
-                     keep_sparse ? 1 : 0, seed, frame, route, sample_idx, valid);
+                     keep_sparse ? 1 : 0, seed, frame, (const uint64_t *)nullptr, route, sample_idx, valid);
+  DCL_LAUNCH_CHECK();
+  return 0;
+}
+
+DCL_API int dcl_crop_draw_keyed(int n_inst, int npoint, const int32_t *counts, int min_valid, int keep_sparse, uint64_t seed,
+                                const uint64_t *keys, int64_t *sample_idx, int32_t *valid, dclStream_t stream) {
+  DCL_CHECK_ARG(n_inst >= 0 && npoint >= 1 && npoint <= DCL_CROP_DRAW_MAX_POINTS);
+  if (n_inst == 0) return 0;
+  DCL_CHECK_ARG(counts && keys && sample_idx && valid);
+  const int route = g_draw_route;
+  hipLaunchKernelGGL(k_crop_draw, dim3(n_inst), dim3(kDrawThreads), 0, (hipStream_t)stream, npoint, counts, min_valid,
+                     keep_sparse ? 1 : 0, seed, (uint64_t)0, keys, route, sample_idx, valid);
   DCL_LAUNCH_CHECK();
   return 0;
 }

@@ -16,17 +16,19 @@ DCL_API int dcl_crop_draw_keys_host(uint64_t seed, uint64_t frame, int inst, int
   return 0;
 }
 
-DCL_API int dcl_crop_draw_host(int n_inst, int npoint, const int32_t *counts, int min_valid, int keep_sparse, uint64_t seed,
-                               uint64_t frame, int64_t *sample_idx, int32_t *valid) {
-  DCL_CHECK_ARG(n_inst >= 0 && npoint >= 1 && npoint <= DCL_CROP_DRAW_MAX_POINTS);
-  if (n_inst == 0) return 0;
-  DCL_CHECK_ARG(counts && sample_idx && valid);
+namespace {
+
+// rows [0, n_inst) of the draw; row_keys (n_inst,2) {frame, inst} or null: (frame, row)
+int crop_draw_rows(int n_inst, int npoint, const int32_t *counts, int min_valid, int keep_sparse, uint64_t seed, uint64_t frame0,
+                   const uint64_t *row_keys, int64_t *sample_idx, int32_t *valid) {
   std::vector<std::pair<uint64_t, int32_t>> keys;
-  for (int inst = 0; inst < n_inst; ++inst) {
-    const int32_t *c = counts + (size_t)inst * 3;
-    int64_t *out = sample_idx + (size_t)inst * npoint;
+  for (int row = 0; row < n_inst; ++row) {
+    const int32_t *c = counts + (size_t)row * 3;
+    int64_t *out = sample_idx + (size_t)row * npoint;
+    const uint64_t frame = row_keys ? row_keys[(size_t)row * 2] : frame0;
+    const int inst = row_keys ? (int)row_keys[(size_t)row * 2 + 1] : row;
     const int ok = draw_valid(c, min_valid, keep_sparse ? 1 : 0);
-    valid[inst] = ok;
+    valid[row] = ok;
     if (!ok) {
       std::fill(out, out + npoint, (int64_t)0);
       continue;
@@ -46,6 +48,24 @@ DCL_API int dcl_crop_draw_host(int n_inst, int npoint, const int32_t *counts, in
   return 0;
 }
 
+}  // namespace
+
+DCL_API int dcl_crop_draw_host(int n_inst, int npoint, const int32_t *counts, int min_valid, int keep_sparse, uint64_t seed,
+                               uint64_t frame, int64_t *sample_idx, int32_t *valid) {
+  DCL_CHECK_ARG(n_inst >= 0 && npoint >= 1 && npoint <= DCL_CROP_DRAW_MAX_POINTS);
+  if (n_inst == 0) return 0;
+  DCL_CHECK_ARG(counts && sample_idx && valid);
+  return crop_draw_rows(n_inst, npoint, counts, min_valid, keep_sparse, seed, frame, nullptr, sample_idx, valid);
+}
+
+DCL_API int dcl_crop_draw_keyed_host(int n_inst, int npoint, const int32_t *counts, int min_valid, int keep_sparse, uint64_t seed,
+                                     const uint64_t *keys, int64_t *sample_idx, int32_t *valid) {
+  DCL_CHECK_ARG(n_inst >= 0 && npoint >= 1 && npoint <= DCL_CROP_DRAW_MAX_POINTS);
+  if (n_inst == 0) return 0;
+  DCL_CHECK_ARG(counts && keys && sample_idx && valid);
+  return crop_draw_rows(n_inst, npoint, counts, min_valid, keep_sparse, seed, 0, keys, sample_idx, valid);
+}
+
 DCL_API int dcl_crop_sample_valid_host(int n_inst, int npoint, int cap, const float *xyz, const float *rgb,
                                        const int64_t *sample_idx, const int32_t *counts, int min_valid, const int32_t *valid,
                                        float half_extent0, const float *unit_host /*3*/, int voxel_limit, float *feats,
@@ -58,7 +78,7 @@ DCL_API int dcl_crop_sample_valid_host(int n_inst, int npoint, int cap, const fl
   for (int inst = 0; inst < n_inst; ++inst)
     for (int j = 0; j < npoint; ++j) {
       const size_t e = (size_t)inst * npoint + j;
-      if (valid[inst]) {
+      if (valid[inst] > 0) {
         const long long i = std::min(std::max((long long)sample_idx[e], 0ll), (long long)cap - 1);
         crop_sample_row(xyz + ((size_t)inst * cap + i) * 3, rgb + ((size_t)inst * cap + i) * 3,
                         counts && counts[inst * 3 + 1] <= min_valid, inst, half_extent0, ux, uy, uz, (float)voxel_limit,

@@ -20,6 +20,8 @@
 //                    (three lanes, one coordinate each, LDS-fed) -- then, all threads, the in-grid count per 4096-row chunk and
 //                    the chunks' exclusive output offsets
 //   k_crop_keep      one workgroup per 4096-row chunk: filter, ordered compaction at the chunk's offset, centring
+// dcl_crop_points_frames is the same three launches over stacked frames: k_crop_mask_frames takes the crop's frame from its
+// src row, the other two kernels are the ones above (the multi-frame eval builders, crops.py: CropBuilder.build_frames).
 #include "common.h"
 #include "crops_body.h"
 
@@ -38,6 +40,27 @@ __global__ __launch_bounds__(kCropThreads) void k_crop_mask(
   const CropBox box = {boxes[inst * 4], boxes[inst * 4 + 1], boxes[inst * 4 + 2], boxes[inst * 4 + 3], obj_ids[inst]};
   crop_mask_body(depth, label, rgb, H, W, rgb_channels, box, cam, mean_r, mean_g, mean_b, cap, chunk,
                  raw_xyz + (size_t)inst * cap * 3, raw_rgb + (size_t)inst * cap * 3, ws + (size_t)inst * crop_ws_ints(cap) + 4);
+}
+
+// k_crop_mask over stacked frames (dcl_crop_points_frames): the crop's box, class AND frame come from its src row; the
+// centroid and keep kernels below never see a frame (they read the crop's own scratch), so they serve both entries
+__global__ __launch_bounds__(kCropThreads) void k_crop_mask_frames(
+    const uint16_t *__restrict__ depth, const int32_t *__restrict__ label, const uint8_t *__restrict__ rgb, int n_frames, int H,
+    int W, int rgb_channels, const int32_t *__restrict__ src /* (n,6) rmin,rmax,cmin,cmax,class,frame */, CropCam cam,
+    double mean_r, double mean_g, double mean_b, int cap, int nch, float *__restrict__ raw_xyz, float *__restrict__ raw_rgb,
+    int32_t *__restrict__ ws) {
+  const int inst = blockIdx.x / nch, chunk = blockIdx.x - inst * nch;
+  const int32_t *s = src + (size_t)inst * 6;
+  CropBox box = {s[0], s[1], s[2], s[3], s[4]};
+  int frame = s[5];
+  if (frame < 0 || frame >= n_frames) {           // no such frame: an empty crop (the host copy was checked by the call)
+    frame = 0;
+    box.rmax = box.rmin;
+  }
+  const size_t npix = (size_t)H * W;
+  crop_mask_body(depth + frame * npix, label + frame * npix, rgb + frame * npix * rgb_channels, H, W, rgb_channels, box, cam,
+                 mean_r, mean_g, mean_b, cap, chunk, raw_xyz + (size_t)inst * cap * 3, raw_rgb + (size_t)inst * cap * 3,
+                 ws + (size_t)inst * crop_ws_ints(cap) + 4);
 }
 
 // ---- 2. centroid = np.mean(cloud, axis=0): running float32 sum in row order, one division (:156); in-grid counts (:160-163)
@@ -101,6 +124,34 @@ DCL_API int dcl_crop_points(const uint16_t *depth, const int32_t *label, const u
   dcl_internal_zero_words(ws, (long long)n_inst * crop_ws_ints(cap), s);       // chunk statuses: 0 = not yet published
   hipLaunchKernelGGL(k_crop_mask, dim3(n_inst * nch), dim3(kCropThreads), 0, s, depth, label, rgb, H, W, rgb_channels, boxes,
                      obj_ids, cam, rgb_mean_host[0], rgb_mean_host[1], rgb_mean_host[2], cap, nch, raw_xyz, raw_rgb, ws);
+  hipLaunchKernelGGL(k_crop_centroid, dim3(n_inst), dim3(kCropThreads), 0, s, cap, nch, half_extent_host[0], half_extent_host[1],
+                     half_extent_host[2], min_valid, always_filter, raw_xyz, centroid, counts, ws);
+  hipLaunchKernelGGL(k_crop_keep, dim3(n_inst * nch), dim3(kCropThreads), 0, s, cap, nch, half_extent_host[0], half_extent_host[1],
+                     half_extent_host[2], raw_xyz, raw_rgb, centroid, out_xyz, out_rgb, ws);
+  DCL_LAUNCH_CHECK();
+  return 0;
+}
+
+DCL_API int dcl_crop_points_frames(const uint16_t *depth, const int32_t *label, const uint8_t *rgb, int n_frames, int H, int W,
+                                   int rgb_channels, int n_inst, const int32_t *frame_idx_host, const int32_t *src,
+                                   const float *cam_host /*6*/, const double *rgb_mean_host /*3*/,
+                                   const float *half_extent_host /*3*/, int min_valid, int always_filter, int cap,
+                                   float *raw_xyz, float *raw_rgb, float *out_xyz, float *out_rgb, float *centroid,
+                                   int32_t *counts, int32_t *ws, dclStream_t stream) {
+  DCL_CHECK_ARG(n_inst >= 0 && n_frames >= 0 && H > 0 && W > 0 && (long long)H * W < (1ll << 31) - 64 && rgb_channels >= 3 &&
+                cap > 0 && cap <= 1024 * kCropChunk);
+  if (n_inst == 0) return 0;
+  DCL_CHECK_ARG(depth && label && rgb && frame_idx_host && src && cam_host && rgb_mean_host && half_extent_host && raw_xyz &&
+                raw_rgb && out_xyz && out_rgb && centroid && counts && ws);
+  for (int i = 0; i < n_inst; ++i) DCL_CHECK_ARG(frame_idx_host[i] >= 0 && frame_idx_host[i] < n_frames);
+  const CropCam cam = {cam_host[0], cam_host[1], cam_host[2], cam_host[3], cam_host[4], cam_host[5]};
+  DCL_CHECK_ARG(cam.scale != 0.0f && cam.post_div != 0.0f);
+  const int nch = dcl_div_up(cap, kCropChunk);
+  DCL_CHECK_ARG((long long)n_inst * nch < (1ll << 31));
+  hipStream_t s = (hipStream_t)stream;
+  dcl_internal_zero_words(ws, (long long)n_inst * crop_ws_ints(cap), s);       // chunk statuses: 0 = not yet published
+  hipLaunchKernelGGL(k_crop_mask_frames, dim3(n_inst * nch), dim3(kCropThreads), 0, s, depth, label, rgb, n_frames, H, W,
+                     rgb_channels, src, cam, rgb_mean_host[0], rgb_mean_host[1], rgb_mean_host[2], cap, nch, raw_xyz, raw_rgb, ws);
   hipLaunchKernelGGL(k_crop_centroid, dim3(n_inst), dim3(kCropThreads), 0, s, cap, nch, half_extent_host[0], half_extent_host[1],
                      half_extent_host[2], min_valid, always_filter, raw_xyz, centroid, counts, ws);
   hipLaunchKernelGGL(k_crop_keep, dim3(n_inst * nch), dim3(kCropThreads), 0, s, cap, nch, half_extent_host[0], half_extent_host[1],

@@ -13,7 +13,8 @@ struct DclTableAcc {
 };
 
 // include/dclnet_hip.h pins this: every comparison in double on the exactly converted fp32 distance; NaN / inf take the
-// branches the comparisons take; valid == 0 is AddsTable.add(c, inf) / dropped (LM) / LmoTable.add_lost.
+// branches the comparisons take; valid == 0 is AddsTable.add(c, inf) / dropped (LM) / LmoTable.add_lost.  A row with
+// valid < 0 is not a crop (padding): the callers skip it before this step, so `valid` here is valid > 0.
 __host__ __device__ inline void dcl_table_step(int mode, bool valid, float df, double diam, DclTableAcc &a) {
   const double d = (double)df;
   if (mode == DCL_TABLE_ADDS) {

@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256) void k_adds_traj_partial(int T, int b, int P, 
   extern __shared__ float gt[];                 // [P][3] posed by the ground truth
   __shared__ float red[4 * kTrajPoses];
   const int obj = blockIdx.y, slice = blockIdx.x, tid = threadIdx.x;
-  if (valid && valid[obj] == 0) return;         // workgroup-uniform: no work, the poses are not read
+  if (valid && valid[obj] <= 0) return;         // workgroup-uniform: no work, the poses are not read (0: no crop, < 0: padding)
   const int cloud = cls ? cls[obj] : obj;
   if ((unsigned)cloud >= (unsigned)n_clouds) return;
   const float *C = cld + (size_t)cloud * P * 3;
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void k_adds_traj_partial(int T, int b, int P, 
 }
 
 __device__ __forceinline__ bool crop_has_distance(const int32_t *valid, const int32_t *cloud, bool by_cloud, int n_clouds, int i) {
-  if (valid && valid[i] == 0) return false;
+  if (valid && valid[i] <= 0) return false;
   return !by_cloud || (unsigned)(cloud ? cloud[i] : i) < (unsigned)n_clouds;
 }
 
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(1024) void k_metric_tabulate(int mode, int b, int C
                                                           int32_t *__restrict__ bad) {
   __shared__ float s_d[kTabChunk];
   __shared__ int32_t s_c[kTabChunk];
-  __shared__ int32_t s_v[kTabChunk];            // bit 0: valid, bit 1: raises bad (a cloud index out of range)
+  __shared__ int32_t s_v[kTabChunk];            // bit 0: valid, bit 1: raises bad (a cloud index out of range), bit 2: padding
   const int t = blockIdx.x, c = blockIdx.y * blockDim.x + threadIdx.x;
   const bool mine = c < C;
   const size_t ent = (size_t)t * C + (mine ? c : 0);
@@ -103,8 +103,9 @@ __global__ __launch_bounds__(1024) void k_metric_tabulate(int mode, int b, int C
     for (int k = threadIdx.x; k < n; k += blockDim.x) {
       const int i = base + k;
       const size_t e = (size_t)t * b + i;
-      const bool ok = !(valid && valid[i] == 0);
-      int flags = ok ? 1 : 0;
+      const int32_t v = valid ? valid[i] : 1;
+      const bool ok = v > 0;
+      int flags = ok ? 1 : (v < 0 ? 4 : 0);      // valid < 0: not a crop -- no entry and no flag is touched for it
       float d;
       if (partial) {
         const bool has = crop_has_distance(valid, cloud, true, n_clouds, i);
@@ -122,6 +123,7 @@ __global__ __launch_bounds__(1024) void k_metric_tabulate(int mode, int b, int C
     if (mine) {
       for (int k = 0; k < n; ++k) {             // ascending crop order: the pinned summation order of sum D
         const int cc = s_c[k], f = s_v[k];
+        if (f & 4) continue;
         if ((unsigned)cc >= (unsigned)C || (f & 2)) saw_bad = true;
         if (cc == c) dcl_table_step(mode, (f & 1) != 0, s_d[k], diam, a);
       }

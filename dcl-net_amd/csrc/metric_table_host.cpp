@@ -11,6 +11,7 @@ DCL_API int dcl_metric_tabulate_host(int mode, int T, int b, int C, const float 
   DCL_CHECK_ARG(dis && cls && T <= (1 << 20));
   for (int t = 0; t < T; ++t)
     for (int i = 0; i < b; ++i) {
+      if (valid && valid[i] < 0) continue;                               // not a crop: nothing is updated, bad included
       const int c = cls[i];
       if ((unsigned)c >= (unsigned)C) {
         bad[0] = 1;

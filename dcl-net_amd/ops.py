@@ -142,7 +142,9 @@ def pad_copy_many(jobs):
         assert pitch or dst.is_contiguous()
         q.dst, q.rows_dst, q.cols_dst, q.dst_pitch = dst.data_ptr(), d2.shape[0], d2.shape[1], pitch
         if torch.is_tensor(src):
-            assert src.is_cuda and src.dim() == 2 and src.stride(1) == 1 and src.element_size() in (4, 8)
+            # (a one-column source has no column stride of its own: torch keeps whatever stride the view it came from had --
+            # the class id of a ONE-crop frame is such a view)
+            assert src.is_cuda and src.dim() == 2 and (src.stride(1) == 1 or src.shape[1] == 1) and src.element_size() in (4, 8)
             assert src.element_size() == 4 or src.dtype == torch.int64
             q.src, q.rows_src, q.cols_src = src.data_ptr(), src.shape[0], src.shape[1]
             q.src_pitch = _pitch(src)
@@ -2423,6 +2425,50 @@ def crop_points(depth, label, rgb, boxes, obj_ids, cam, rgb_mean, half_extent, m
     return xyz, col, centroid, counts
 
 
+def crop_points_frames(depth, label, rgb, frame_idx, src, cam, rgb_mean, half_extent, min_valid=32, always_filter=False, cap=None,
+                       rows=None):
+    """crop_points over STACKED frames (csrc/crops.hip: dcl_crop_points_frames): depth / label (f,H,W), rgb (f,H,W,C);
+    frame_idx: the crops' frames as a HOST sequence (checked against f by the call, before any device work); src (n,6) i32
+    [rmin,rmax,cmin,cmax,class,frame] CUDA -- a device row that names no frame gives an empty crop.  One camera
+    cam = (cx,cy,fx,fy,scale[,post_div]) for all frames.  -> xyz (n,cap,3), rgb (n,cap,3), centroid (n,3), counts (n,3) i32, for
+    every instance bit for bit what crop_points returns for its frame alone.  No host synchronisation when cap is given.
+    rows >= n: centroid and counts have that many rows, the ones behind n are zero (the padding rows of a padded batch)."""
+    import numpy as np
+    N.need_cuda(depth, label, rgb, src)
+    assert depth.dtype in (torch.int16, torch.uint16) and label.dtype == torch.int32 and rgb.dtype == torch.uint8
+    assert depth.dim() == 3 and label.shape == depth.shape and rgb.dim() == 4 and rgb.shape[:3] == depth.shape
+    assert depth.is_contiguous() and label.is_contiguous() and rgb.is_contiguous()
+    n = src.shape[0]
+    assert src.dtype == torch.int32 and src.is_contiguous() and tuple(src.shape) == (n, 6)
+    fidx = np.ascontiguousarray(np.asarray(frame_idx, np.int32).reshape(-1))
+    assert fidx.shape[0] == n
+    f, H, W = depth.shape
+    dev = depth.device
+    if cap is None:
+        bx = src.cpu()
+        cap = int(max(1, ((bx[:, 1] - bx[:, 0]).clamp(min=0) * (bx[:, 3] - bx[:, 2]).clamp(min=0)).max().item())) if n else 1
+    raw_xyz = torch.empty((n, cap, 3), dtype=torch.float32, device=dev)
+    raw_rgb = torch.empty((n, cap, 3), dtype=torch.float32, device=dev)
+    xyz = torch.empty((n, cap, 3), dtype=torch.float32, device=dev)
+    col = torch.empty((n, cap, 3), dtype=torch.float32, device=dev)
+    rows = n if rows is None else int(rows)
+    assert rows >= n
+    centroid = (torch.empty if rows == n else torch.zeros)((rows, 3), dtype=torch.float32, device=dev)
+    counts = torch.zeros((rows, 3), dtype=torch.int32, device=dev)
+    ws_ints = C.c_int64(0)
+    N.check(N.lib().dcl_crop_points_ws_ints(n, int(cap), C.byref(ws_ints)), "crop_points_ws_ints")
+    ws = torch.empty(max(int(ws_ints.value), 1), dtype=torch.int32, device=dev)
+    cam_a = (C.c_float * 6)(*([float(v) for v in cam] + [1.0])[:6])
+    mean_a = (C.c_double * 3)(*[float(v) for v in rgb_mean])
+    he_a = (C.c_float * 3)(*[float(v) for v in half_extent])
+    N.check(N.lib().dcl_crop_points_frames(N.ptr(depth), N.ptr(label), N.ptr(rgb), f, H, W, rgb.shape[3], n,
+                                           fidx.ctypes.data_as(C.c_void_p), N.ptr(src), cam_a, mean_a, he_a, int(min_valid),
+                                           int(bool(always_filter)), int(cap), N.ptr(raw_xyz), N.ptr(raw_rgb), N.ptr(xyz),
+                                           N.ptr(col), N.ptr(centroid), N.ptr(counts), N.ptr(ws), N.stream()),
+            "crop_points_frames")
+    return xyz, col, centroid, counts
+
+
 def crop_sample(xyz, rgb, sample_idx, counts, half_extent0, unit, voxel_limit, npoint=None, min_valid=32):
     """Sampled points -> feats (n*npoint,7) [1,rgb,xyz] and voxelize_idx input rows (n*npoint,4) i64 [instance,ix,iy,iz]
     (dataloader_test_YCBV.py:166-177,186-190).  sample_idx (n,npoint) i64 CUDA or None (identity, template clouds)."""
@@ -2477,6 +2523,47 @@ def crop_draw_host(counts, npoint, seed, frame, min_valid=32, keep_sparse=True):
     return idx, valid
 
 
+def crop_draw_keyed(counts, npoint, seed, keys, min_valid=32, keep_sparse=True, rows=None):
+    """crop_draw with a key per row (dcl_crop_draw_keyed): keys (n,2) CUDA int64 storage of the uint64 rows {frame, inst}; row i
+    draws what row keys[i][1] of crop_draw(..., frame=keys[i][0]) draws on the same counts row -- a batch of several frames
+    draws what the frames draw one by one.  -> sample_idx (n,npoint) i64, valid (n) i32, both CUDA; no host synchronisation.
+    counts may hold more than n rows (the zero rows of a padded batch): the first n are drawn.  rows >= n: the outputs have that many rows, the ones behind n are PADDING (sample_idx 0, valid -1: "not a crop")."""
+    N.need_cuda(counts, keys)
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.dim() == 2 and counts.shape[1] == 3
+    n = keys.shape[0]
+    assert keys.dtype == torch.int64 and keys.is_contiguous() and tuple(keys.shape) == (n, 2) and counts.shape[0] >= n
+    rows = n if rows is None else int(rows)
+    assert rows >= n
+    if rows > n:
+        idx = torch.zeros((rows, max(int(npoint), 0)), dtype=torch.int64, device=counts.device)
+        valid = torch.full((rows,), -1, dtype=torch.int32, device=counts.device)
+    else:
+        idx = torch.empty((n, max(int(npoint), 0)), dtype=torch.int64, device=counts.device)
+        valid = torch.empty((n,), dtype=torch.int32, device=counts.device)
+    N.check(N.lib().dcl_crop_draw_keyed(n, int(npoint), N.ptr(counts), int(min_valid), int(bool(keep_sparse)),
+                                        C.c_uint64(int(seed) & _U64), N.ptr(keys), N.ptr(idx), N.ptr(valid), N.stream()),
+            "crop_draw_keyed")
+    return idx, valid
+
+
+def crop_draw_keyed_host(counts, npoint, seed, keys, min_valid=32, keep_sparse=True):
+    """the host twin of crop_draw_keyed (dcl_crop_draw_keyed_host, plain C++, no GPU call): counts (n,3) and keys (n,2)
+    {frame, inst} integer numpy arrays -> (sample_idx (n,npoint) int64, valid (n) int32) numpy arrays."""
+    import numpy as np
+    cnt = np.ascontiguousarray(np.asarray(counts).astype(np.int32)).reshape(-1, 3)
+    n = cnt.shape[0]
+    ks = None if keys is None else np.ascontiguousarray(np.asarray(keys).astype(np.uint64)).reshape(-1, 2)
+    assert ks is None or ks.shape[0] == n
+    idx = np.zeros((n, max(int(npoint), 0)), np.int64)
+    valid = np.zeros(n, np.int32)
+    N.check(N.lib().dcl_crop_draw_keyed_host(n, int(npoint), cnt.ctypes.data_as(C.c_void_p), int(min_valid), int(bool(keep_sparse)),
+                                             C.c_uint64(int(seed) & _U64),
+                                             C.c_void_p(0) if ks is None else ks.ctypes.data_as(C.c_void_p),
+                                             idx.ctypes.data_as(C.c_void_p), valid.ctypes.data_as(C.c_void_p)),
+            "crop_draw_keyed_host")
+    return idx, valid
+
+
 def crop_draw_keys_host(seed, frame, inst, s, n):
     """base(seed, frame, inst, s) and key(0..n-1) of the draw's generator (dcl_crop_draw_keys_host) -> (int, uint64 array)"""
     import numpy as np
@@ -2488,15 +2575,18 @@ def crop_draw_keys_host(seed, frame, inst, s, n):
 
 
 def crop_sample_valid(xyz, rgb, sample_idx, counts, valid, half_extent0, unit, voxel_limit, min_valid=32):
-    """crop_sample for the instances with valid != 0 (the same rows, bit for bit), a lattice dummy crop -- point j at the centre
+    """crop_sample for the instances with valid > 0 (the same rows, bit for bit), a lattice dummy crop -- point j at the centre
     of voxel (j mod S, (j div S) mod S, j div S^2), colour 0 -- for the others (csrc/crop_draw.hip).  sample_idx (n,npoint) i64,
-    valid (n) i32, counts (n,3) i32 or None, all CUDA.  -> feats (n*npoint,7), coords (n*npoint,4) i64."""
+    valid (n) i32, counts (n,3) i32 or None, all CUDA.  -> feats (n*npoint,7), coords (n*npoint,4) i64.
+    sample_idx / valid may have MORE rows than xyz (crop_draw_keyed(rows=...)): the rows behind xyz's are padding, their valid
+    must be <= 0 (the kernel addresses xyz, rgb and counts only through rows with valid > 0) and they get lattice rows too."""
     N.need_cuda(xyz, rgb, sample_idx, counts, valid)
     assert xyz.is_contiguous() and rgb.is_contiguous() and xyz.dtype == torch.float32 and rgb.dtype == torch.float32
-    n, cap = xyz.shape[0], xyz.shape[1]
+    n, cap = valid.shape[0], xyz.shape[1]
+    assert n >= xyz.shape[0]
     assert sample_idx.dtype == torch.int64 and sample_idx.is_contiguous() and sample_idx.shape[0] == n
-    assert valid.dtype == torch.int32 and valid.is_contiguous() and valid.shape[0] == n
-    assert counts is None or (counts.dtype == torch.int32 and counts.is_contiguous() and counts.shape[0] == n)
+    assert valid.dtype == torch.int32 and valid.is_contiguous()
+    assert counts is None or (counts.dtype == torch.int32 and counts.is_contiguous() and counts.shape[0] >= xyz.shape[0])
     npoint = sample_idx.shape[1]
     dev = xyz.device
     feats = torch.empty((n * npoint, 7), dtype=torch.float32, device=dev)

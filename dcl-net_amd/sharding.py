@@ -201,7 +201,9 @@ class _DeviceTable(object):
     def add_frame(self, cld, cls, rots, transs, R_gt, t_gt, valid=None, sym_flag=None, per_crop=False):
         """one frame from poses: rots (b,3,3) / (steps,b,3,3), transs (b,3) / (steps,b,3), one ground truth (b,3,3), (b,3);
         cls (b,) int32 the class ids; cld (n_clouds,P,3) with crop i's cloud cld[cls[i]], or, per_crop=True, (b,P,3) with
-        crop i's cloud cld[i]; valid (b,) int32 or None (the crop builder's data["valid"]); sym_flag (b,) as add_lm's.
+        crop i's cloud cld[i]; valid (b,) int32 or None (the crop builder's data["valid"]: > 0 a crop, 0 a candidate that gave
+        none, < 0 a PADDING row of build_frames(pad_to=...) -- not a crop: its poses are not read and no entry of any table, nor
+        `bad`, is touched for it); sym_flag (b,) as add_lm's.
         The distance is ADD-S for the YCB-V table; for the LineMOD tables ADD where sym_flag == 0 (or None), ADD-S elsewhere.
         On the GPU: two launches, no read-back, and no allocation after the first call of a (b, P) when the tensors are
         float32 / int32 and contiguous."""

@@ -834,6 +834,18 @@ int dcl_crop_points(const uint16_t *depth, const int32_t *label, const uint8_t *
                     const double *rgb_mean_host, const float *half_extent_host, int min_valid, int always_filter, int cap,
                     float *raw_xyz, float *raw_rgb, float *out_xyz, float *out_rgb, float *centroid,
                     int32_t *counts, int32_t *ws, dclStream_t stream);
+/* dcl_crop_points over STACKED frames (the multi-frame eval builders, crops.py: CropBuilder.build_frames): depth / label
+ * (n_frames,H,W), rgb (n_frames,H,W,rgb_channels); crop i reads frame src[i][5] of them, src (n_inst,6) i32 DEVICE rows
+ * {rmin, rmax, cmin, cmax, class id, frame} (the row layout of dcl_crop_points_posed).  frame_idx_host (n_inst) is the HOST
+ * copy of column 5: the call checks it against n_frames before any device work (DCL_EINVAL); a device row that disagrees and
+ * names no frame gives an empty crop (counts row 0), never an address.  One camera (cam_host) for all frames; every other
+ * argument, the scratch and ws as dcl_crop_points.  The same three kernel bodies (csrc/crops_body.h) without a pose:
+ * out_xyz, out_rgb, centroid and counts of instance i are BIT FOR BIT what dcl_crop_points writes for that frame alone.   */
+int dcl_crop_points_frames(const uint16_t *depth, const int32_t *label, const uint8_t *rgb, int n_frames, int H, int W,
+                           int rgb_channels, int n_inst, const int32_t *frame_idx_host, const int32_t *src,
+                           const float *cam_host, const double *rgb_mean_host, const float *half_extent_host,
+                           int min_valid, int always_filter, int cap, float *raw_xyz, float *raw_rgb, float *out_xyz,
+                           float *out_rgb, float *centroid, int32_t *counts, int32_t *ws, dclStream_t stream);
 /* Sampled points -> feats rows [1,r,g,b,x,y,z] (n*npoint,7) and voxelize_idx input rows [instance,ix,iy,iz] (n*npoint,4)
  * i64 (:166-176,186-190): voxel = trunc((xyz + half_extent0)/unit) in float32, clamped to [0,voxel_limit-1] first for
  * instances with counts[i][1] <= min_valid.  sample_idx (n,npoint) i64 = the caller's np.random.choice draws (NULL:
@@ -867,8 +879,15 @@ int dcl_crop_sample(int n_inst, int npoint, int cap, const float *xyz, const flo
  * read back, no allocation: capturable.  DCL_EINVAL before any device work for npoint < 1 or > DCL_CROP_DRAW_MAX_POINTS,
  * n_inst < 0, or a null pointer of a non-empty call; n_inst == 0 returns 0 and launches nothing.
  *
+ * dcl_crop_draw_keyed: dcl_crop_draw with a key PER ROW instead of (frame, row): keys (n_inst,2) u64 DEVICE rows
+ * {frame, inst}, and row i draws with base(seed, keys[i][0], keys[i][1], s) on counts row i -- so row i equals row keys[i][1]
+ * of dcl_crop_draw(..., frame = keys[i][0]) on the same counts row (one kernel body; the pinned constants above hold through
+ * it).  A batch that stacks several frames draws what the frames draw one by one.  keys[i][1] < 2^31.  Same selection routes,
+ * limits, DCL_EINVAL rules (keys is a required pointer of a non-empty call) and capturability.
+ *
  * dcl_crop_sample_valid: dcl_crop_sample's rows (the same body, csrc/crops_body.h: the same bits) for every instance with
- * valid[inst] != 0 (sample_idx required; an index is clamped to [0, cap - 1] before it addresses anything), and for the
+ * valid[inst] > 0 (0: no crop; < 0: not a crop at all, the padding rows of CropBuilder.build_frames(pad_to=...), which have
+ * no xyz row and are never used as an address) (sample_idx required; an index is clamped to [0, cap - 1] before it addresses anything), and for the
  * others a LATTICE DUMMY CROP, S = voxel_limit: point j lies at the centre of voxel (ix, iy, iz) = (j mod S, (j div S) mod S,
  * j div S^2) -- feats row [1, 0, 0, 0, x, y, z] with x = (float(ix) + 0.5f) * unit[0] - half_extent0 (uncontracted; y, z alike),
  * coords row [inst, ix, iy, iz].  Requires npoint <= S^3 (and <= DCL_CROP_DRAW_MAX_POINTS).  Why not zeros: an instance
@@ -884,6 +903,10 @@ int dcl_crop_draw(int n_inst, int npoint, const int32_t *counts, int min_valid, 
 int dcl_crop_draw_host(int n_inst, int npoint, const int32_t *counts, int min_valid, int keep_sparse, uint64_t seed,
                        uint64_t frame, int64_t *sample_idx, int32_t *valid);
 int dcl_crop_draw_keys_host(uint64_t seed, uint64_t frame, int inst, int s, int n, uint64_t *base, uint64_t *keys);
+int dcl_crop_draw_keyed(int n_inst, int npoint, const int32_t *counts, int min_valid, int keep_sparse, uint64_t seed,
+                        const uint64_t *keys, int64_t *sample_idx, int32_t *valid, dclStream_t stream);
+int dcl_crop_draw_keyed_host(int n_inst, int npoint, const int32_t *counts, int min_valid, int keep_sparse, uint64_t seed,
+                             const uint64_t *keys, int64_t *sample_idx, int32_t *valid);
 int dcl_crop_sample_valid(int n_inst, int npoint, int cap, const float *xyz, const float *rgb, const int64_t *sample_idx,
                           const int32_t *counts, int min_valid, const int32_t *valid, float half_extent0,
                           const float *unit_host, int voxel_limit, float *feats, int64_t *coords, dclStream_t stream);
@@ -1079,7 +1102,11 @@ int dcl_add_by_symmetry(int b, int P, const float *cld, const int32_t *cls, cons
  *     DCL_TABLE_LM    LmTable.add:    num += 1, success += d < diameter[c].  valid[i] == 0: dropped (a lost detection).
  *     DCL_TABLE_LMO   LmoTable:       as LM, but valid[i] == 0 is add_lost: num += 1.
  * NaN and +-inf take the branches these comparisons take (misses); they are never skipped and never reach sum D.  A class id
- * outside [0, C) updates nothing and raises bad[0].  b == 0 returns 0 without a launch; T < 1, C < 1, b < 0, an unknown mode
+ * outside [0, C) updates nothing and raises bad[0].
+ * THE THIRD STATE OF valid: valid[i] < 0 is "not a crop" (a padding row of a batch padded to a fixed size).  dcl_add_traj does
+ * no work for it, does not read its poses and writes dis[t,i] = +inf; dcl_metric_tabulate, dcl_add_tabulate and the host twin
+ * update NOTHING for it in any mode -- no entry, and not bad either, whatever its class id or cloud index.  valid[i] == 0 and
+ * valid[i] > 0 mean what they mean above.  b == 0 returns 0 without a launch; T < 1, C < 1, b < 0, an unknown mode
  * or a NULL required pointer (dis, cls, bad, the mode's arrays) returns DCL_EINVAL before any GPU work.
  * dcl_metric_tabulate_host: the same contract in plain C++ on HOST pointers (csrc/metric_table_host.cpp; no GPU call).
  *

@@ -37,6 +37,23 @@ int main() {
         for (int j = 0; j < npoint; ++j) CHECK(idx[(size_t)i * npoint + j] >= 0 && idx[(size_t)i * npoint + j] < (ms[i] > 0 ? ms[i] : 1));
       }
     }
+    // the keyed twin on scrambled (frame, inst) keys: row i is row keys[i][1] of the plain draw with frame keys[i][0], made here
+    // on a counts array that has the row's counts at that position
+    {
+      std::vector<uint64_t> rk((size_t)n * 2);
+      std::vector<int32_t> kvalid((size_t)n), c2((size_t)n * 3), v2((size_t)n);
+      std::vector<int64_t> kidx((size_t)n * npoint), idx2((size_t)n * npoint);
+      for (int i = 0; i < n; ++i) { rk[2 * i] = (i % 3 == 0) ? (1ull << 40) + 5 : (uint64_t)(i % 3); rk[2 * i + 1] = (uint64_t)((i * 7 + 3) % n); }
+      CHECK(dcl_crop_draw_keyed_host(n, npoint, counts.data(), 32, 1, 0xFEDCBA9876543210ull, rk.data(), kidx.data(), kvalid.data()) == 0);
+      for (int i = 0; i < n; ++i) {
+        const int r = (int)rk[2 * i + 1];
+        for (int q = 0; q < n * 3; ++q) c2[q] = 0;
+        c2[3 * r] = c2[3 * r + 1] = c2[3 * r + 2] = ms[i];
+        CHECK(dcl_crop_draw_host(n, npoint, c2.data(), 32, 1, 0xFEDCBA9876543210ull, rk[2 * i], idx2.data(), v2.data()) == 0);
+        CHECK(kvalid[i] == v2[r]);
+        for (int j = 0; j < npoint; ++j) CHECK(kidx[(size_t)i * npoint + j] == idx2[(size_t)r * npoint + j]);
+      }
+    }
     // the sample rows over clouds of exactly the rows the draw may address, one instance without a crop among them
     const int inst = 3, cap = 700, S = 64;
     const int32_t c3[inst * 3] = {cap, cap, cap, 0, 0, 0, cap, 20, cap};
@@ -64,6 +81,16 @@ int main() {
   CHECK(dcl_crop_draw_host(1, 8, nullptr, 32, 1, 0, 0, i1, &v1) == DCL_EINVAL);
   CHECK(dcl_crop_draw_host(0, 8, nullptr, 32, 1, 0, 0, nullptr, nullptr) == 0);
   CHECK(dcl_crop_draw_host(1, 8, c1, 32, 1, 2, 7, i1, &v1) == 0 && v1 == 1);
+  const uint64_t k1[2] = {7, 0};
+  CHECK(dcl_crop_draw_keyed_host(1, 0, c1, 32, 1, 0, k1, i1, &v1) == DCL_EINVAL);
+  CHECK(dcl_crop_draw_keyed_host(1, 4097, c1, 32, 1, 0, k1, i1, &v1) == DCL_EINVAL);
+  CHECK(dcl_crop_draw_keyed_host(1, 8, c1, 32, 1, 0, nullptr, i1, &v1) == DCL_EINVAL);
+  CHECK(dcl_crop_draw_keyed_host(0, 8, nullptr, 32, 1, 0, nullptr, nullptr, nullptr) == 0);
+  // the pinned constants through the keyed twin: base(2,7,3,1) with m = 5 <= npoint draws floor(key(j) * 5 / 2^64)
+  const uint64_t k2[2] = {7, 3};
+  CHECK(dcl_crop_draw_keyed_host(1, 8, c1, 32, 1, 2, k2, i1, &v1) == 0 && v1 == 1);
+  CHECK(i1[0] == (int64_t)(((unsigned __int128)0xc1bed6510d07ff6cull * 5) >> 64));
+  CHECK(i1[1] == (int64_t)(((unsigned __int128)0x3c33370239554870ull * 5) >> 64));
   printf("crop_draw_host_check: ok\n");
   return 0;
 }

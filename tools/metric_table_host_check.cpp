@@ -94,6 +94,11 @@ int main() {
         CHECK(got.bad == 1);
         got.bad = 0;
         CHECK(got.same(before));
+        // rows of valid < 0 are not crops: nothing changes and `bad` stays down, whatever their class id and distance
+        const int32_t pad_cls[4] = {0, -1, C, 1 << 30}, pad_valid[4] = {-1, -7, -1, INT32_MIN};
+        const float d4[12] = {0.01f, NAN, INFINITY, 0.0f, 0.01f, NAN, INFINITY, 0.0f, 0.01f, NAN, INFINITY, 0.0f};
+        CHECK(run(mode, got, 4, d4, pad_cls, pad_valid) == 0);
+        CHECK(got.bad == 0 && got.same(before));
       }
   // refusals
   Table t1(1, 2);
