@@ -81,6 +81,10 @@ def _open(path):
     L.dcl_template_rows.argtypes = [vp, i64, i, i, vp, i, vp, i, vp, i, vp, vp]
     L.dcl_template_rows_host.argtypes = [vp, i64, i, i, vp, i, vp, i, vp, i, vp]
     L.dcl_template_rows.restype = L.dcl_template_rows_host.restype = i
+    # csrc/optim.hip, csrc/optim_clip_host.cpp: an int64 count and a double percentile among the pointers
+    L.dcl_autoclip_observe.argtypes = [i64] + [vp] * 4 + [C.c_double, vp, vp]
+    L.dcl_autoclip_observe_host.argtypes = [i64] + [vp] * 4 + [C.c_double, vp]
+    L.dcl_autoclip_observe.restype = L.dcl_autoclip_observe_host.restype = i
     for fn in (L.dcl_linear_narrow_fwd, L.dcl_linear_narrow_fwd_host, L.dcl_linear_narrow_bwd_ws_bytes, L.dcl_linear_narrow_bwd,
                L.dcl_linear_narrow_bwd_host, L.dcl_pose_heads_train_fwd, L.dcl_pose_heads_train_fwd_host,
                L.dcl_pose_heads_train_bwd_ws_bytes, L.dcl_pose_heads_train_bwd, L.dcl_pose_heads_train_bwd_host):

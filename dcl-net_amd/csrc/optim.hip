@@ -15,7 +15,11 @@
 // dcl_grad_sqnorm: launch 1 writes one float64 partial per chunk (exact products, fixed lane order, fixed tree), launch 2
 // (one workgroup) adds a tensor's partials in chunk order, the tensors in table order, and takes the root.  No atomics.
 // dcl_adam_step: the five documented fp32 lines per element, in that order (the library is built with -ffp-contract=off).
+// dcl_adam_step_dev: the same body with the clip factor read from device memory.
+// dcl_autoclip_observe: AutoClip's percentile over a history kept sorted on the device -- launch 1 inserts this step's norm
+// (one lane per held entry, ping-pong buffers), launch 2 (one lane) evaluates np.percentile and the factor (optim_clip.h).
 #include "common.h"
+#include "optim_clip.h"
 #include <math.h>
 
 namespace {
@@ -146,9 +150,12 @@ __device__ __forceinline__ void adam_element(float &p, float g, float &m, float 
   p = p - step_size * (m / d);
 }
 
-__global__ __launch_bounds__(kThreads) void k_adam_step(const dclOptimTensor *__restrict__ table,
-                                                        const int32_t *__restrict__ chunk_tensor,
-                                                        const int64_t *__restrict__ chunk_begin, AdamConst k) {
+// one chunk's update; kDevScale: the clip factor is read from device memory here instead of arriving in k
+template <bool kDevScale>
+__device__ __forceinline__ void adam_chunk(const dclOptimTensor *__restrict__ table, const int32_t *__restrict__ chunk_tensor,
+                                           const int64_t *__restrict__ chunk_begin, AdamConst k,
+                                           const float *__restrict__ grad_scale_dev) {
+  if (kDevScale) k.grad_scale = grad_scale_dev[0];
   const int c = blockIdx.x, tid = threadIdx.x;
   const dclOptimTensor T = table[chunk_tensor[c]];
   const int64_t begin = chunk_begin[c];
@@ -188,6 +195,32 @@ __global__ __launch_bounds__(kThreads) void k_adam_step(const dclOptimTensor *__
   }
 }
 
+__global__ __launch_bounds__(kThreads) void k_adam_step(const dclOptimTensor *__restrict__ table,
+                                                        const int32_t *__restrict__ chunk_tensor,
+                                                        const int64_t *__restrict__ chunk_begin, AdamConst k) {
+  adam_chunk<false>(table, chunk_tensor, chunk_begin, k, nullptr);
+}
+
+__global__ __launch_bounds__(kThreads) void k_adam_step_dev(const dclOptimTensor *__restrict__ table,
+                                                            const int32_t *__restrict__ chunk_tensor,
+                                                            const int64_t *__restrict__ chunk_begin, AdamConst k,
+                                                            const float *__restrict__ grad_scale_dev) {
+  adam_chunk<true>(table, chunk_tensor, chunk_begin, k, grad_scale_dev);
+}
+
+// AutoClip's insertion: one lane per held entry (optim_clip.h: dcl_clip_insert_lane); lane 0 exists for n == 0 as well
+__global__ __launch_bounds__(kThreads) void k_autoclip_insert(int64_t n, const double *__restrict__ src, double *__restrict__ dst,
+                                                              double *__restrict__ arrival, const double *__restrict__ norm) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n && i != 0) return;
+  dcl_clip_insert_lane(n, src, dst, arrival, norm[0], i);
+}
+
+__global__ __launch_bounds__(64) void k_autoclip_finish(int64_t n, const double *__restrict__ sorted, const double *__restrict__ norm,
+                                                        double percentile, double *__restrict__ out) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) dcl_clip_finish(n, sorted, norm[0], percentile, out);
+}
+
 }  // namespace
 
 DCL_API int dcl_grad_sqnorm(int n_tensors, const dclOptimTensor *table, int n_chunks, const int32_t *chunk_tensor,
@@ -206,6 +239,17 @@ DCL_API int dcl_grad_sqnorm(int n_tensors, const dclOptimTensor *table, int n_ch
   return 0;
 }
 
+static AdamConst adam_const(float grad_scale, float beta1, float beta2, float eps) {
+  AdamConst k;
+  k.grad_scale = grad_scale;
+  k.beta1 = beta1;
+  k.omb1 = (float)(1.0 - (double)beta1);
+  k.beta2 = beta2;
+  k.omb2 = (float)(1.0 - (double)beta2);
+  k.eps = eps;
+  return k;
+}
+
 DCL_API int dcl_adam_step(int n_tensors, const dclOptimTensor *table, int n_chunks, const int32_t *chunk_tensor,
                           const int64_t *chunk_begin, float grad_scale, float beta1, float beta2, float eps,
                           dclStream_t stream) {
@@ -216,14 +260,38 @@ DCL_API int dcl_adam_step(int n_tensors, const dclOptimTensor *table, int n_chun
   if (n_tensors == 0) return 0;
   DCL_CHECK_ARG(n_chunks >= n_tensors);
   DCL_CHECK_ARG(table && chunk_tensor && chunk_begin);
-  AdamConst k;
-  k.grad_scale = grad_scale;
-  k.beta1 = beta1;
-  k.omb1 = (float)(1.0 - (double)beta1);
-  k.beta2 = beta2;
-  k.omb2 = (float)(1.0 - (double)beta2);
-  k.eps = eps;
+  const AdamConst k = adam_const(grad_scale, beta1, beta2, eps);
   hipLaunchKernelGGL(k_adam_step, dim3(n_chunks), dim3(kThreads), 0, (hipStream_t)stream, table, chunk_tensor, chunk_begin, k);
+  DCL_LAUNCH_CHECK();
+  return 0;
+}
+
+DCL_API int dcl_adam_step_dev(int n_tensors, const dclOptimTensor *table, int n_chunks, const int32_t *chunk_tensor,
+                              const int64_t *chunk_begin, const float *grad_scale_dev, float beta1, float beta2, float eps,
+                              dclStream_t stream) {
+  DCL_CHECK_ARG(n_tensors >= 0 && n_chunks >= 0);
+  DCL_CHECK_ARG(beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f);
+  DCL_CHECK_ARG(eps > 0.0f);
+  if (n_tensors == 0) return 0;
+  DCL_CHECK_ARG(n_chunks >= n_tensors);
+  DCL_CHECK_ARG(table && chunk_tensor && chunk_begin && grad_scale_dev);
+  DCL_CHECK_ARG((reinterpret_cast<uintptr_t>(grad_scale_dev) & 3) == 0);
+  const AdamConst k = adam_const(1.0f, beta1, beta2, eps);            // grad_scale: the kernel reads it
+  hipLaunchKernelGGL(k_adam_step_dev, dim3(n_chunks), dim3(kThreads), 0, (hipStream_t)stream, table, chunk_tensor, chunk_begin,
+                     k, grad_scale_dev);
+  DCL_LAUNCH_CHECK();
+  return 0;
+}
+
+DCL_API int dcl_autoclip_observe(int64_t n, const double *sorted_src, double *sorted_dst, double *arrival, const double *norm,
+                                 double percentile, void *out, dclStream_t stream) {
+  DCL_AUTOCLIP_CHECK_ARGS();
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t lanes = n > 0 ? n : 1;
+  hipLaunchKernelGGL(k_autoclip_insert, dim3((unsigned)((lanes + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, n, sorted_src,
+                     sorted_dst, arrival, norm);
+  DCL_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_autoclip_finish, dim3(1), dim3(64), 0, s, n, (const double *)sorted_dst, norm, percentile, (double *)out);
   DCL_LAUNCH_CHECK();
   return 0;
 }

@@ -1558,6 +1558,54 @@ def adam_step(table, chunk_tensor, chunk_begin, grad_scale, beta1, beta2, eps):
             "adam_step")
 
 
+def adam_step_dev(table, chunk_tensor, chunk_begin, grad_scale, beta1, beta2, eps):
+    """adam_step with the clip factor read from device memory when the kernel runs (dcl_adam_step_dev): grad_scale = a
+    one-element fp32 CUDA tensor, in [0, 1] by its producer's contract (ops.autoclip_observe's fp32 slot).  Nothing is read
+    back; equal factor bits give adam_step's bits."""
+    n_tensors, n_chunks = _optim_tables(table, chunk_tensor, chunk_begin)
+    N.need_cuda(grad_scale)
+    assert grad_scale.dtype == torch.float32 and grad_scale.numel() == 1 and grad_scale.device == table.device
+    N.check(N.lib().dcl_adam_step_dev(n_tensors, N.ptr(table), n_chunks, N.ptr(chunk_tensor), N.ptr(chunk_begin),
+                                      N.ptr(grad_scale), _c_float(beta1), _c_float(beta2), _c_float(eps), N.stream()),
+            "adam_step_dev")
+
+
+AUTOCLIP_OUT_DOUBLES = 4       # include/dclnet_hip.h: DCL_AUTOCLIP_OUT_BYTES / 8 -- {norm, clip_value, scale} and the fp32 slot
+AUTOCLIP_SCALE_F32_INDEX = 6   # DCL_AUTOCLIP_SCALE_F32_OFFSET / 4: where (float)scale lies in out.view(torch.float32)
+
+
+def _autoclip_observe(n, sorted_src, sorted_dst, arrival, norm, percentile, out, host):
+    n = int(n)
+    ts = (sorted_src, sorted_dst, arrival, norm, out)
+    if host:
+        assert not any(t.is_cuda for t in ts)
+    else:
+        N.need_cuda(*ts)
+        assert all(t.device == out.device for t in ts)
+    assert all(t.dtype == torch.float64 and t.dim() == 1 and t.is_contiguous() for t in ts)
+    assert n >= 0 and sorted_src.numel() >= n and sorted_dst.numel() >= n + 1 and arrival.numel() >= n + 1
+    assert norm.numel() == 1 and out.numel() == AUTOCLIP_OUT_DOUBLES
+    args = (n, N.ptr(sorted_src), N.ptr(sorted_dst), N.ptr(arrival), N.ptr(norm), float(percentile), N.ptr(out))
+    if host:
+        N.check(N.lib().dcl_autoclip_observe_host(*args), "autoclip_observe_host")
+    else:
+        N.check(N.lib().dcl_autoclip_observe(*(args + (N.stream(),))), "autoclip_observe")
+    return out
+
+
+def autoclip_observe(n, sorted_src, sorted_dst, arrival, norm, percentile, out):
+    """AutoClip's host arithmetic on the device (dcl_autoclip_observe, two launches, no read-back): inserts norm (1,) f64 into
+    the n ascending norms of sorted_src -> sorted_dst[:n + 1] (NaN last, the new one behind equal ones), writes arrival[n],
+    and out (AUTOCLIP_OUT_DOUBLES,) f64 = {norm, np.percentile(history, percentile), min(1.0, clip / (norm + 1e-6))} with the
+    factor rounded once to fp32 at out.view(torch.float32)[AUTOCLIP_SCALE_F32_INDEX].  n is the HOST's count of held norms."""
+    return _autoclip_observe(n, sorted_src, sorted_dst, arrival, norm, percentile, out, False)
+
+
+def autoclip_observe_host(n, sorted_src, sorted_dst, arrival, norm, percentile, out):
+    """the host twin of autoclip_observe (dcl_autoclip_observe_host, plain C++, no GPU call) on CPU tensors"""
+    return _autoclip_observe(n, sorted_src, sorted_dst, arrival, norm, percentile, out, True)
+
+
 def three_interpolate(features, idx, weight):
     N.need_cuda(features, idx, weight)
     assert features.is_contiguous() and idx.is_contiguous() and weight.is_contiguous()

@@ -12,9 +12,11 @@ Here the same three lines of a training script,
     clipper(model)
     opt.step()
 
-are one norm pass over all gradients (two launches), ONE 8-byte read-back (inherent: the clip value is a percentile over a
-host-side history that includes this step) and one update launch per parameter group, the clip factor multiplied in on the
-way (p.grad itself is not rewritten: DESIGN.md section 9).  The kernels are driven by two small device tables
+are one norm pass over all gradients (two launches), ONE 8-byte read-back (the clip value is a percentile over a host-side
+history that includes this step) and one update launch per parameter group, the clip factor multiplied in on the way
+(p.grad itself is not rewritten: DESIGN.md section 9).  dcl.optim.DeviceAutoClip(50, optimizer=opt) in AutoClip's place
+keeps that history sorted on the GPU and takes the percentile there: no read-back at all, and a cost that does not grow
+with the length of the run.  The kernels are driven by two small device tables
 (include/dclnet_hip.h at dclOptimTensor) that are packed on the host every step and uploaded with one asynchronous copy
 from pinned memory; there is no CPU fallback."""
 import numpy as np
@@ -191,7 +193,7 @@ class Adam(torch.optim.Optimizer):
         self._ring = _TableRing(dev)
         self._layouts = {}
         self._pending = None          # tables a clipper has already uploaded for the coming step
-        self._grad_scale = 1.0        # handed over by AutoClip for the next step() only
+        self._grad_scale = 1.0        # handed over by AutoClip for the next step() only (DeviceAutoClip: a device fp32)
 
     @staticmethod
     def _new_flat(total, dev):
@@ -289,8 +291,16 @@ class Adam(torch.optim.Optimizer):
         return out
 
     def set_grad_scale(self, scale):
-        """multiply the gradients by `scale` inside the NEXT step() only (what AutoClip hands over)"""
-        self._grad_scale = float(scale)
+        """multiply the gradients by `scale` inside the NEXT step() only (what AutoClip hands over).  A float goes to the
+        kernel as an argument; a one-element fp32 CUDA tensor (what DeviceAutoClip hands over) is read by the kernel when it
+        runs (dcl_adam_step_dev), so the host never sees the value."""
+        if isinstance(scale, torch.Tensor):
+            if not scale.is_cuda or scale.dtype != torch.float32 or scale.numel() != 1 or scale.device != self._flat[0].device:
+                raise TypeError("dcl.optim.Adam.set_grad_scale: a tensor factor must be one fp32 element on the parameters' GPU "
+                                "(got %s, %s, %d elements)" % (scale.dtype, scale.device, scale.numel()))
+            self._grad_scale = scale
+        else:
+            self._grad_scale = float(scale)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -303,8 +313,9 @@ class Adam(torch.optim.Optimizer):
         self._pending = None
         if plan is None:
             return loss
+        update = ops.adam_step_dev if isinstance(scale, torch.Tensor) else ops.adam_step
         for (t0, n, c0, nc), (_, beta1, beta2, eps) in zip(plan.layout.groups, plan.hyper):
-            ops.adam_step(*plan.layout.views(plan.slot.dev, t0, n, c0, nc), scale, beta1, beta2, eps)
+            update(*plan.layout.views(plan.slot.dev, t0, n, c0, nc), scale, beta1, beta2, eps)
         _TableRing.used(plan.slot)
         self._steps.numpy()[plan.layout.step_index] += 1.0           # state[p]["step"] are views of it
         # the kernel wrote through raw pointers: tell autograd (and every cache keyed on _version) that these tensors changed
@@ -405,3 +416,101 @@ class AutoClip(object):
     def load_state_dict(self, sd):
         self.percentile = sd["percentile"]
         self.history = [float(x) for x in sd["history"]]
+
+
+class DeviceAutoClip(object):
+    """AutoClip(percentile, optimizer=a dcl.optim.Adam) with the history on the GPU (csrc/optim.hip: dcl_autoclip_observe), as
+    sharding.DeviceAddsTable is of AddsTable: the norms seen so far are kept SORTED in device memory, `clipper(model)` inserts
+    this step's norm there, evaluates np.percentile and the factor on the device (the arithmetic is pinned line by line in
+    include/dclnet_hip.h) and hands the optimizer a POINTER to the factor, which the next step()'s kernels read.  No
+    read-back, so the host goes on issuing the next step; and the cost does not grow with the run as np.percentile over a
+    Python list does.  Same norm kernel, same fp32 factor: the parameters have AutoClip's bits.
+
+    A call is the optimizer's norm pass and two launches on the current stream -- the one the optimizer launches on; nothing
+    is allocated after construction except at growth: when the `capacity` entries are used up the buffers double by device
+    copies (the host counts its own calls, so it knows when without asking the device).  `model` is not looked at: the
+    optimizer's parameters are what is clipped.  The model-only form is AutoClip's.
+
+    history (arrival order), clip_value and scale (of the latest call; None before it) each READ BACK: for logging and
+    checkpoints, not for the loop.  state_dict() / load_state_dict() carry AutoClip's keys, and a dict moves between the
+    two classes either way; loading sorts once on the host.  A norm with the sign bit set (-0.0 included) is refused there:
+    the order of the device history is defined for norms (>= +0, +inf, NaN; NaN last)."""
+
+    def __init__(self, percentile=50, optimizer=None, capacity=4096):
+        if not isinstance(optimizer, Adam):
+            raise TypeError("DeviceAutoClip(optimizer=...) takes a dcl.optim.Adam (got %s); the model-only form is AutoClip's"
+                            % type(optimizer).__name__)
+        if not 0 <= percentile <= 100:
+            raise ValueError("DeviceAutoClip: percentile must be in [0, 100] (got %r)" % (percentile,))
+        if int(capacity) < 1:
+            raise ValueError("DeviceAutoClip: capacity must be >= 1 (got %r)" % (capacity,))
+        self.percentile = percentile
+        self.optimizer = optimizer
+        self.device = optimizer._flat[0].device
+        self._n = 0
+        self._observed = False        # whether _out holds a call's results
+        self._out = torch.zeros(ops.AUTOCLIP_OUT_DOUBLES, dtype=torch.float64, device=self.device)
+        self._scale32 = self._out.view(torch.float32)[ops.AUTOCLIP_SCALE_F32_INDEX:ops.AUTOCLIP_SCALE_F32_INDEX + 1]
+        self._allocate(int(capacity))
+
+    def _allocate(self, capacity):
+        """fresh buffers of `capacity` entries: the sorted history ([0] holds it, [1] takes the next insertion) and the arrivals"""
+        self.capacity = capacity
+        self._sorted = [torch.empty(capacity, dtype=torch.float64, device=self.device) for _ in range(2)]
+        self._arrival = torch.empty(capacity, dtype=torch.float64, device=self.device)
+
+    def _grow(self):
+        n, src, arrival = self._n, self._sorted[0], self._arrival
+        self._allocate(2 * self.capacity)
+        self._sorted[0][:n].copy_(src[:n])                # device to device, on the stream of the launches around them
+        self._arrival[:n].copy_(arrival[:n])              # (the third buffer is the next insertion's destination: all written)
+
+    def __len__(self):
+        return self._n
+
+    def __call__(self, model=None):
+        _, norm = self.optimizer.grad_norm()
+        if self._n == self.capacity:
+            self._grow()
+        src, dst = self._sorted
+        ops.autoclip_observe(self._n, src, dst, self._arrival, norm, self.percentile, self._out)
+        self._sorted = [dst, src]
+        self._n += 1
+        self._observed = True
+        self.optimizer.set_grad_scale(self._scale32)
+
+    @property
+    def history(self):
+        """the norms in arrival order, as AutoClip.history (a read-back of the whole history)"""
+        return self._arrival[:self._n].cpu().tolist()
+
+    @property
+    def clip_value(self):
+        """of the latest call (a read-back); None before it"""
+        return float(self._out[1].cpu()) if self._observed else None
+
+    @property
+    def scale(self):
+        """the factor of the latest call, in double (a read-back); None before it"""
+        return float(self._out[2].cpu()) if self._observed else None
+
+    def state_dict(self):
+        return {"percentile": self.percentile, "history": self.history}
+
+    def load_state_dict(self, sd):
+        history = np.array([float(x) for x in sd["history"]], dtype=np.float64)
+        if np.signbit(history).any():
+            raise ValueError("DeviceAutoClip.load_state_dict: entry %d of the history has its sign bit set (%r): not a norm"
+                             % (int(np.flatnonzero(np.signbit(history))[0]), float(history[np.signbit(history)][0])))
+        if not 0 <= sd["percentile"] <= 100:
+            raise ValueError("DeviceAutoClip: percentile must be in [0, 100] (got %r)" % (sd["percentile"],))
+        self.percentile = sd["percentile"]
+        n = history.size
+        capacity = self.capacity
+        while capacity < n:
+            capacity *= 2
+        self._allocate(capacity)
+        self._sorted[0][:n].copy_(torch.from_numpy(np.sort(history)))     # np.sort: ascending, NaN last -- the device's key
+        self._arrival[:n].copy_(torch.from_numpy(history))
+        self._n = n
+        self._observed = False

@@ -1504,6 +1504,47 @@ int dcl_grad_sqnorm(int n_tensors, const dclOptimTensor *table, int n_chunks, co
  * launch.                                                                                                                  */
 int dcl_adam_step(int n_tensors, const dclOptimTensor *table, int n_chunks, const int32_t *chunk_tensor,
                   const int64_t *chunk_begin, float grad_scale, float beta1, float beta2, float eps, dclStream_t stream);
+/* dcl_adam_step with the clip factor read from DEVICE memory when the kernel runs (grad_scale_dev: one fp32, 4-byte aligned;
+ * what dcl_autoclip_observe leaves at DCL_AUTOCLIP_SCALE_F32_OFFSET): the same kernel body and the same five lines, so a
+ * factor of equal bits gives dcl_adam_step's bits.  The host cannot look at the factor: it is the producer's contract that it
+ * lies in [0, 1].  A NULL grad_scale_dev (with n_tensors > 0) and everything dcl_adam_step refuses return DCL_EINVAL before
+ * any GPU call.                                                                                                            */
+int dcl_adam_step_dev(int n_tensors, const dclOptimTensor *table, int n_chunks, const int32_t *chunk_tensor,
+                      const int64_t *chunk_begin, const float *grad_scale_dev, float beta1, float beta2, float eps,
+                      dclStream_t stream);
+
+/* AutoClip's arithmetic on the device (csrc/optim.hip; the shared functions: csrc/optim_clip.h): the history of gradient norms
+ * is kept SORTED in device memory, one call inserts this step's norm and evaluates the reference's
+ *     clip_value = np.percentile(history, percentile);  scale = min(1.0, clip_value / (norm + 1e-6))
+ * (tools/train_YCBV_stage1.py:212-231) without a read-back.  n = the norms already held -- a HOST integer, the caller counts
+ * its own calls; sorted_src = those n float64 ascending; norm = the device double dcl_grad_sqnorm wrote (x below).
+ *   Key of the order: ascending numeric, a NaN of either sign behind everything else, all NaN equal.  Entries are norms:
+ *     >= +0, +inf or NaN (an entry with the sign bit set is the caller's to refuse).  The new entry goes BEHIND equal ones.
+ *   Launch 1, one lane per held entry (256-lane workgroups, at least one): lane i stores sorted_src[i] at sorted_dst[i], or
+ *     at [i + 1] when it is behind x by the key; the lane whose entry is the last not behind x also stores x at [i + 1], lane 0
+ *     stores it at [0] when every entry is behind x (or n == 0) and writes arrival[n] = x.  sorted_dst[0 .. n] and arrival[n]
+ *     are written, each slot once, nothing beyond them; sorted_src and sorted_dst must not overlap (ping-pong buffers).
+ *   Launch 2, one lane, with s = sorted_dst and every operation rounded on its own (no contraction into fma):
+ *     m = n + 1;  vi = (m - 1) * (percentile / 100.0);  lo = floor(vi);  t = vi - lo;  hi = min(lo + 1, m - 1)
+ *     a = s[lo];  b = s[hi];  d = b - a
+ *     clip = (t >= 0.5) ? b - d * (1 - t) : a + d * t          numpy's `linear` method, its lerp included
+ *     if clip is NaN: clip = the quiet NaN 0xFFF8000000000000  (only inf - inf makes one here; x86-64's bits for it)
+ *     if s[m - 1] is NaN: clip = s[m - 1]                       np.percentile with a NaN anywhere returns that entry
+ *     q = clip / (x + 1e-6);  scale = (q < 1.0) ? q : 1.0       Python's min(1.0, q): a NaN quotient gives 1.0
+ *   out (DCL_AUTOCLIP_OUT_BYTES, 8-byte aligned): doubles {x, clip, scale} at bytes 0, 8, 16 and (float)scale, rounded once,
+ *     at byte DCL_AUTOCLIP_SCALE_F32_OFFSET -- the pointer dcl_adam_step_dev takes.  scale is always in [0, 1].
+ * Stream-ordered, plain 8-byte loads and stores (16 n bytes of traffic), no atomics, no workgroup waits on another, the result
+ * does not depend on the grid, nothing is read back or allocated.  n < 0, n > DCL_AUTOCLIP_MAX_N, a percentile outside
+ * [0, 100] (NaN included), a NULL pointer (sorted_src may be NULL with n == 0) and sorted_src == sorted_dst return DCL_EINVAL
+ * before any work.
+ * dcl_autoclip_observe_host: the same contract in plain C++ on HOST pointers (csrc/optim_clip_host.cpp; no GPU call).      */
+#define DCL_AUTOCLIP_OUT_BYTES 32
+#define DCL_AUTOCLIP_SCALE_F32_OFFSET 24
+#define DCL_AUTOCLIP_MAX_N ((int64_t)1 << 31)
+int dcl_autoclip_observe(int64_t n, const double *sorted_src, double *sorted_dst, double *arrival, const double *norm,
+                         double percentile, void *out, dclStream_t stream);
+int dcl_autoclip_observe_host(int64_t n, const double *sorted_src, double *sorted_dst, double *arrival, const double *norm,
+                              double percentile, void *out);
 
 /* The loaders' point-sampling draws, bit for bit (host code, no GPU call): for each of k objects out[o*n .. o*n+n) =
  * np.random.permutation(m[o])[:n] = what np.random.choice(m[o], n, replace=False) returns (YCBV/dataloader_test_YCBV.py:166-169,

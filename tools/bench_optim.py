@@ -7,13 +7,20 @@ and on the refiner's 18, with synthetic gradients:
   item+fused    the same with torch.optim.Adam(fused=True)
   dcl           dcl.optim.AutoClip(50, optimizer=opt) + dcl.optim.Adam.step(): one norm pass, one read-back, one update launch
 
-  python tools/bench_optim.py [--iters 50] [--warmup 5]
+  python tools/bench_optim.py [--iters 50] [--warmup 5] [--part all|forms|history]
 
 Per model: median ms of one device-synchronised tail (host clock), in blocks that rotate the three forms inside one process,
 every form on its own copy of the parameters with the same gradients.  Then the two library calls alone (device events)
 against the bytes they must move (4 B per element the norm, 28 B the update) as a fraction of the 6.3 TB/s copy rate; the
 update's 235 MB of Network fit the 256 MiB Infinity Cache, so that fraction is of a rate, not proof of HBM traffic.
-profiles/optim.txt holds one run's output."""
+profiles/optim.txt holds one run's output.
+
+--part history: the dcl tail again on Network's tensors with a norm history ALREADY HELD, as late in a run (the reference's
+schedule ends at 631 050 steps): dcl.optim.AutoClip (np.percentile over a Python list, one read-back) against
+dcl.optim.DeviceAutoClip (the sorted history and the percentile on the GPU, no read-back), histories of HISTORY_LENGTHS entries
+preloaded through load_state_dict and loaded again in front of every block, the two forms alternating block by block, a
+block at least BLOCK_SECONDS of single synchronised tails; then the two observe launches alone (device events) against
+the 16 n bytes they move.  profiles/autoclip_device.txt holds one run's output."""
 import argparse
 import importlib
 import os
@@ -31,6 +38,8 @@ import torch  # noqa: E402
 COPY_RATE = 6.3e12            # bytes/s: the measured device-to-device copy rate the byte counts are held against
 SHIPPED = dict(lr=1e-3, betas=(0.5, 0.999), eps=1e-6)
 REPS = 20                     # library calls per timed window
+HISTORY_LENGTHS = (0, 10000, 100000, 631050)      # 631 050 = 210 epochs x 3005 iterations, the reference's schedule
+BLOCK_SECONDS = 0.3
 
 
 class ItemAutoClip(object):
@@ -162,18 +171,96 @@ def bench(dcl, name, model, iters, warmup):
     return mid
 
 
+def bench_history(dcl, model, warmup, rounds=3):
+    """the dcl tail with a history already held: AutoClip ("host") against DeviceAutoClip ("device"), see the module docstring"""
+    setups = {}
+    for tag in ("host", "device"):
+        m = _Params(model)
+        opt = dcl.optim.Adam(m.parameters(), **SHIPPED)
+        clip = (dcl.optim.DeviceAutoClip if tag == "device" else dcl.optim.AutoClip)(50, optimizer=opt)
+        setups[tag] = (m, opt, clip)
+    print("\nNetwork with a held history: %d parameter tensors; dcl.optim.AutoClip (host) vs dcl.optim.DeviceAutoClip (device)"
+          % len(setups["host"][0].ps))
+    print("  per block: the history is loaded again, then single synchronised tails for >= %.1f s; median ms of one tail"
+          % BLOCK_SECONDS)
+    rng = np.random.default_rng(0)
+
+    def block(tag, sd):
+        m, opt, clip = setups[tag]
+        clip.load_state_dict(sd)
+        ts, t_end = [], time.perf_counter() + BLOCK_SECONDS
+        while len(ts) < 20 or (time.perf_counter() < t_end and len(ts) < 2000):
+            m.fill()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            clip(m)
+            opt.step()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        ts.sort()
+        return ts[len(ts) // 2], len(ts)
+    table = []
+    for n in HISTORY_LENGTHS:
+        sd = {"percentile": 50, "history": rng.lognormal(0.0, 1.0, n).tolist()}
+        for tag in setups:                                            # warm-up at this length: growth, the staging ring
+            m, opt, clip = setups[tag]
+            clip.load_state_dict(sd)
+            for _ in range(warmup):
+                m.fill()
+                clip(m)
+                opt.step()
+        torch.cuda.synchronize()
+        blocks = []
+        for r in range(rounds):
+            for tag in (("host", "device") if r % 2 == 0 else ("device", "host")):
+                blocks.append((tag,) + block(tag, sd))
+        print("  history %7d, blocks in run order: %s" % (n, ", ".join("%s %.3f (%d tails)" % bl for bl in blocks)))
+        row = {}
+        for tag in setups:
+            v = sorted(t for k, t, _ in blocks if k == tag)
+            row[tag] = (v[len(v) // 2], v[0], v[-1])
+            print("    %-6s %8.3f ms  (blocks %.3f .. %.3f)" % ((tag,) + row[tag]))
+        h, d = row["host"], row["device"]
+        verdict = "device faster, block ranges disjoint" if d[2] < h[1] else \
+                  "host faster, block ranges disjoint" if h[2] < d[1] else "block ranges overlap: a tie"
+        print("    host / device = %.2f  (%s)" % (h[0] / d[0], verdict))
+        table.append((n, row))
+    # the two observe launches alone, at a fixed n (the same source and destination every call)
+    dev = torch.device("cuda")
+    ops = dcl.ops
+    for n in HISTORY_LENGTHS:
+        src = torch.from_numpy(np.sort(rng.lognormal(0.0, 1.0, n))).to(dev)
+        dst, arrival = (torch.empty(n + 1, dtype=torch.float64, device=dev) for _ in range(2))
+        norm = torch.ones(1, dtype=torch.float64, device=dev)
+        out = torch.zeros(ops.AUTOCLIP_OUT_DOUBLES, dtype=torch.float64, device=dev)
+
+        def calls():
+            for _ in range(REPS):
+                ops.autoclip_observe(n, src, dst, arrival, norm, 50, out)
+        t = events_ms(calls, 30, warmup) / REPS
+        nbytes = 16 * n
+        print("  dcl_autoclip_observe (both launches), n = %7d: %.4f ms for %.3f MB: %.3f TB/s, %.1f %% of the 6.3 TB/s copy rate"
+              % (n, t, nbytes / 1e6, nbytes / (t * 1e-3) / 1e12, 100 * nbytes / (t * 1e-3) / COPY_RATE))
+    return table
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--part", choices=("all", "forms", "history"), default="all")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_optim: needs the GPU (no CPU timing is meaningful)")
     dcl = importlib.import_module("dcl-net_amd")
     print("AutoClip + Adam after loss.backward(): the reference's form (per-tensor .item()) vs dcl.optim (csrc/optim.hip)")
     net = dcl.DCL_Net.Network(dcl.synth.default_cfg(1024, 1024), mode="train").cuda()
-    mids = [bench(dcl, "Network", net, args.iters, args.warmup)]
-    mids.append(bench(dcl, "Refiner", dcl.refiner.Refiner().cuda(), args.iters, args.warmup))
+    mids = []
+    if args.part in ("all", "forms"):
+        mids.append(bench(dcl, "Network", net, args.iters, args.warmup))
+        mids.append(bench(dcl, "Refiner", dcl.refiner.Refiner().cuda(), args.iters, args.warmup))
+    if args.part in ("all", "history"):
+        bench_history(dcl, net, args.warmup)
     for mid in mids:
         if mid["dcl"] > min(mid["item+default"], mid["item+fused"]):
             raise SystemExit("bench_optim: dcl.optim is SLOWER than the reference's form: a defect, not a result")

@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """Training-step timing (forward in train mode + loss + backward + Adam) on synthetic crops:
-tools/train_step.py [b] [N] [--optim torch|fused] [--autoclip] [--chamfer chunked|fused] [--objective module|fused]
+tools/train_step.py [b] [N] [--optim torch|fused] [--autoclip [host|device]] [--chamfer chunked|fused] [--objective module|fused]
 [--conv-wgrad rows|pairs] [--conv-dgrad conv|direct] [--pool modules|fused] [--norm modules|fused]
 [--attention materialised|fused] [--dense modules|point_major] [--heads modules|kernels] [--conv-fwd tiles|compact] [--conv-fwd-all]
 [--rotation host|device] [--kernels]
 --kernels: the all-kernels configuration in one flag -- Network(**DCL_Net.TRAIN_KERNELS) with --chamfer fused --objective fused
---optim fused --autoclip; it overrides the single switches.  --rotation: Network(train_rotation=).
+--optim fused --autoclip (the host form, unless --autoclip device is given); it overrides the single switches.  --rotation: Network(train_rotation=).
 --optim fused: dcl.optim.Adam (csrc/optim.hip) instead of torch.optim.Adam; --autoclip: AutoClip(50) in front of the step, as
-the reference's training scripts run it -- the per-tensor .item() form with --optim torch, dcl.optim.AutoClip with fused.
+the reference's training scripts run it -- the per-tensor .item() form with --optim torch, dcl.optim.AutoClip with fused;
+--autoclip device (needs --optim fused, or --kernels): dcl.optim.DeviceAutoClip, the history and the percentile on the GPU.
 --chamfer / --objective: the loss module's switches (models/losses.py); --objective fused evaluates the objective on
 csrc/objective.hip and logs all five loss values with one read-back of crit.packed.  --conv-wgrad: the form of the sparse
 convolutions' weight gradient, Network(train_conv_wgrad=); --conv-dgrad: the form of their input gradient,
@@ -27,7 +28,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("b", type=int, nargs="?", default=8)
 ap.add_argument("n", type=int, nargs="?", default=1024)
 ap.add_argument("--optim", choices=("torch", "fused"), default="torch")
-ap.add_argument("--autoclip", action="store_true")
+ap.add_argument("--autoclip", nargs="?", const="host", default=None, choices=("host", "device"))
 ap.add_argument("--chamfer", choices=("chunked", "fused"), default="chunked")
 ap.add_argument("--objective", choices=("module", "fused"), default="module")
 ap.add_argument("--conv-wgrad", choices=("rows", "pairs"), default="rows")
@@ -48,7 +49,9 @@ switches = dict(train_conv_wgrad=args.conv_wgrad, train_conv_dgrad=args.conv_dgr
                 train_rotation=args.rotation)
 if args.kernels:
     switches = dict(dcl.DCL_Net.TRAIN_KERNELS)
-    args.chamfer, args.objective, args.optim, args.autoclip = "fused", "fused", "fused", True
+    args.chamfer, args.objective, args.optim, args.autoclip = "fused", "fused", "fused", args.autoclip or "host"
+if args.autoclip == "device" and args.optim != "fused":
+    ap.error("--autoclip device needs --optim fused (or --kernels)")
 if args.conv_fwd_all:
     dcl.ops.CONV_FWD_COMPACT_WIDTHS = frozenset(((32, 32), (64, 64), (128, 128)))
 net = dcl.DCL_Net.Network(dcl.synth.default_cfg(n, n), mode="train", **switches)
@@ -59,7 +62,7 @@ clip = None
 if args.optim == "fused":
     opt = dcl.optim.Adam(net.parameters(), lr=1e-4)
     if args.autoclip:
-        clip = dcl.optim.AutoClip(50, optimizer=opt)
+        clip = (dcl.optim.DeviceAutoClip if args.autoclip == "device" else dcl.optim.AutoClip)(50, optimizer=opt)
 else:
     opt = torch.optim.Adam(net.parameters(), lr=1e-4)
     if args.autoclip:
@@ -79,6 +82,6 @@ for _ in range(3): step()
 torch.cuda.synchronize(); t0 = time.perf_counter()
 for _ in range(10): l = step()
 torch.cuda.synchronize()
-print("train step b=%d N=M=%d (optim %s%s, chamfer %s, objective %s, conv fwd %s%s, wgrad %s, dgrad %s, pool %s, norm %s, attention %s, dense %s, heads %s): %.1f ms (loss %.4f), peak mem %.2f GB" % (b, n, args.optim, " + autoclip" if clip is not None else "", args.chamfer, args.objective, switches["train_conv_fwd"], " on %s" % sorted(dcl.ops.CONV_FWD_COMPACT_WIDTHS) if switches["train_conv_fwd"] == "compact" else "", switches["train_conv_wgrad"], switches["train_conv_dgrad"], switches["train_pool"], switches["train_norm"], switches["train_attention"], switches["train_dense"], switches["train_heads"], (time.perf_counter() - t0) / 10 * 1e3, float(l.detach()), torch.cuda.max_memory_allocated() / 1e9))
+print("train step b=%d N=M=%d (optim %s%s, chamfer %s, objective %s, conv fwd %s%s, wgrad %s, dgrad %s, pool %s, norm %s, attention %s, dense %s, heads %s): %.1f ms (loss %.4f), peak mem %.2f GB" % (b, n, args.optim, " + autoclip (%s)" % args.autoclip if clip is not None else "", args.chamfer, args.objective, switches["train_conv_fwd"], " on %s" % sorted(dcl.ops.CONV_FWD_COMPACT_WIDTHS) if switches["train_conv_fwd"] == "compact" else "", switches["train_conv_wgrad"], switches["train_conv_dgrad"], switches["train_pool"], switches["train_norm"], switches["train_attention"], switches["train_dense"], switches["train_heads"], (time.perf_counter() - t0) / 10 * 1e3, float(l.detach()), torch.cuda.max_memory_allocated() / 1e9))
 if args.objective == "fused":
     print("  [loss_pose, loss_Xo, loss_Yc, loss_conf, loss_all] from one read-back: %s" % (["%.5f" % v for v in crit.packed.tolist()],))
