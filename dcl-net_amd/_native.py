@@ -1,10 +1,15 @@
 """ctypes loader of libdclnet_hip.so (the C ABI declared in include/dclnet_hip.h).
 
+The header is the ONE source of the call signatures and of the constants this package shares with the library: it is parsed
+once per process, and every declared entry point a library exports gets its argtypes / restype from its prototype, so the call
+sites pass plain Python ints and floats.  The header therefore travels with the package.
+
 The product path has NO CPU fallback: if the library is missing or a call fails, a RuntimeError
 is raised.  PyTorch is used for device memory and streams only.
 """
 import ctypes as C
 import os
+import re
 import subprocess
 
 import torch
@@ -12,6 +17,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "libdclnet_hip.so")
 DIAG_SO_PATH = os.path.join(os.path.dirname(_HERE), "tools", "_bin", "libdclnet_hip_diag.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "dclnet_hip.h")
 _LIB = None
 
 vp = C.c_void_p
@@ -25,76 +31,100 @@ def build(verbose=False, diag=False):
     return SO_PATH
 
 
-ABI_VERSION = 2                 # include/dclnet_hip.h: DCL_ABI_VERSION this package's ctypes calls are written against
+# ---- include/dclnet_hip.h -> signatures and constants.  The header's whole vocabulary; anything else is an error, never a guess.
+_BY_VALUE = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "long long": C.c_longlong, "uint64_t": C.c_uint64,
+             "unsigned long long": C.c_ulonglong, "float": C.c_float, "double": C.c_double, "dclStream_t": vp}
+_RETURNS = {"int": C.c_int, "void": None, "int64_t": C.c_int64, "long long": C.c_longlong,
+            "unsigned long long": C.c_ulonglong, "const char *": C.c_char_p}
+_PROTOTYPE = re.compile(r"(.*?)\b(\w+)\s*\((.*)\)", re.S)
+_DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(DCL_\w+)[ \t]+(.*?)[ \t]*$", re.M)
+_INT_LITERAL = re.compile(r"(-?(?:0[xX][0-9a-fA-F]+|\d+))|\(\s*(-?(?:0[xX][0-9a-fA-F]+|\d+))\s*\)")
+
+
+def _blank(m):
+    return " " + "\n" * m.group(0).count("\n")              # (line numbers survive)
+
+
+def _parameter(text, line):
+    if "*" in text or "[" in text:
+        return vp
+    words = [w for w in text.split() if w != "const"]
+    for typ in (" ".join(words), " ".join(words[:-1])):     # unnamed, or followed by the parameter's name
+        if typ in _BY_VALUE:
+            return _BY_VALUE[typ]
+    raise RuntimeError("include/dclnet_hip.h line %d: no ctypes type for the parameter `%s` (by-value types: %s)"
+                       % (line, text, ", ".join(sorted(_BY_VALUE))))
+
+
+def parse_header(text):
+    """-> (signatures {name: (restype, [argtypes])}, constants {DCL_X: int, or the text of a non-literal #define})"""
+    text = re.sub(r"/\*.*?\*/", _blank, text, flags=re.S)
+    constants = {}
+    for name, value in _DEFINE.findall(text):
+        m = _INT_LITERAL.fullmatch(value)
+        constants[name] = int(m.group(1) or m.group(2), 0) if m else value
+    text = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*", _blank, text, flags=re.M)
+    text = re.sub(r"\btypedef\b[^;{]*(?:\{[^}]*\}[^;]*)?;", _blank, text)
+    text = re.sub(r'extern\s+"C"\s*\{', _blank, text)
+    signatures, pos = {}, 0
+    for stmt in text.split(";"):
+        line = text.count("\n", 0, pos + len(stmt) - len(stmt.lstrip())) + 1
+        pos += len(stmt) + 1
+        stmt = " ".join(stmt.split())
+        if stmt in ("", "}"):
+            continue
+        m = _PROTOTYPE.fullmatch(stmt)
+        if not m:
+            raise RuntimeError("include/dclnet_hip.h line %d: not a prototype this loader can read: `%s`" % (line, stmt))
+        ret, name, params = m.group(1).strip(), m.group(2), m.group(3).strip()
+        if ret not in _RETURNS:
+            raise RuntimeError("include/dclnet_hip.h line %d: no ctypes type for the return type `%s` of %s" % (line, ret, name))
+        args = [] if params in ("", "void") else [_parameter(p.strip(), line) for p in params.split(",")]
+        signatures[name] = (_RETURNS[ret], args)
+    return signatures, constants
+
+
+_HEADER = None
+
+
+def _header():
+    global _HEADER
+    if _HEADER is None:
+        if not os.path.exists(HEADER_PATH):
+            raise RuntimeError("include/dclnet_hip.h is missing (%s): the header travels with the package -- every ctypes "
+                               "signature and shared constant is read from it.  There is no fallback table." % HEADER_PATH)
+        with open(HEADER_PATH) as f:
+            _HEADER = parse_header(f.read())
+    return _HEADER
+
+
+def signatures():
+    """{entry point: (restype, [argtypes])} of every prototype include/dclnet_hip.h declares (the DCL_DIAG block included)"""
+    return _header()[0]
+
+
+def define(name):
+    """the value of `#define DCL_...` in include/dclnet_hip.h; integer literals only -- anything else raises"""
+    value = _header()[1].get(name)
+    if not isinstance(value, int):
+        raise RuntimeError("include/dclnet_hip.h: %s is %s" % (
+            name, "not defined" if value is None else "`%s`, not an integer literal" % value))
+    return value
+
+
+ABI_VERSION = define("DCL_ABI_VERSION")     # the header this package's calls are written against
 
 
 def _open(path):
     L = C.CDLL(path)
-    L.dcl_last_error.restype = C.c_char_p
+    for name, (restype, argtypes) in signatures().items():
+        fn = getattr(L, name, None)         # (the product library lacks the `#ifdef DCL_DIAG` block)
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
     got = int(L.dcl_abi_version())
     if got != ABI_VERSION:
         raise RuntimeError("%s speaks C-ABI version %d, this package calls version %d (include/dclnet_hip.h): rebuild the "
                            "library (make -C dcl-net_amd/csrc)" % (path, got, ABI_VERSION))
-    # csrc/linear_bwd.hip: int64 pitches between int sizes -- declared, so that a plain Python int converts correctly
-    i, i64 = C.c_int, C.c_int64
-    L.dcl_linear_wgrad_splits.argtypes = [i, C.POINTER(C.c_int32)]
-    L.dcl_linear_wgrad.argtypes = [vp, i64, vp, i64, i, i, i, vp, vp, i64, vp]
-    L.dcl_relu_bwd.argtypes = [vp, i64, vp, i64, vp, vp, i64, i, i, i, vp, i64, vp, vp, vp]
-    # csrc/conv_dgrad.hip
-    L.dcl_sparse_conv_dgrad.argtypes = [vp, i, vp, i, i, vp, i, i, i, vp, vp]
-    L.dcl_sparse_conv_dgrad_host.argtypes = [vp, i, vp, i, i, vp, i, i, i, vp]
-    # csrc/conv_fwd_compact.hip
-    L.dcl_sparse_conv_fwd_compact.argtypes = [vp, i, vp, i, i, vp, i, i, i, i, vp, vp]
-    L.dcl_sparse_conv_fwd_compact_host.argtypes = [vp, i, vp, i, i, vp, i, i, i, i, vp]
-    # csrc/conf_pool_grad.hip: an int64 scratch size among the pointers
-    L.dcl_conf_pool_cm_fwd.argtypes = [i] * 4 + [vp] * 5
-    L.dcl_conf_pool_cm_fwd_host.argtypes = [i] * 4 + [vp] * 4
-    L.dcl_conf_pool_cm_bwd_ws_bytes.argtypes = [i] * 4 + [C.POINTER(C.c_int64)]
-    L.dcl_conf_pool_cm_bwd.argtypes = [i] * 4 + [vp] * 11 + [i64, vp]
-    L.dcl_conf_pool_cm_bwd_host.argtypes = [i] * 4 + [vp] * 10
-    # csrc/conf_pool_pm.hip: the channel-major set's argument lists
-    L.dcl_conf_pool_pm_fwd.argtypes = [i] * 4 + [vp] * 5
-    L.dcl_conf_pool_pm_fwd_host.argtypes = [i] * 4 + [vp] * 4
-    L.dcl_conf_pool_pm_bwd_ws_bytes.argtypes = [i] * 4 + [C.POINTER(C.c_int64)]
-    L.dcl_conf_pool_pm_bwd.argtypes = [i] * 4 + [vp] * 11 + [i64, vp]
-    L.dcl_conf_pool_pm_bwd_host.argtypes = [i] * 4 + [vp] * 10
-    # csrc/bn_relu.hip: int64 row counts, and eps / momentum as C floats
-    f = C.c_float
-    L.dcl_bn_relu_ws_bytes.argtypes = [i64, i, C.POINTER(C.c_int64)]
-    L.dcl_bn_relu_fwd.argtypes = [i64, i] + [vp] * 3 + [f, f] + [vp] * 5 + [i, vp, i64, vp]
-    L.dcl_bn_relu_fwd_host.argtypes = [i64, i] + [vp] * 3 + [f, f] + [vp] * 5 + [i]
-    L.dcl_bn_relu_bwd.argtypes = [i64, i] + [vp] * 6 + [i] + [vp] * 3 + [vp, i64, vp]
-    L.dcl_bn_relu_bwd_host.argtypes = [i64, i] + [vp] * 6 + [i] + [vp] * 3
-    # csrc/linear_narrow.hip: an int64 row count and row pitch
-    L.dcl_linear_narrow_fwd.argtypes = [i64, i, i, vp, i64] + [vp] * 4
-    L.dcl_linear_narrow_fwd_host.argtypes = [i64, i, i, vp, i64] + [vp] * 3
-    L.dcl_linear_narrow_bwd_ws_bytes.argtypes = [i64, i, i, C.POINTER(C.c_int64)]
-    L.dcl_linear_narrow_bwd.argtypes = [i64, i, i, vp, i64] + [vp] * 6 + [i64, vp]
-    L.dcl_linear_narrow_bwd_host.argtypes = [i64, i, i, vp, i64] + [vp] * 5
-    # csrc/pose_heads_grad.hip
-    L.dcl_pose_heads_train_fwd.argtypes = [i] * 6 + [vp] * 18
-    L.dcl_pose_heads_train_fwd_host.argtypes = [i] * 6 + [vp] * 17
-    L.dcl_pose_heads_train_bwd_ws_bytes.argtypes = [i] * 6 + [C.POINTER(C.c_int64)]
-    L.dcl_pose_heads_train_bwd.argtypes = [i] * 6 + [vp] * 25 + [i64, vp]
-    L.dcl_pose_heads_train_bwd_host.argtypes = [i] * 6 + [vp] * 24
-    # csrc/template_rows.hip: an int64 class pitch
-    L.dcl_template_rows.argtypes = [vp, i64, i, i, vp, i, vp, i, vp, i, vp, vp]
-    L.dcl_template_rows_host.argtypes = [vp, i64, i, i, vp, i, vp, i, vp, i, vp]
-    L.dcl_template_rows.restype = L.dcl_template_rows_host.restype = i
-    # csrc/optim.hip, csrc/optim_clip_host.cpp: an int64 count and a double percentile among the pointers
-    L.dcl_autoclip_observe.argtypes = [i64] + [vp] * 4 + [C.c_double, vp, vp]
-    L.dcl_autoclip_observe_host.argtypes = [i64] + [vp] * 4 + [C.c_double, vp]
-    L.dcl_autoclip_observe.restype = L.dcl_autoclip_observe_host.restype = i
-    for fn in (L.dcl_linear_narrow_fwd, L.dcl_linear_narrow_fwd_host, L.dcl_linear_narrow_bwd_ws_bytes, L.dcl_linear_narrow_bwd,
-               L.dcl_linear_narrow_bwd_host, L.dcl_pose_heads_train_fwd, L.dcl_pose_heads_train_fwd_host,
-               L.dcl_pose_heads_train_bwd_ws_bytes, L.dcl_pose_heads_train_bwd, L.dcl_pose_heads_train_bwd_host):
-        fn.restype = i
-    for fn in (L.dcl_linear_wgrad_splits, L.dcl_linear_wgrad, L.dcl_relu_bwd, L.dcl_sparse_conv_dgrad,
-               L.dcl_sparse_conv_dgrad_host, L.dcl_sparse_conv_fwd_compact, L.dcl_sparse_conv_fwd_compact_host, L.dcl_conf_pool_cm_fwd, L.dcl_conf_pool_cm_fwd_host,
-               L.dcl_conf_pool_cm_bwd_ws_bytes, L.dcl_conf_pool_cm_bwd, L.dcl_conf_pool_cm_bwd_host,
-               L.dcl_conf_pool_pm_fwd, L.dcl_conf_pool_pm_fwd_host, L.dcl_conf_pool_pm_bwd_ws_bytes, L.dcl_conf_pool_pm_bwd,
-               L.dcl_conf_pool_pm_bwd_host, L.dcl_bn_relu_ws_bytes, L.dcl_bn_relu_fwd, L.dcl_bn_relu_fwd_host, L.dcl_bn_relu_bwd, L.dcl_bn_relu_bwd_host):
-        fn.restype = i
     return L
 
 
@@ -135,6 +165,22 @@ class diagnostic_library(object):
 def check(rc, what=""):
     if rc != 0:
         raise RuntimeError("libdclnet_hip %s failed (rc=%d): %s" % (what, rc, lib().dcl_last_error().decode()))
+
+
+def query(sym, *args, what=None, ctype=C.c_int64):
+    """the integer `sym` writes through its LAST parameter, an `int64_t *` -- the *_ws_bytes family.  ctype: another integer
+    type, or a tuple of them for several trailing out-parameters (-> a tuple).  what: the label of a failure (default: the
+    symbol without its dcl_ prefix)."""
+    outs = [t(0) for t in (ctype if isinstance(ctype, tuple) else (ctype,))]
+    check(getattr(lib(), sym)(*args, *[C.byref(o) for o in outs]), sym[4:] if what is None else what)
+    return tuple(int(o.value) for o in outs) if isinstance(ctype, tuple) else int(outs[0].value)
+
+
+def twin(sym, host, what, *args):
+    """a kernel or its host twin on one argument list: <sym>_host(*args), or <sym>(*args, stream) on torch's current stream
+    (a device form's workspace arguments are the caller's to append)"""
+    L = lib()
+    check(getattr(L, sym + "_host")(*args) if host else getattr(L, sym)(*args, stream()), what)
 
 
 def stream():

@@ -3,6 +3,10 @@
 Every function takes/returns CUDA tensors (PyTorch is the allocator and stream provider), checks
 arguments the way the reference's Python wrappers do (contiguity, dtypes) and calls the HIP
 library on torch's current stream.  No function here has a CPU fallback.
+
+One calling convention: scalars go in as plain Python ints / floats (_native declares every entry point's signature from the
+header, so nothing is wrapped by hand here), pointers as N.ptr(tensor) / ctypes arrays / None; a size asked through an
+out-parameter is N.query(...), and a kernel with a host twin is N.twin(...) on one argument list.
 """
 import ctypes as C
 import threading
@@ -12,9 +16,6 @@ import weakref
 import torch
 
 from . import _native as N
-
-_c_int = C.c_int
-_c_float = C.c_float
 
 # bench.py sets this to a list to collect (name, start_event, end_event) around selected launches on torch's
 # current stream (the stream the kernels are launched on); None = off.
@@ -34,12 +35,11 @@ def voxelize_idx(coords, batch_size, mode=4):
     assert coords.is_contiguous() and coords.dtype == torch.int64 and coords.dim() == 2
     n, ncol = coords.shape
     input_map = torch.zeros(n, dtype=torch.int32)
-    na, ma = C.c_int32(0), C.c_int32(0)
-    N.check(N.lib().dcl_voxelize_idx_count(N.ptr(coords), n, ncol, int(batch_size), int(mode), N.ptr(input_map),
-                                           C.byref(na), C.byref(ma)), "voxelize_idx_count")
-    out_coords = torch.zeros((na.value, ncol), dtype=torch.int64)
-    out_map = torch.zeros((na.value, ma.value + 1), dtype=torch.int32)
-    N.check(N.lib().dcl_voxelize_idx_fill_mode(N.ptr(coords), n, ncol, N.ptr(input_map), na.value, ma.value, int(mode),
+    na, ma = N.query("dcl_voxelize_idx_count", N.ptr(coords), n, ncol, int(batch_size), int(mode), N.ptr(input_map),
+                     ctype=(C.c_int32, C.c_int32))
+    out_coords = torch.zeros((na, ncol), dtype=torch.int64)
+    out_map = torch.zeros((na, ma + 1), dtype=torch.int32)
+    N.check(N.lib().dcl_voxelize_idx_fill_mode(N.ptr(coords), n, ncol, N.ptr(input_map), na, ma, int(mode),
                                                N.ptr(out_coords), N.ptr(out_map)), "voxelize_idx_fill")
     return out_coords, input_map, out_map
 
@@ -50,12 +50,11 @@ def voxelize_idx_gpu(coords, batch_size, S=64, mode=4):
     N.need_cuda(coords)
     assert coords.is_contiguous() and coords.dtype == torch.int64 and coords.shape[1] == 4
     n, dev = coords.shape[0], coords.device
-    nbytes = C.c_int64(0)
-    N.check(N.lib().dcl_voxelize_idx_gpu_ws_bytes(n, int(batch_size), int(S), C.byref(nbytes)), "voxelize_idx_gpu_ws_bytes")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    nbytes = N.query("dcl_voxelize_idx_gpu_ws_bytes", n, int(batch_size), int(S))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     input_map = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
     info = torch.empty(3, dtype=torch.int32, device=dev)
-    N.check(N.lib().dcl_voxelize_idx_gpu_count(N.ptr(coords), n, int(batch_size), int(S), int(mode), N.ptr(ws), nbytes.value,
+    N.check(N.lib().dcl_voxelize_idx_gpu_count(N.ptr(coords), n, int(batch_size), int(S), int(mode), N.ptr(ws), nbytes,
                                                N.ptr(input_map), N.ptr(info), N.stream()), "voxelize_idx_gpu_count")
     V, ma, err = info.cpu().tolist()
     if err:
@@ -155,7 +154,7 @@ def pad_copy_many(jobs):
 
 
 # ------------------------------------------------------------------------------------ per-class template cache
-TEMPLATE_MAX_BLOCKS = 8         # include/dclnet_hip.h: DCL_TEMPLATE_MAX_BLOCKS
+TEMPLATE_MAX_BLOCKS = N.define("DCL_TEMPLATE_MAX_BLOCKS")
 
 
 class _TemplateBlock(C.Structure):
@@ -202,11 +201,8 @@ def _template_rows(cache, lut, cls, blocks, miss, host):
         q = arr[j]
         q.src_col, q.width, q.dst = int(src_col), width, dst.data_ptr()
         q.dst_pitch = int(dst.stride(0)) if dst.shape[0] > 1 else width
-    a = (N.ptr(cache), class_floats, row_floats, n_tmp, N.ptr(lut), int(lut.numel()), N.ptr(cls), b, arr, len(blocks), N.ptr(miss))
-    if host:
-        N.check(N.lib().dcl_template_rows_host(*a), what)
-    else:
-        N.check(N.lib().dcl_template_rows(*(a + (N.stream(),))), what)
+    N.twin("dcl_template_rows", host, what, N.ptr(cache), class_floats, row_floats, n_tmp, N.ptr(lut), int(lut.numel()), N.ptr(cls),
+           b, arr, len(blocks), N.ptr(miss))
     return miss
 
 
@@ -370,14 +366,13 @@ def order_rows(out_set, in_mask, subm):
     n, dev = int(out_set.n), out_set.indices.device
     cap = max(n, 1)
     tiles = (cap + 127) // 128
-    nbytes = C.c_int64(0)
-    N.check(N.lib().dcl_order_rows_ws_bytes(cap, C.byref(nbytes)), "order_rows_ws_bytes")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    nbytes = N.query("dcl_order_rows_ws_bytes", cap)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     order = torch.empty(cap, dtype=torch.int32, device=dev)
     bal = torch.zeros(tiles + 2, dtype=torch.int32, device=dev)
     smask = torch.zeros(tiles + 1, dtype=torch.int32, device=dev)
     N.check(N.lib().dcl_order_rows(N.ptr(out_set.indices), N.vp(0), n, cap, N.ptr(in_mask), int(out_set.S), int(bool(subm)),
-                                   N.ptr(ws), nbytes.value, N.ptr(order), N.ptr(bal), N.ptr(smask), N.stream()), "order_rows")
+                                   N.ptr(ws), nbytes, N.ptr(order), N.ptr(bal), N.ptr(smask), N.stream()), "order_rows")
     nt = (n + 127) // 128
     return order[:n], bal[:nt + 1], smask[:nt]
 
@@ -402,20 +397,18 @@ def sparse_conv(feat, nbr, n_out, W, subm, scale=None, shift=None, relu=False, o
     # stream-K scratch (partial-tile slots + tile tickets, csrc/sparse_conv.hip::launch_conv_dma)
     scratch = None
     if cout % 32 == 0:
-        need = C.c_int64(0)
-        N.check(N.lib().dcl_sparse_conv_scratch_floats(int(cap), int(cout), C.byref(need)), "sparse_conv_scratch_floats")
-        scratch = torch.empty(need.value, dtype=torch.float32, device=feat.device)
+        scratch = torch.empty(N.query("dcl_sparse_conv_scratch_floats", int(cap), int(cout)), dtype=torch.float32, device=feat.device)
     if order is not None:
         o, bal, smask = order
         assert o.numel() >= n_out and o.dtype == torch.int32 and o.is_cuda
         N.check(N.lib().dcl_sparse_conv_fwd_ordered(N.ptr(feat), N.ptr(nbr), cap, N.vp(0), int(n_out), N.ptr(W), cin, cout, kvol,
                                                     int(bool(subm)), N.ptr(scale), N.ptr(shift), int(bool(relu)), N.ptr(out),
-                                                    N.ptr(scratch), C.c_int64(0 if scratch is None else scratch.numel()),
+                                                    N.ptr(scratch), 0 if scratch is None else scratch.numel(),
                                                     N.ptr(o), N.ptr(bal), N.ptr(smask), N.stream()), "sparse_conv_fwd_ordered")
         return out
     N.check(N.lib().dcl_sparse_conv_fwd_ws(N.ptr(feat), N.ptr(nbr), cap, N.vp(0), int(n_out), N.ptr(W), cin, cout, kvol,
                                            int(bool(subm)), N.ptr(scale), N.ptr(shift), int(bool(relu)), N.ptr(out),
-                                           N.ptr(scratch), C.c_int64(0 if scratch is None else scratch.numel()),
+                                           N.ptr(scratch), 0 if scratch is None else scratch.numel(),
                                            N.stream()), "sparse_conv_fwd")
     return out
 
@@ -467,7 +460,6 @@ def conv_split_weight(W):
     kvol, cin, cout = W.shape
     assert W.is_contiguous() and W.dtype == torch.float32 and conv_split_ok(kvol, cin, cout)
     lib = N.lib()
-    lib.dcl_conv_split_weight_bytes.restype = C.c_int64
     nbytes = int(lib.dcl_conv_split_weight_bytes(int(kvol), int(cin), int(cout)))
     planes = torch.empty(nbytes, dtype=torch.uint8, device=W.device)
     N.check(lib.dcl_conv_split_weight(N.ptr(W), int(kvol), int(cin), int(cout), N.ptr(planes), N.stream()), "conv_split_weight")
@@ -518,14 +510,13 @@ def sparse_conv_sides(feats, nbrs, n_outs, Ws, subm, pieces=None, scales=None, s
     kvol, cin, cout = Ws[0].shape
     outs = [torch.empty((int(n), cout), dtype=torch.float32, device=feats[0].device) for n in n_outs]
     cap_sum = sum(int(nb.shape[1]) for nb in nbrs)
-    need = C.c_int64(0)
-    N.check(N.lib().dcl_sparse_conv_scratch_floats(int(cap_sum), int(cout), C.byref(need)), "sparse_conv_scratch_floats")
-    scratch = torch.empty(need.value, dtype=torch.float32, device=feats[0].device)
+    scratch = torch.empty(N.query("dcl_sparse_conv_scratch_floats", int(cap_sum), int(cout)), dtype=torch.float32,
+                          device=feats[0].device)
     arr = lambda ts: None if ts is None else _ptr_array(ts)                                   # noqa: E731
     N.check(N.lib().dcl_sparse_conv_fwd_sides(
         ns, _ptr_array(feats), _ptr_array(nbrs), (C.c_int32 * ns)(*[int(nb.shape[1]) for nb in nbrs]),
         (C.c_int32 * ns)(*[int(n) for n in n_outs]), _ptr_array(Ws), arr(pieces), int(cin), int(cout), int(kvol), int(bool(subm)),
-        arr(scales), arr(shifts), int(bool(relu)), _ptr_array(outs), N.ptr(scratch), C.c_int64(scratch.numel()),
+        arr(scales), arr(shifts), int(bool(relu)), _ptr_array(outs), N.ptr(scratch), scratch.numel(),
         arr(None if orders is None else [o[0] for o in orders]), arr(None if orders is None else [o[1] for o in orders]),
         arr(None if orders is None else [o[2] for o in orders]), N.stream()), "sparse_conv_fwd_sides")
     return outs
@@ -542,15 +533,14 @@ class BackboneRun(object):
         N.need_cuda(occ)
         assert occ.dtype == torch.int32 and occ.is_contiguous()
         self.occ, self.batch, self.S, self.V0 = occ, int(batch), int(S), occ.shape[0]
-        nbytes = C.c_int64(0)
-        N.check(N.lib().dcl_backbone_ws_bytes(self.batch, self.S, self.V0, C.byref(nbytes)), "backbone_ws_bytes")
-        self.ws = torch.empty(nbytes.value, dtype=torch.uint8, device=occ.device)
+        nbytes = N.query("dcl_backbone_ws_bytes", self.batch, self.S, self.V0)
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=occ.device)
         if counts_dev is not None and not counts_dev.is_cuda and not counts_dev.is_pinned():
             raise RuntimeError("BackboneRun: a host counts buffer must be pinned (the geometry kernels write into it)")
         self.counts_dev = torch.empty(8, dtype=torch.int32, device=occ.device) if counts_dev is None else counts_dev
         self.chan = (C.c_int32 * 9)(*BACKBONE_CHANNELS)
         N.check(N.lib().dcl_backbone_geometry_window(N.ptr(occ), self.V0, int(batch_lo), self.batch, self.S, N.ptr(self.ws),
-                                                     nbytes.value, N.ptr(self.counts_dev), N.stream()),
+                                                     nbytes, N.ptr(self.counts_dev), N.stream()),
                 "backbone_geometry")
         self.counts = None
         self.levels = None
@@ -563,25 +553,22 @@ class BackboneRun(object):
         """-> list of 4 level feature tensors (n_pool_m, C_m).  split: the backbone's ConvSplitPieces (the layers CONV_SPLIT_WIDTHS
         lists for this many crops then run the split-bf16 conv form) or None."""
         dev = vox_feats.device
-        nbytes = C.c_int64(0)
-        N.check(N.lib().dcl_backbone_ws2_bytes(self.ccounts, self.chan, C.byref(nbytes)), "backbone_ws2_bytes")
-        ws2 = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        nbytes = N.query("dcl_backbone_ws2_bytes", self.ccounts, self.chan)
+        ws2 = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self.levels = [torch.empty((self.counts[2 * m + 1], BACKBONE_CHANNELS[2 * m + 2]), dtype=torch.float32,
                                    device=dev) for m in range(4)]
         N.check(N.lib().dcl_backbone_features_split(N.ptr(self.occ), self.V0, self.batch, self.S, N.ptr(self.ws), self.ccounts,
                                                     self.chan, N.ptr(vox_feats), weights_arr,
                                                     None if split is None else split.ptrs(self.batch), scales_arr, shifts_arr,
-                                                    N.ptr(ws2), nbytes.value, _ptr_array(self.levels), N.stream()),
+                                                    N.ptr(ws2), nbytes, _ptr_array(self.levels), N.stream()),
                 "backbone_features")
         return self.levels
 
     def level_indices(self, m):
         """(n_pool_m, 4) int32 view of pooled level m's voxel rows inside the workspace."""
-        off, wp, Sl = C.c_int64(0), C.c_int64(0), C.c_int32(0)
-        N.check(N.lib().dcl_backbone_level_info(self.batch, self.S, self.V0, m, C.byref(off), C.byref(wp), C.byref(Sl)),
-                "backbone_level_info")
+        off, _, _ = N.query("dcl_backbone_level_info", self.batch, self.S, self.V0, m, ctype=(C.c_int64, C.c_int64, C.c_int32))
         n = self.counts[2 * m + 1]
-        return self.ws[off.value:off.value + 16 * n].view(torch.int32).view(n, 4)
+        return self.ws[off:off + 16 * n].view(torch.int32).view(n, 4)
 
     def point_features(self, points_b4, voxel_extents, offset, out=None):
         """points_b4 (n,4) -> (n,480) interpolated multi-scale features."""
@@ -593,7 +580,7 @@ class BackboneRun(object):
         tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=dev)
         ve = (C.c_float * 4)(*[float(v) for v in voxel_extents])
         N.check(N.lib().dcl_point_features(n, N.ptr(points_b4), self.batch, self.S, self.V0, N.ptr(self.ws), self.ccounts,
-                                           self.chan, _ptr_array(self.levels), ve, _c_float(offset), N.ptr(out),
+                                           self.chan, _ptr_array(self.levels), ve, offset, N.ptr(out),
                                            out.stride(0), N.ptr(tmp), tmp_bytes, N.stream()), "point_features")
         return out
 
@@ -606,7 +593,7 @@ class BackboneRun(object):
         idx = torch.empty((4, n, 3), dtype=torch.int32, device=dev)
         ve = (C.c_float * 4)(*[float(v) for v in voxel_extents])
         N.check(N.lib().dcl_point_neighbours(n, N.ptr(points_b4), self.batch, self.S, self.V0, N.ptr(self.ws), self.ccounts,
-                                             ve, _c_float(offset), N.ptr(dist2), N.ptr(idx), N.stream()),
+                                             ve, offset, N.ptr(dist2), N.ptr(idx), N.stream()),
                 "point_neighbours")
         return dist2, idx
 
@@ -636,10 +623,8 @@ def backbone_features_pair(run_a, vox_a, ptrs_a, run_b, vox_b, ptrs_b):
     else:
         ws2, ws2_bytes = [], []
         for r in runs:
-            nbytes = C.c_int64(0)
-            N.check(N.lib().dcl_backbone_ws2_bytes(r.ccounts, r.chan, C.byref(nbytes)), "backbone_ws2_bytes")
-            ws2.append(torch.empty(nbytes.value, dtype=torch.uint8, device=dev))
-            ws2_bytes.append(nbytes.value)
+            ws2_bytes.append(N.query("dcl_backbone_ws2_bytes", r.ccounts, r.chan))
+            ws2.append(torch.empty(ws2_bytes[-1], dtype=torch.uint8, device=dev))
             r.levels = [torch.empty((r.counts[2 * m + 1], BACKBONE_CHANNELS[2 * m + 2]), dtype=torch.float32, device=dev)
                         for m in range(4)]
         counts_host = (C.POINTER(C.c_int32) * 2)(*[C.cast(r.ccounts, C.POINTER(C.c_int32)) for r in runs])
@@ -670,18 +655,14 @@ class BackboneRunCap(object):
         assert occ.dtype == torch.int32 and occ.is_contiguous() and v0_dev.dtype == torch.int32
         self.occ, self.v0_dev, self.batch, self.S, self.V0 = occ, v0_dev, int(batch), int(S), occ.shape[0]
         dev = occ.device
-        nbytes = C.c_int64(0)
-        N.check(N.lib().dcl_backbone_ws_bytes(self.batch, self.S, self.V0, C.byref(nbytes)), "backbone_ws_bytes")
-        self.ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        self.ws_bytes = nbytes.value
+        self.ws_bytes = N.query("dcl_backbone_ws_bytes", self.batch, self.S, self.V0)
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
         self.counts_dev = torch.zeros(8, dtype=torch.int32, device=dev)
         self.chan = (C.c_int32 * 9)(*BACKBONE_CHANNELS)
         self.caps = (C.c_int32 * 8)()
         N.check(N.lib().dcl_backbone_caps(self.batch, self.S, self.V0, self.caps), "backbone_caps")
-        n2 = C.c_int64(0)
-        N.check(N.lib().dcl_backbone_ws2_bytes(self.caps, self.chan, C.byref(n2)), "backbone_ws2_bytes")
-        self.ws2 = torch.empty(n2.value, dtype=torch.uint8, device=dev)
-        self.ws2_bytes = n2.value
+        self.ws2_bytes = N.query("dcl_backbone_ws2_bytes", self.caps, self.chan)
+        self.ws2 = torch.empty(self.ws2_bytes, dtype=torch.uint8, device=dev)
         self.levels = [torch.empty((self.caps[2 * m + 1], BACKBONE_CHANNELS[2 * m + 2]), dtype=torch.float32, device=dev)
                        for m in range(4)]
         self.level_ptrs = _ptr_array(self.levels)
@@ -716,7 +697,7 @@ class BackboneRunCap(object):
         n = points_b4.shape[0]
         ve = (C.c_float * 4)(*[float(v) for v in voxel_extents])
         N.check(N.lib().dcl_point_features_cap(n, N.ptr(points_b4), self.batch, self.S, self.V0, N.ptr(self.ws),
-                                               N.ptr(self.counts_dev), self.chan, self.level_ptrs, ve, _c_float(offset),
+                                               N.ptr(self.counts_dev), self.chan, self.level_ptrs, ve, offset,
                                                N.ptr(out), out.stride(0), N.ptr(tmp), tmp.numel(), N.stream()),
                 "point_features_cap")
         return out
@@ -729,7 +710,7 @@ class BackboneRunCap(object):
         n = points_b4.shape[0]
         ve = (C.c_float * 4)(*[float(v) for v in voxel_extents])
         N.check(N.lib().dcl_point_neighbours_cap(n, N.ptr(points_b4), self.batch, self.S, self.V0, N.ptr(self.ws), ve,
-                                                 _c_float(offset), N.ptr(dist2), N.ptr(idx), N.stream()),
+                                                 offset, N.ptr(dist2), N.ptr(idx), N.stream()),
                 "point_neighbours_cap")
 
     def point_interpolate(self, dist2, idx, out):
@@ -776,7 +757,7 @@ def voxel_centres(aset_or_indices, ve, off, n=None):
     ind = aset_or_indices
     n = ind.shape[0] if n is None else n
     out = torch.empty((max(n, 1), 4), dtype=torch.float32, device=ind.device)
-    N.check(N.lib().dcl_voxel_centres(N.ptr(ind), N.vp(0), int(n), _c_float(ve), _c_float(off), N.ptr(out), N.stream()),
+    N.check(N.lib().dcl_voxel_centres(N.ptr(ind), N.vp(0), int(n), ve, off, N.ptr(out), N.stream()),
             "voxel_centres")
     return out[:n]
 
@@ -788,7 +769,7 @@ def ball_query(radius, nsample, xyz, new_xyz):
     B, n, _ = xyz.shape
     m = new_xyz.shape[1]
     idx = torch.empty((B, m, nsample), dtype=torch.int32, device=xyz.device)
-    N.check(N.lib().dcl_ball_query(B, n, m, _c_float(radius), int(nsample), N.ptr(new_xyz), N.ptr(xyz), N.ptr(idx),
+    N.check(N.lib().dcl_ball_query(B, n, m, radius, int(nsample), N.ptr(new_xyz), N.ptr(xyz), N.ptr(idx),
                                    N.stream()), "ball_query")
     return idx
 
@@ -923,12 +904,10 @@ def _rigid_args(pts, R, t, inverse, host, what):
 
 
 def _rigid_points(pts, R, t, inverse, host):
-    b, n, inv = _rigid_args(pts, R, t, inverse, host, "rigid_points_host" if host else "rigid_points")
+    what = "rigid_points_host" if host else "rigid_points"
+    b, n, inv = _rigid_args(pts, R, t, inverse, host, what)
     out = torch.empty_like(pts)
-    if host:
-        N.check(N.lib().dcl_rigid_points_host(b, n, N.ptr(pts), N.ptr(R), N.ptr(t), inv, N.ptr(out)), "rigid_points_host")
-    else:
-        N.check(N.lib().dcl_rigid_points(b, n, N.ptr(pts), N.ptr(R), N.ptr(t), inv, N.ptr(out), N.stream()), "rigid_points")
+    N.twin("dcl_rigid_points", host, what, b, n, N.ptr(pts), N.ptr(R), N.ptr(t), inv, N.ptr(out))
     return out
 
 
@@ -939,12 +918,8 @@ def _rigid_points_backward(pts, R, t, inverse, g_out, need_pts, host):
     _f32_like(g_out, (b, n, 3), "g_out")
     g_R, g_t = torch.empty_like(R), torch.empty_like(t)
     g_pts = torch.empty_like(pts) if need_pts else None
-    if host:
-        N.check(N.lib().dcl_rigid_points_bwd_host(b, n, N.ptr(pts), N.ptr(R), N.ptr(t), inv, N.ptr(g_out), N.ptr(g_R),
-                                                  N.ptr(g_t), N.ptr(g_pts)), what)
-    else:
-        N.check(N.lib().dcl_rigid_points_bwd(b, n, N.ptr(pts), N.ptr(R), N.ptr(t), inv, N.ptr(g_out), N.ptr(g_R), N.ptr(g_t),
-                                             N.ptr(g_pts), N.stream()), what)
+    N.twin("dcl_rigid_points_bwd", host, what, b, n, N.ptr(pts), N.ptr(R), N.ptr(t), inv, N.ptr(g_out), N.ptr(g_R), N.ptr(g_t),
+           N.ptr(g_pts))
     return g_R, g_t, g_pts
 
 
@@ -1008,10 +983,7 @@ def _pose_objective(posed, posed_gt, sym, cd_pose, Yc, cano_pred, cano_gt, Xo, c
     L = torch.empty((b, 2 * n), dtype=torch.float32, device=dev) if full else None
     crop_sums = torch.empty((max(b, 1), 5), dtype=torch.float32, device=dev)
     packed = torch.zeros((5,), dtype=torch.float32, device=dev) if b == 0 else torch.empty((5,), dtype=torch.float32, device=dev)
-    if host:
-        N.check(N.lib().dcl_pose_objective_fwd_host(b, n, *ptrs, N.ptr(L), N.ptr(crop_sums), N.ptr(packed)), what)
-    else:
-        N.check(N.lib().dcl_pose_objective_fwd(b, n, *ptrs, N.ptr(L), N.ptr(crop_sums), N.ptr(packed), N.stream()), what)
+    N.twin("dcl_pose_objective_fwd", host, what, b, n, *ptrs, N.ptr(L), N.ptr(crop_sums), N.ptr(packed))
     return packed, L
 
 
@@ -1030,10 +1002,7 @@ def _pose_objective_backward(g_packed, posed, posed_gt, sym, Yc, cano_pred, cano
     g_cd = [new(b, n) for _ in range(6 if full else 2)] + ([] if full else [None] * 4)
     g_Xo, g_Yc, g_conf = (new(b, n, 3), new(b, n, 3), new(b, 2 * n)) if full else (None, None, None)
     outs = (N.ptr(g_packed), N.ptr(g_posed), N.ptr(g_Xo), N.ptr(g_Yc), N.ptr(g_conf)) + tuple(N.ptr(g) for g in g_cd)
-    if host:
-        N.check(N.lib().dcl_pose_objective_bwd_host(b, n, *ptrs, N.ptr(L), *outs), what)
-    else:
-        N.check(N.lib().dcl_pose_objective_bwd(b, n, *ptrs, N.ptr(L), *outs, N.stream()), what)
+    N.twin("dcl_pose_objective_bwd", host, what, b, n, *ptrs, N.ptr(L), *outs)
     return g_posed, g_Xo, g_Yc, g_conf, (g_cd[0], g_cd[1]), (g_cd[2], g_cd[3]), (g_cd[4], g_cd[5])
 
 
@@ -1077,75 +1046,6 @@ def _conf_pool_cm_args(w, F1, F2, host, what):
     return b, c, n1, n2, N.f32c(w), N.f32c(F1), N.f32c(F2)
 
 
-def _conf_pool_cm(w, F1, F2, host):
-    what = "conf_pool_cm_host" if host else "conf_pool_cm"
-    b, c, n1, n2, w, F1, F2 = _conf_pool_cm_args(w, F1, F2, host, what)
-    pooled = torch.empty((b, c), dtype=torch.float32, device=F1.device)
-    if host:
-        N.check(N.lib().dcl_conf_pool_cm_fwd_host(b, c, n1, n2, N.ptr(w), N.ptr(F1), N.ptr(F2), N.ptr(pooled)), what)
-    else:
-        N.check(N.lib().dcl_conf_pool_cm_fwd(b, c, n1, n2, N.ptr(w), N.ptr(F1), N.ptr(F2), N.ptr(pooled), N.stream()), what)
-    return pooled
-
-
-def _conf_pool_cm_backward(conf, w, F1, F2, g_pooled, g_conf, need_logits, need_F, host):
-    what = "conf_pool_cm_backward_host" if host else "conf_pool_cm_backward"
-    b, c, n1, n2, w, F1, F2 = _conf_pool_cm_args(w, F1, F2, host, what)
-    _same_side(host, what, conf, g_pooled, g_conf)
-    assert need_logits or need_F
-    assert tuple(conf.shape) == (b, n1 + n2) and tuple(g_pooled.shape) == (b, c), (tuple(conf.shape), tuple(g_pooled.shape))
-    assert g_conf is None or tuple(g_conf.shape) == (b, n1 + n2), tuple(g_conf.shape)
-    conf, g_pooled = N.f32c(conf), N.f32c(g_pooled)
-    g_conf = None if g_conf is None else N.f32c(g_conf)
-    dev = F1.device
-    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)                  # noqa: E731
-    dl1, dl2 = (new(b, n1), new(b, n2)) if need_logits else (None, None)
-    dF1, dF2 = (torch.empty_like(F1), torch.empty_like(F2)) if need_F else (None, None)
-    ins = (N.ptr(conf), N.ptr(w), N.ptr(F1), N.ptr(F2), N.ptr(g_pooled), N.ptr(g_conf))
-    outs = (N.ptr(dl1), N.ptr(dl2), N.ptr(dF1), N.ptr(dF2))
-    if host:
-        N.check(N.lib().dcl_conf_pool_cm_bwd_host(b, c, n1, n2, *ins, *outs), what)
-    else:
-        ws, nbytes = None, 0
-        if need_logits:
-            q = C.c_int64(0)
-            N.check(N.lib().dcl_conf_pool_cm_bwd_ws_bytes(b, c, n1, n2, C.byref(q)), "conf_pool_cm_bwd_ws_bytes")
-            nbytes = int(q.value)
-            ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=dev)
-        N.check(N.lib().dcl_conf_pool_cm_bwd(b, c, n1, n2, *ins, *outs, N.ptr(ws), nbytes, N.stream()), what)
-    return dl1, dl2, dF1, dF2
-
-
-def conf_pool_cm(w, F1, F2):
-    """The confidence-weighted pooling on channel-major activations (dcl_conf_pool_cm_fwd; csrc/conf_pool_grad.hip): w (b, n1+n2)
-    the softmax weights as conf_softmax leaves them, F1 (b,C,n1), F2 (b,C,n2) -> pooled (b,C) = sum_j w[j] F[c][j] over both
-    directions, in the summation order include/dclnet_hip.h pins.  One launch; F is read once and nothing of its size is made
-    (a non-contiguous F is copied first)."""
-    return _conf_pool_cm(w, F1, F2, False)
-
-
-def conf_pool_cm_backward(conf, w, F1, F2, g_pooled, g_conf=None, need_logits=True, need_F=True):
-    """Gradients of sigmoid -> softmax -> conf_pool_cm (dcl_conf_pool_cm_bwd): conf, w (b, n1+n2) as conf_softmax returned them,
-    g_pooled (b,C) and g_conf (b, n1+n2) or None (zero) the upstream gradients of pooled and conf -> (dlogit1 (b,n1), dlogit2
-    (b,n2), dF1 (b,C,n1), dF2 (b,C,n2)); a pair that is not needed is None and is not computed.  F is read once (for the
-    logits), dF is a pure write; no atomics, every sum in a pinned order: the same inputs give the same bits."""
-    return _conf_pool_cm_backward(conf, w, F1, F2, g_pooled, g_conf, need_logits, need_F, False)
-
-
-def conf_pool_cm_host(w, F1, F2):
-    """conf_pool_cm on CPU tensors: the kernel's routines compiled for the host, in their summation order.  For checking the
-    arithmetic where there is no GPU; no model path calls it."""
-    return _conf_pool_cm(w, F1, F2, True)
-
-
-def conf_pool_cm_backward_host(conf, w, F1, F2, g_pooled, g_conf=None, need_logits=True, need_F=True):
-    """conf_pool_cm_backward on CPU tensors; no model path calls it."""
-    return _conf_pool_cm_backward(conf, w, F1, F2, g_pooled, g_conf, need_logits, need_F, True)
-
-
-POOL_PM_ROWS = 64              # include/dclnet_hip.h: DCL_POOL_PM_ROWS, the rows per chunk of the point-major pooling's sums
-
-
 def _conf_pool_pm_args(w, F1, F2, host, what):
     _same_side(host, what, w, F1, F2)
     assert F1.dim() == 2 and F2.dim() == 2 and F1.shape[1] == F2.shape[1], (tuple(F1.shape), tuple(F2.shape))
@@ -1157,20 +1057,21 @@ def _conf_pool_pm_args(w, F1, F2, host, what):
     return b, c, n1, n2, N.f32c(w), N.f32c(F1), N.f32c(F2)
 
 
-def _conf_pool_pm(w, F1, F2, host):
-    what = "conf_pool_pm_host" if host else "conf_pool_pm"
-    b, c, n1, n2, w, F1, F2 = _conf_pool_pm_args(w, F1, F2, host, what)
+_CONF_POOL_ARGS = {"cm": _conf_pool_cm_args, "pm": _conf_pool_pm_args}
+
+
+def _conf_pool_layout(layout, w, F1, F2, host):
+    """conf_pool_cm / conf_pool_pm and their host twins: one implementation, the layout picks the shape check and the symbols"""
+    what = "conf_pool_%s%s" % (layout, "_host" if host else "")
+    b, c, n1, n2, w, F1, F2 = _CONF_POOL_ARGS[layout](w, F1, F2, host, what)
     pooled = torch.empty((b, c), dtype=torch.float32, device=F1.device)
-    if host:
-        N.check(N.lib().dcl_conf_pool_pm_fwd_host(b, c, n1, n2, N.ptr(w), N.ptr(F1), N.ptr(F2), N.ptr(pooled)), what)
-    else:
-        N.check(N.lib().dcl_conf_pool_pm_fwd(b, c, n1, n2, N.ptr(w), N.ptr(F1), N.ptr(F2), N.ptr(pooled), N.stream()), what)
+    N.twin("dcl_conf_pool_%s_fwd" % layout, host, what, b, c, n1, n2, N.ptr(w), N.ptr(F1), N.ptr(F2), N.ptr(pooled))
     return pooled
 
 
-def _conf_pool_pm_backward(conf, w, F1, F2, g_pooled, g_conf, need_logits, need_F, host):
-    what = "conf_pool_pm_backward_host" if host else "conf_pool_pm_backward"
-    b, c, n1, n2, w, F1, F2 = _conf_pool_pm_args(w, F1, F2, host, what)
+def _conf_pool_layout_backward(layout, conf, w, F1, F2, g_pooled, g_conf, need_logits, need_F, host):
+    what = "conf_pool_%s_backward%s" % (layout, "_host" if host else "")
+    b, c, n1, n2, w, F1, F2 = _CONF_POOL_ARGS[layout](w, F1, F2, host, what)
     _same_side(host, what, conf, g_pooled, g_conf)
     assert need_logits or need_F
     assert tuple(conf.shape) == (b, n1 + n2) and tuple(g_pooled.shape) == (b, c), (tuple(conf.shape), tuple(g_pooled.shape))
@@ -1181,19 +1082,46 @@ def _conf_pool_pm_backward(conf, w, F1, F2, g_pooled, g_conf, need_logits, need_
     new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)                  # noqa: E731
     dl1, dl2 = (new(b, n1), new(b, n2)) if need_logits else (None, None)
     dF1, dF2 = (torch.empty_like(F1), torch.empty_like(F2)) if need_F else (None, None)
-    ins = (N.ptr(conf), N.ptr(w), N.ptr(F1), N.ptr(F2), N.ptr(g_pooled), N.ptr(g_conf))
-    outs = (N.ptr(dl1), N.ptr(dl2), N.ptr(dF1), N.ptr(dF2))
-    if host:
-        N.check(N.lib().dcl_conf_pool_pm_bwd_host(b, c, n1, n2, *ins, *outs), what)
-    else:
+    scratch = ()
+    if not host:
         ws, nbytes = None, 0
         if need_logits:
-            q = C.c_int64(0)
-            N.check(N.lib().dcl_conf_pool_pm_bwd_ws_bytes(b, c, n1, n2, C.byref(q)), "conf_pool_pm_bwd_ws_bytes")
-            nbytes = int(q.value)
+            nbytes = N.query("dcl_conf_pool_%s_bwd_ws_bytes" % layout, b, c, n1, n2)
             ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=dev)
-        N.check(N.lib().dcl_conf_pool_pm_bwd(b, c, n1, n2, *ins, *outs, N.ptr(ws), nbytes, N.stream()), what)
+        scratch = (N.ptr(ws), nbytes)
+    N.twin("dcl_conf_pool_%s_bwd" % layout, host, what, b, c, n1, n2, N.ptr(conf), N.ptr(w), N.ptr(F1), N.ptr(F2), N.ptr(g_pooled),
+           N.ptr(g_conf), N.ptr(dl1), N.ptr(dl2), N.ptr(dF1), N.ptr(dF2), *scratch)
     return dl1, dl2, dF1, dF2
+
+
+def conf_pool_cm(w, F1, F2):
+    """The confidence-weighted pooling on channel-major activations (dcl_conf_pool_cm_fwd; csrc/conf_pool_grad.hip): w (b, n1+n2)
+    the softmax weights as conf_softmax leaves them, F1 (b,C,n1), F2 (b,C,n2) -> pooled (b,C) = sum_j w[j] F[c][j] over both
+    directions, in the summation order include/dclnet_hip.h pins.  One launch; F is read once and nothing of its size is made
+    (a non-contiguous F is copied first)."""
+    return _conf_pool_layout("cm", w, F1, F2, False)
+
+
+def conf_pool_cm_backward(conf, w, F1, F2, g_pooled, g_conf=None, need_logits=True, need_F=True):
+    """Gradients of sigmoid -> softmax -> conf_pool_cm (dcl_conf_pool_cm_bwd): conf, w (b, n1+n2) as conf_softmax returned them,
+    g_pooled (b,C) and g_conf (b, n1+n2) or None (zero) the upstream gradients of pooled and conf -> (dlogit1 (b,n1), dlogit2
+    (b,n2), dF1 (b,C,n1), dF2 (b,C,n2)); a pair that is not needed is None and is not computed.  F is read once (for the
+    logits), dF is a pure write; no atomics, every sum in a pinned order: the same inputs give the same bits."""
+    return _conf_pool_layout_backward("cm", conf, w, F1, F2, g_pooled, g_conf, need_logits, need_F, False)
+
+
+def conf_pool_cm_host(w, F1, F2):
+    """conf_pool_cm on CPU tensors: the kernel's routines compiled for the host, in their summation order.  For checking the
+    arithmetic where there is no GPU; no model path calls it."""
+    return _conf_pool_layout("cm", w, F1, F2, True)
+
+
+def conf_pool_cm_backward_host(conf, w, F1, F2, g_pooled, g_conf=None, need_logits=True, need_F=True):
+    """conf_pool_cm_backward on CPU tensors; no model path calls it."""
+    return _conf_pool_layout_backward("cm", conf, w, F1, F2, g_pooled, g_conf, need_logits, need_F, True)
+
+
+POOL_PM_ROWS = N.define("DCL_POOL_PM_ROWS")         # the rows per chunk of the point-major pooling's sums
 
 
 def conf_pool_pm(w, F1, F2):
@@ -1201,7 +1129,7 @@ def conf_pool_pm(w, F1, F2):
     the softmax weights as conf_softmax leaves them, F1 (b n1, C), F2 (b n2, C) row-major, crop i owning rows i n .. i n + n - 1
     -> pooled (b,C) = sum_j w[j] F[j][c] over both directions, in the summation order include/dclnet_hip.h pins (chunks of
     POOL_PM_ROWS rows).  One launch; F is read once and nothing of its size is made (a non-contiguous F is copied first)."""
-    return _conf_pool_pm(w, F1, F2, False)
+    return _conf_pool_layout("pm", w, F1, F2, False)
 
 
 def conf_pool_pm_backward(conf, w, F1, F2, g_pooled, g_conf=None, need_logits=True, need_F=True):
@@ -1209,23 +1137,23 @@ def conf_pool_pm_backward(conf, w, F1, F2, g_pooled, g_conf=None, need_logits=Tr
     g_pooled (b,C) and g_conf (b, n1+n2) or None (zero) the upstream gradients of pooled and conf -> (dlogit1 (b,n1), dlogit2
     (b,n2), dF1 (b n1, C), dF2 (b n2, C)); a pair that is not needed is None and is not computed.  F is read once (for the
     logits), dF is a pure write; no atomics, every sum in a pinned order: the same inputs give the same bits."""
-    return _conf_pool_pm_backward(conf, w, F1, F2, g_pooled, g_conf, need_logits, need_F, False)
+    return _conf_pool_layout_backward("pm", conf, w, F1, F2, g_pooled, g_conf, need_logits, need_F, False)
 
 
 def conf_pool_pm_host(w, F1, F2):
     """conf_pool_pm on CPU tensors: the kernel's routines compiled for the host, in their summation order.  For checking the
     arithmetic where there is no GPU; no model path calls it."""
-    return _conf_pool_pm(w, F1, F2, True)
+    return _conf_pool_layout("pm", w, F1, F2, True)
 
 
 def conf_pool_pm_backward_host(conf, w, F1, F2, g_pooled, g_conf=None, need_logits=True, need_F=True):
     """conf_pool_pm_backward on CPU tensors; no model path calls it."""
-    return _conf_pool_pm_backward(conf, w, F1, F2, g_pooled, g_conf, need_logits, need_F, True)
+    return _conf_pool_layout_backward("pm", conf, w, F1, F2, g_pooled, g_conf, need_logits, need_F, True)
 
 
 N_ = N                         # (below, N is a layer's width)
-NARROW_MAX_N = 16              # include/dclnet_hip.h: DCL_NARROW_MAX_N, the widest layer linear_narrow serves
-NARROW_ROWS = 64               # include/dclnet_hip.h: DCL_NARROW_ROWS, the rows per chunk of its dW / db sums
+NARROW_MAX_N = N.define("DCL_NARROW_MAX_N")         # the widest layer linear_narrow serves
+NARROW_ROWS = N.define("DCL_NARROW_ROWS")           # the rows per chunk of its dW / db sums
 TRAIN_HEADS_MODES = ("modules", "kernels")
 
 
@@ -1257,10 +1185,7 @@ def _linear_narrow(x, W, bias, host):
     bias = None if bias is None else N_.f32c(bias)
     assert bias is None or tuple(bias.shape) == (N,), tuple(bias.shape)
     y = torch.empty((M, N), dtype=torch.float32, device=x.device)
-    if host:
-        N_.check(N_.lib().dcl_linear_narrow_fwd_host(M, K, N, N_.ptr(x), pitch, N_.ptr(W), N_.ptr(bias), N_.ptr(y)), what)
-    else:
-        N_.check(N_.lib().dcl_linear_narrow_fwd(M, K, N, N_.ptr(x), pitch, N_.ptr(W), N_.ptr(bias), N_.ptr(y), N_.stream()), what)
+    N_.twin("dcl_linear_narrow_fwd", host, what, M, K, N, N_.ptr(x), pitch, N_.ptr(W), N_.ptr(bias), N_.ptr(y))
     return y
 
 
@@ -1276,18 +1201,15 @@ def _linear_narrow_backward(x, W, g, need_x, need_w, need_b, host):
     new = (lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)) if M == 0 else \
         (lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev))
     dx, dW, db = new(M, K) if need_x else None, new(N, K) if need_w else None, new(N) if need_b else None
-    if host:
-        N_.check(N_.lib().dcl_linear_narrow_bwd_host(M, K, N, N_.ptr(x), pitch, N_.ptr(W), N_.ptr(g), N_.ptr(dx), N_.ptr(dW),
-                                                     N_.ptr(db)), what)
-    else:
+    scratch = ()
+    if not host:
         ws, nbytes = None, 0
         if need_w or need_b:
-            q = C.c_int64(0)
-            N_.check(N_.lib().dcl_linear_narrow_bwd_ws_bytes(M, K, N, C.byref(q)), "linear_narrow_bwd_ws_bytes")
-            nbytes = int(q.value)
+            nbytes = N_.query("dcl_linear_narrow_bwd_ws_bytes", M, K, N)
             ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=dev)
-        N_.check(N_.lib().dcl_linear_narrow_bwd(M, K, N, N_.ptr(x), pitch, N_.ptr(W), N_.ptr(g), N_.ptr(dx), N_.ptr(dW), N_.ptr(db),
-                                                N_.ptr(ws), nbytes, N_.stream()), what)
+        scratch = (N_.ptr(ws), nbytes)
+    N_.twin("dcl_linear_narrow_bwd", host, what, M, K, N, N_.ptr(x), pitch, N_.ptr(W), N_.ptr(g), N_.ptr(dx), N_.ptr(dW), N_.ptr(db),
+            *scratch)
     return dx, dW, db
 
 
@@ -1347,10 +1269,7 @@ def _pose_heads_train(x, params, host):
     new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)            # noqa: E731
     h1, h2, o9, t3 = new(2, b, d1), new(2, b, d2), new(b, n_rot), new(b, n_trans)
     ptrs = [N_.ptr(t) for t in [x] + params + [h1, h2, o9, t3]]
-    if host:
-        N_.check(N_.lib().dcl_pose_heads_train_fwd_host(*dims, *ptrs), what)
-    else:
-        N_.check(N_.lib().dcl_pose_heads_train_fwd(*dims, *ptrs, N_.stream()), what)
+    N_.twin("dcl_pose_heads_train_fwd", host, what, *dims, *ptrs)
     return o9, t3, h1, h2
 
 
@@ -1373,14 +1292,12 @@ def _pose_heads_train_backward(x, params, h1, h2, g_o9, g_t3, need_x, need_param
     grads = [new(p) if need else None for p, need in zip(params, need_params)]
     ins = [N_.ptr(t) for t in [x] + params[0:6:2] + params[6:12:2] + [h1, h2, g_o9, g_t3]]
     outs = [N_.ptr(dx)] + [N_.ptr(t) for t in grads]
-    if host:
-        N_.check(N_.lib().dcl_pose_heads_train_bwd_host(*dims, *ins, *outs), what)
-    else:
-        q = C.c_int64(0)
-        N_.check(N_.lib().dcl_pose_heads_train_bwd_ws_bytes(*dims, C.byref(q)), "pose_heads_train_bwd_ws_bytes")
-        nbytes = int(q.value)
+    scratch = ()
+    if not host:
+        nbytes = N_.query("dcl_pose_heads_train_bwd_ws_bytes", *dims)
         ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=x.device)
-        N_.check(N_.lib().dcl_pose_heads_train_bwd(*dims, *ins, *outs, N_.ptr(ws), nbytes, N_.stream()), what)
+        scratch = (N_.ptr(ws), nbytes)
+    N_.twin("dcl_pose_heads_train_bwd", host, what, *dims, *ins, *outs, *scratch)
     return dx, grads
 
 
@@ -1411,7 +1328,7 @@ def pose_heads_train_backward_host(x, params, h1, h2, g_o9, g_t3, need_x=True, n
     return _pose_heads_train_backward(x, params, h1, h2, g_o9, g_t3, need_x, need_params, True)
 
 
-BN_ROWS = 256                  # include/dclnet_hip.h: DCL_BN_ROWS, the rows per chunk of the BatchNorm sums
+BN_ROWS = N.define("DCL_BN_ROWS")                   # the rows per chunk of the BatchNorm sums
 TRAIN_NORM_MODES = ("modules", "fused")
 
 
@@ -1433,9 +1350,7 @@ def _bn_relu_args(x, host, what, *vectors):
 
 
 def _bn_relu_ws(rows, c, dev):
-    q = C.c_int64(0)
-    N.check(N.lib().dcl_bn_relu_ws_bytes(rows, c, C.byref(q)), "bn_relu_ws_bytes")
-    nbytes = int(q.value)
+    nbytes = N.query("dcl_bn_relu_ws_bytes", rows, c)
     return torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=dev), nbytes
 
 
@@ -1455,13 +1370,12 @@ def _bn_relu(x, gamma, beta, running_mean, running_var, momentum, eps, relu, hos
     invstd = torch.empty_like(mean)
     if rows == 0:
         return z, mean.zero_(), invstd.zero_()
-    args = (rows, c, N.ptr(x), N.ptr(gamma), N.ptr(beta), float(eps), float(momentum), N.ptr(running_mean),
-            N.ptr(running_var), N.ptr(mean), N.ptr(invstd), N.ptr(z), int(bool(relu)))
-    if host:
-        N.check(N.lib().dcl_bn_relu_fwd_host(*args), what)
-    else:
+    scratch = ()
+    if not host:
         ws, nbytes = _bn_relu_ws(rows, c, x.device)
-        N.check(N.lib().dcl_bn_relu_fwd(*args, N.ptr(ws), nbytes, N.stream()), what)
+        scratch = (N.ptr(ws), nbytes)
+    N.twin("dcl_bn_relu_fwd", host, what, rows, c, N.ptr(x), N.ptr(gamma), N.ptr(beta), float(eps), float(momentum),
+           N.ptr(running_mean), N.ptr(running_var), N.ptr(mean), N.ptr(invstd), N.ptr(z), int(bool(relu)), *scratch)
     return z, mean, invstd
 
 
@@ -1482,13 +1396,12 @@ def _bn_relu_backward(x, gamma, beta, mean, invstd, g, relu, need_x, need_affine
     dgamma, dbeta = (torch.empty_like(gamma), torch.empty_like(gamma)) if need_affine else (None, None)
     if rows == 0:
         return dx, None if dgamma is None else dgamma.zero_(), None if dbeta is None else dbeta.zero_()
-    args = (rows, c, N.ptr(x), N.ptr(gamma), N.ptr(beta), N.ptr(mean), N.ptr(invstd), N.ptr(g), int(bool(relu)),
-            N.ptr(dx), N.ptr(dgamma), N.ptr(dbeta))
-    if host:
-        N.check(N.lib().dcl_bn_relu_bwd_host(*args), what)
-    else:
+    scratch = ()
+    if not host:
         ws, nbytes = _bn_relu_ws(rows, c, x.device)
-        N.check(N.lib().dcl_bn_relu_bwd(*args, N.ptr(ws), nbytes, N.stream()), what)
+        scratch = (N.ptr(ws), nbytes)
+    N.twin("dcl_bn_relu_bwd", host, what, rows, c, N.ptr(x), N.ptr(gamma), N.ptr(beta), N.ptr(mean), N.ptr(invstd), N.ptr(g),
+           int(bool(relu)), N.ptr(dx), N.ptr(dgamma), N.ptr(dbeta), *scratch)
     return dx, dgamma, dbeta
 
 
@@ -1520,7 +1433,7 @@ def bn_relu_backward_host(x, gamma, beta, mean, invstd, g, relu=True, need_x=Tru
     return _bn_relu_backward(x, gamma, beta, mean, invstd, g, relu, need_x, need_affine, out, True)
 
 
-OPTIM_CHUNK = 4096             # include/dclnet_hip.h: DCL_OPTIM_CHUNK
+OPTIM_CHUNK = N.define("DCL_OPTIM_CHUNK")
 OPTIM_TENSOR_BYTES = 48        # sizeof(dclOptimTensor): four pointers, int64 numel, float step_size, float bc2_sqrt
 
 
@@ -1554,7 +1467,7 @@ def adam_step(table, chunk_tensor, chunk_begin, grad_scale, beta1, beta2, eps):
     POINTERS: the caller moves the tensors' version counters (dcl.optim.Adam does)."""
     n_tensors, n_chunks = _optim_tables(table, chunk_tensor, chunk_begin)
     N.check(N.lib().dcl_adam_step(n_tensors, N.ptr(table), n_chunks, N.ptr(chunk_tensor), N.ptr(chunk_begin),
-                                  _c_float(grad_scale), _c_float(beta1), _c_float(beta2), _c_float(eps), N.stream()),
+                                  grad_scale, beta1, beta2, eps, N.stream()),
             "adam_step")
 
 
@@ -1566,12 +1479,12 @@ def adam_step_dev(table, chunk_tensor, chunk_begin, grad_scale, beta1, beta2, ep
     N.need_cuda(grad_scale)
     assert grad_scale.dtype == torch.float32 and grad_scale.numel() == 1 and grad_scale.device == table.device
     N.check(N.lib().dcl_adam_step_dev(n_tensors, N.ptr(table), n_chunks, N.ptr(chunk_tensor), N.ptr(chunk_begin),
-                                      N.ptr(grad_scale), _c_float(beta1), _c_float(beta2), _c_float(eps), N.stream()),
+                                      N.ptr(grad_scale), beta1, beta2, eps, N.stream()),
             "adam_step_dev")
 
 
-AUTOCLIP_OUT_DOUBLES = 4       # include/dclnet_hip.h: DCL_AUTOCLIP_OUT_BYTES / 8 -- {norm, clip_value, scale} and the fp32 slot
-AUTOCLIP_SCALE_F32_INDEX = 6   # DCL_AUTOCLIP_SCALE_F32_OFFSET / 4: where (float)scale lies in out.view(torch.float32)
+AUTOCLIP_OUT_DOUBLES = N.define("DCL_AUTOCLIP_OUT_BYTES") // 8                # {norm, clip_value, scale} and the fp32 slot
+AUTOCLIP_SCALE_F32_INDEX = N.define("DCL_AUTOCLIP_SCALE_F32_OFFSET") // 4     # where (float)scale lies in out.view(torch.float32)
 
 
 def _autoclip_observe(n, sorted_src, sorted_dst, arrival, norm, percentile, out, host):
@@ -1585,11 +1498,8 @@ def _autoclip_observe(n, sorted_src, sorted_dst, arrival, norm, percentile, out,
     assert all(t.dtype == torch.float64 and t.dim() == 1 and t.is_contiguous() for t in ts)
     assert n >= 0 and sorted_src.numel() >= n and sorted_dst.numel() >= n + 1 and arrival.numel() >= n + 1
     assert norm.numel() == 1 and out.numel() == AUTOCLIP_OUT_DOUBLES
-    args = (n, N.ptr(sorted_src), N.ptr(sorted_dst), N.ptr(arrival), N.ptr(norm), float(percentile), N.ptr(out))
-    if host:
-        N.check(N.lib().dcl_autoclip_observe_host(*args), "autoclip_observe_host")
-    else:
-        N.check(N.lib().dcl_autoclip_observe(*(args + (N.stream(),))), "autoclip_observe")
+    N.twin("dcl_autoclip_observe", host, "autoclip_observe_host" if host else "autoclip_observe", n, N.ptr(sorted_src),
+           N.ptr(sorted_dst), N.ptr(arrival), N.ptr(norm), float(percentile), N.ptr(out))
     return out
 
 
@@ -1633,7 +1543,6 @@ def attention_planes(b, nq, nk, concurrent=1, device=None):
     if not ATTENTION_SPLIT:
         return None, False
     lib = N.lib()
-    lib.dcl_cross_attention_planes_bytes.restype = C.c_int64
     pb = int(lib.dcl_cross_attention_planes_bytes(int(b), int(nq), int(nk), int(concurrent)))
     if not pb:
         return None, False
@@ -1662,17 +1571,16 @@ def cross_attention(b, Q, K, V1, O1, V2=None, O2=None, concurrent=1, planes=None
         ev[0].record()
     scratch = None
     if dv1 == 256 and dv2 == 64:          # key-split partial records (small launches, badly quantised large ones)
-        need = C.c_int64(0)
-        N.check(N.lib().dcl_cross_attention_scratch_floats(b, nq, C.byref(need)), "cross_attention_scratch_floats")
-        if need.value:
-            scratch = torch.empty(need.value, dtype=torch.float32, device=Q.device)
+        need = N.query("dcl_cross_attention_scratch_floats", b, nq)
+        if need:
+            scratch = torch.empty(need, dtype=torch.float32, device=Q.device)
     if planes is None and dv1 == 256 and dv2 == 64:    # large calls: scratch for the K / V pieces of the split-bf16 kernel (csrc/dense.hip)
         planes, _ = attention_planes(b, nq, nk, concurrent, Q.device)
     N.check(N.lib().dcl_cross_attention_ws3(b, nq, nk, N.ptr(Q), _ld(Q), N.ptr(K), _ld(K), N.ptr(V1), dv1, 256 if V1 is None else _ld(V1),
                                             N.ptr(O1), _ld(O1), N.ptr(V2), dv2, 0 if V2 is None else _ld(V2), N.ptr(O2),
                                             0 if O2 is None else _ld(O2), N.ptr(scratch),
-                                            C.c_int64(0 if scratch is None else scratch.numel()), int(concurrent), N.ptr(planes),
-                                            C.c_int64(0 if planes is None else planes.numel()), N.stream()),
+                                            0 if scratch is None else scratch.numel(), int(concurrent), N.ptr(planes),
+                                            0 if planes is None else planes.numel(), N.stream()),
             "cross_attention")
     if ev is not None:
         ev[1].record()
@@ -1701,14 +1609,13 @@ def cross_attention_backward_into(b, Q, K, V1, V2, O1, O2, dO1, dO2, dQ, dK, dV1
     """cross_attention_backward writing into the caller's dQ, dK, dV1, dV2 (which may be column blocks of wider buffers)."""
     N.need_cuda(Q, K, V1, V2, O1, O2, dO1, dO2, dQ, dK, dV1, dV2)
     nq, nk = Q.shape[0] // b, K.shape[0] // b
-    nbytes = C.c_int64(0)
-    N.check(N.lib().dcl_cross_attention_bwd_ws_bytes(int(b), nq, nk, C.byref(nbytes)), "cross_attention_bwd_ws_bytes")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=Q.device)
+    nbytes = N.query("dcl_cross_attention_bwd_ws_bytes", int(b), nq, nk)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=Q.device)
     N.check(N.lib().dcl_cross_attention_bwd(int(b), nq, nk, N.ptr(Q), _ld(Q), N.ptr(K), _ld(K), N.ptr(V1), V1.shape[1], _ld(V1),
                                             N.ptr(V2), V2.shape[1], _ld(V2), N.ptr(O1), _ld(O1), N.ptr(O2), _ld(O2),
                                             N.ptr(dO1), _ld(dO1), N.ptr(dO2), 0 if dO2 is None else _ld(dO2),
                                             N.ptr(dQ), _ld(dQ), N.ptr(dK), _ld(dK), N.ptr(dV1), _ld(dV1), N.ptr(dV2), _ld(dV2),
-                                            N.ptr(ws), C.c_int64(nbytes.value), N.stream()), "cross_attention_bwd")
+                                            N.ptr(ws), nbytes, N.stream()), "cross_attention_bwd")
     return dQ, dK, dV1, dV2
 
 
@@ -1754,7 +1661,7 @@ def affine3_relu(xyz, W3, term):
     rows, c = term.shape
     assert tuple(W3.shape) == (3, c) and xyz.shape[0] == rows
     out = torch.empty_like(term)
-    N.check(N.lib().dcl_affine3_relu(C.c_int64(rows), int(c), N.ptr(xyz), N.ptr(W3), N.ptr(term), N.ptr(out), N.stream()),
+    N.check(N.lib().dcl_affine3_relu(rows, int(c), N.ptr(xyz), N.ptr(W3), N.ptr(term), N.ptr(out), N.stream()),
             "affine3_relu")
     return out
 
@@ -1810,11 +1717,7 @@ def _refine_first(pts, R, t, W3, term, host):
     _f32_like(term, (b * n, c), "term")
     _f32_like(W3, (3, c), "W3")
     out = torch.empty_like(term)
-    if host:
-        N.check(N.lib().dcl_refine_first_host(b, n, c, N.ptr(pts), N.ptr(R), N.ptr(t), N.ptr(W3), N.ptr(term), N.ptr(out)), what)
-    else:
-        N.check(N.lib().dcl_refine_first(b, n, c, N.ptr(pts), N.ptr(R), N.ptr(t), N.ptr(W3), N.ptr(term), N.ptr(out), N.stream()),
-                what)
+    N.twin("dcl_refine_first", host, what, b, n, c, N.ptr(pts), N.ptr(R), N.ptr(t), N.ptr(W3), N.ptr(term), N.ptr(out))
     return out
 
 
@@ -1925,10 +1828,10 @@ def _linear_fp32(x, Wt, bias, relu, out, vendor):
     K, n = Wt.shape
     out = _layer_io(x, K, n, bias, out, dense=(Wt,))
     M = x.shape[0]
-    args = (N.ptr(x), C.c_int64(_pitch(x)), N.ptr(Wt), C.c_int64(_pitch(Wt)), N.ptr(bias), N.ptr(out), C.c_int64(_pitch(out)),
+    args = (N.ptr(x), _pitch(x), N.ptr(Wt), _pitch(Wt), N.ptr(bias), N.ptr(out), _pitch(out),
             int(M), int(n), int(K), int(bool(relu)))
     if vendor:
-        N.check(N.lib().dcl_linear_fwd(*args, None, C.c_int64(0), N.stream()), "linear_fwd")
+        N.check(N.lib().dcl_linear_fwd(*args, None, 0, N.stream()), "linear_fwd")
     else:
         N.check(N.lib().dcl_linear_dma_fwd(*args, N.stream()), "linear_dma_fwd")
     return out
@@ -2006,8 +1909,8 @@ def _linear_pool(fn, what, x, wargs, K, n, bias, roww, relu, part, rows_per_crop
     if part is None:
         part = torch.empty((tiles, n), dtype=torch.float32, device=x.device)
     assert part.shape == (tiles, n) and part.stride(1) == 1
-    N.check(fn(N.ptr(x), C.c_int64(_pitch(x)), *wargs, N.ptr(bias), N.ptr(roww), int(rows_per_crop),
-                                          C.c_int64(int(w_stride)), N.ptr(part), C.c_int64(_pitch(part)), int(M), int(n), int(K),
+    N.check(fn(N.ptr(x), _pitch(x), *wargs, N.ptr(bias), N.ptr(roww), int(rows_per_crop),
+                                          int(w_stride), N.ptr(part), _pitch(part), int(M), int(n), int(K),
                                           int(bool(relu)), N.stream()), what)
     return part
 
@@ -2023,7 +1926,7 @@ def linear_pool(x, Wt, bias, roww, relu=True, part=None, rows_per_crop=None, w_s
     if sw is not None:
         return linear_split_pool(x, sw, bias, roww, relu, part, rows_per_crop, w_stride)
     M, K = x.shape
-    return _linear_pool(N.lib().dcl_linear_pool_fwd, "linear_pool_fwd", x, (N.ptr(Wt), C.c_int64(_pitch(Wt))), K, Wt.shape[1], bias, roww, relu, part,
+    return _linear_pool(N.lib().dcl_linear_pool_fwd, "linear_pool_fwd", x, (N.ptr(Wt), _pitch(Wt)), K, Wt.shape[1], bias, roww, relu, part,
                         rows_per_crop, w_stride)
 
 
@@ -2036,7 +1939,7 @@ def _linear_rowdot(fn, what, x, wargs, K, n, bias, w3, b3, out):
     assert out.is_contiguous() and out.numel() == M
     if M == 0:                                              # (an empty tensor has no address to pass)
         return out
-    N.check(fn(N.ptr(x), C.c_int64(_pitch(x)), *wargs, N.ptr(bias), N.ptr(w3), C.c_int64(int(w3.stride(0))),
+    N.check(fn(N.ptr(x), _pitch(x), *wargs, N.ptr(bias), N.ptr(w3), int(w3.stride(0)),
                                           N.ptr(b3), N.ptr(out), int(M), int(n), int(K), N.stream()), what)
     return out
 
@@ -2050,7 +1953,7 @@ def linear_rowdot(x, Wt, bias, w3, b3, out=None):
     if sw is not None:
         return linear_split_rowdot(x, sw, bias, w3, b3, out)
     M, K = x.shape
-    return _linear_rowdot(N.lib().dcl_linear_rowdot_fwd, "linear_rowdot_fwd", x, (N.ptr(Wt), C.c_int64(_pitch(Wt))), K, Wt.shape[1],
+    return _linear_rowdot(N.lib().dcl_linear_rowdot_fwd, "linear_rowdot_fwd", x, (N.ptr(Wt), _pitch(Wt)), K, Wt.shape[1],
                           bias, w3, b3, out)
 
 
@@ -2064,11 +1967,10 @@ class SplitWeight:
         assert Wt.dim() == 2 and Wt.dtype == torch.float32 and (Wt.stride(1) == 1 or Wt.shape[1] == 1)
         self.Wt, (self.K, self.n) = Wt, Wt.shape
         lib = N.lib()
-        lib.dcl_linear_split_weight_bytes.restype = C.c_int64
         nbytes = int(lib.dcl_linear_split_weight_bytes(int(self.K), int(self.n)))
         assert nbytes > 0, "split-bf16 GEMM core: K must be a multiple of 16"
         self.planes = torch.empty(nbytes, dtype=torch.uint8, device=Wt.device)
-        N.check(lib.dcl_linear_split_weight(N.ptr(Wt), C.c_int64(_pitch(Wt)), int(self.K), int(self.n), N.ptr(self.planes), N.stream()),
+        N.check(lib.dcl_linear_split_weight(N.ptr(Wt), _pitch(Wt), int(self.K), int(self.n), N.ptr(self.planes), N.stream()),
                 "linear_split_weight")
 
 
@@ -2084,7 +1986,7 @@ def linear_split(x, sw, bias=None, relu=False, out=None):
     N.need_cuda(x)
     M, K, n = x.shape[0], sw.K, sw.n
     out = _layer_io(x, K, n, bias, out)
-    N.check(N.lib().dcl_linear_split_fwd(N.ptr(x), C.c_int64(_pitch(x)), N.ptr(sw.planes), N.ptr(bias), N.ptr(out), C.c_int64(_pitch(out)),
+    N.check(N.lib().dcl_linear_split_fwd(N.ptr(x), _pitch(x), N.ptr(sw.planes), N.ptr(bias), N.ptr(out), _pitch(out),
                                          int(M), int(n), int(K), int(bool(relu)), N.stream()), "linear_split_fwd")
     return out
 
@@ -2104,7 +2006,7 @@ def linear_split_vpieces(x, sw, bias, vplanes, rows_per_crop, relu=True):
     N.need_cuda(x, vplanes)
     M, K, n = x.shape[0], sw.K, sw.n
     assert x.shape[1] == K and n <= 320 and n % 32 == 0 and rows_per_crop % 256 == 0 and M % rows_per_crop == 0
-    N.check(N.lib().dcl_linear_split_vpieces_fwd(N.ptr(x), C.c_int64(_pitch(x)), N.ptr(sw.planes), N.ptr(bias), N.ptr(vplanes),
+    N.check(N.lib().dcl_linear_split_vpieces_fwd(N.ptr(x), _pitch(x), N.ptr(sw.planes), N.ptr(bias), N.ptr(vplanes),
                                                  int(rows_per_crop), int(M), int(n), int(K), int(bool(relu)), N.stream()),
             "linear_split_vpieces_fwd")
     return vplanes
@@ -2149,7 +2051,7 @@ class _LinearJob(C.Structure):
                 ("y", C.c_void_p), ("ldy", C.c_int64), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("relu", C.c_int32)]
 
 
-LINEAR_GROUP_MAX = 8
+LINEAR_GROUP_MAX = N.define("DCL_LINEAR_MAX_JOBS")
 
 
 def linear_group(jobs):
@@ -2199,8 +2101,8 @@ def mlp128_to1(x, layers, out=None):
     if out is None:
         out = torch.empty((M, 1), dtype=torch.float32, device=x.device)
     assert out.is_contiguous() and out.numel() == M
-    N.check(N.lib().dcl_mlp128_to1(N.ptr(x), C.c_int64(_pitch(x)), int(M), N.ptr(W1t), N.ptr(b1), N.ptr(W2t),
-                                   N.ptr(b2), N.ptr(W3t), C.c_int64(int(W3t.stride(0))), N.ptr(b3), N.ptr(out), N.stream()), "mlp128_to1")
+    N.check(N.lib().dcl_mlp128_to1(N.ptr(x), _pitch(x), int(M), N.ptr(W1t), N.ptr(b1), N.ptr(W2t),
+                                   N.ptr(b2), N.ptr(W3t), int(W3t.stride(0)), N.ptr(b3), N.ptr(out), N.stream()), "mlp128_to1")
     return out
 
 
@@ -2277,7 +2179,7 @@ def add(cld, R_pred, t_pred, R_gt, t_gt, cls=None):
 
 
 # ------------------------------------------------------------------------------------ device-resident evaluation tables
-TABLE_MODES = {"adds": 0, "lm": 1, "lmo": 2}          # include/dclnet_hip.h: DCL_TABLE_ADDS / _LM / _LMO
+TABLE_MODES = {"adds": N.define("DCL_TABLE_ADDS"), "lm": N.define("DCL_TABLE_LM"), "lmo": N.define("DCL_TABLE_LMO")}
 
 
 def metric_table_arrays(mode, steps=1, n_classes=21, device="cpu"):
@@ -2367,12 +2269,9 @@ def _tabulate(table, dis, cls, valid, mode, diameter, host):
     assert tuple(dis.shape) == (T, b), "dis must be (steps, b) = %s, got %s" % ((T, b), tuple(dis.shape))
     valid = None if valid is None else N.i32c(valid)
     assert valid is None or valid.numel() == b
-    args = (TABLE_MODES[mode], T, b, C, N.ptr(dis), N.ptr(cls), N.ptr(valid), N.ptr(diameter), N.ptr(table["sums"]),
-            N.ptr(table["maxd"]), N.ptr(table["counts"]), N.ptr(table["bad"]))
-    if host:
-        N.check(N.lib().dcl_metric_tabulate_host(*args), "metric_tabulate_host")
-    else:
-        N.check(N.lib().dcl_metric_tabulate(*(args + (N.stream(),))), "metric_tabulate")
+    N.twin("dcl_metric_tabulate", host, "metric_tabulate_host" if host else "metric_tabulate", TABLE_MODES[mode], T, b, C,
+           N.ptr(dis), N.ptr(cls), N.ptr(valid), N.ptr(diameter), N.ptr(table["sums"]), N.ptr(table["maxd"]),
+           N.ptr(table["counts"]), N.ptr(table["bad"]))
     return table
 
 
@@ -2459,9 +2358,7 @@ def crop_points(depth, label, rgb, boxes, obj_ids, cam, rgb_mean, half_extent, m
     col = torch.empty((n, cap, 3), dtype=torch.float32, device=dev)
     centroid = torch.empty((n, 3), dtype=torch.float32, device=dev)
     counts = torch.zeros((n, 3), dtype=torch.int32, device=dev)
-    ws_ints = C.c_int64(0)
-    N.check(N.lib().dcl_crop_points_ws_ints(n, int(cap), C.byref(ws_ints)), "crop_points_ws_ints")
-    ws = torch.empty(max(int(ws_ints.value), 1), dtype=torch.int32, device=dev)
+    ws = torch.empty(max(N.query("dcl_crop_points_ws_ints", n, int(cap)), 1), dtype=torch.int32, device=dev)
     cam_a = (C.c_float * 6)(*([float(v) for v in cam] + [1.0])[:6])
     mean_a = (C.c_double * 3)(*[float(v) for v in rgb_mean])
     he_a = (C.c_float * 3)(*[float(v) for v in half_extent])
@@ -2503,9 +2400,7 @@ def crop_points_frames(depth, label, rgb, frame_idx, src, cam, rgb_mean, half_ex
     assert rows >= n
     centroid = (torch.empty if rows == n else torch.zeros)((rows, 3), dtype=torch.float32, device=dev)
     counts = torch.zeros((rows, 3), dtype=torch.int32, device=dev)
-    ws_ints = C.c_int64(0)
-    N.check(N.lib().dcl_crop_points_ws_ints(n, int(cap), C.byref(ws_ints)), "crop_points_ws_ints")
-    ws = torch.empty(max(int(ws_ints.value), 1), dtype=torch.int32, device=dev)
+    ws = torch.empty(max(N.query("dcl_crop_points_ws_ints", n, int(cap)), 1), dtype=torch.int32, device=dev)
     cam_a = (C.c_float * 6)(*([float(v) for v in cam] + [1.0])[:6])
     mean_a = (C.c_double * 3)(*[float(v) for v in rgb_mean])
     he_a = (C.c_float * 3)(*[float(v) for v in half_extent])
@@ -2533,12 +2428,12 @@ def crop_sample(xyz, rgb, sample_idx, counts, half_extent0, unit, voxel_limit, n
     coords = torch.empty((n * npoint, 4), dtype=torch.int64, device=dev)
     unit_a = (C.c_float * 3)(*[float(v) for v in unit])
     N.check(N.lib().dcl_crop_sample(n, npoint, cap, N.ptr(xyz), N.ptr(rgb), N.ptr(sample_idx), N.ptr(counts),
-                                    int(min_valid), _c_float(half_extent0), unit_a, int(voxel_limit), N.ptr(feats),
+                                    int(min_valid), half_extent0, unit_a, int(voxel_limit), N.ptr(feats),
                                     N.ptr(coords), N.stream()), "crop_sample")
     return feats, coords
 
 
-CROP_DRAW_MAX_POINTS = 4096    # include/dclnet_hip.h: DCL_CROP_DRAW_MAX_POINTS
+CROP_DRAW_MAX_POINTS = N.define("DCL_CROP_DRAW_MAX_POINTS")
 _U64 = (1 << 64) - 1
 
 
@@ -2552,7 +2447,7 @@ def crop_draw(counts, npoint, seed, frame, min_valid=32, keep_sparse=True):
     idx = torch.empty((n, max(int(npoint), 0)), dtype=torch.int64, device=counts.device)
     valid = torch.empty((n,), dtype=torch.int32, device=counts.device)
     N.check(N.lib().dcl_crop_draw(n, int(npoint), N.ptr(counts), int(min_valid), int(bool(keep_sparse)),
-                                  C.c_uint64(int(seed) & _U64), C.c_uint64(int(frame) & _U64), N.ptr(idx), N.ptr(valid),
+                                  int(seed) & _U64, int(frame) & _U64, N.ptr(idx), N.ptr(valid),
                                   N.stream()), "crop_draw")
     return idx, valid
 
@@ -2566,7 +2461,7 @@ def crop_draw_host(counts, npoint, seed, frame, min_valid=32, keep_sparse=True):
     idx = np.zeros((n, max(int(npoint), 0)), np.int64)
     valid = np.zeros(n, np.int32)
     N.check(N.lib().dcl_crop_draw_host(n, int(npoint), cnt.ctypes.data_as(C.c_void_p), int(min_valid), int(bool(keep_sparse)),
-                                       C.c_uint64(int(seed) & _U64), C.c_uint64(int(frame) & _U64),
+                                       int(seed) & _U64, int(frame) & _U64,
                                        idx.ctypes.data_as(C.c_void_p), valid.ctypes.data_as(C.c_void_p)), "crop_draw_host")
     return idx, valid
 
@@ -2589,7 +2484,7 @@ def crop_draw_keyed(counts, npoint, seed, keys, min_valid=32, keep_sparse=True, 
         idx = torch.empty((n, max(int(npoint), 0)), dtype=torch.int64, device=counts.device)
         valid = torch.empty((n,), dtype=torch.int32, device=counts.device)
     N.check(N.lib().dcl_crop_draw_keyed(n, int(npoint), N.ptr(counts), int(min_valid), int(bool(keep_sparse)),
-                                        C.c_uint64(int(seed) & _U64), N.ptr(keys), N.ptr(idx), N.ptr(valid), N.stream()),
+                                        int(seed) & _U64, N.ptr(keys), N.ptr(idx), N.ptr(valid), N.stream()),
             "crop_draw_keyed")
     return idx, valid
 
@@ -2605,7 +2500,7 @@ def crop_draw_keyed_host(counts, npoint, seed, keys, min_valid=32, keep_sparse=T
     idx = np.zeros((n, max(int(npoint), 0)), np.int64)
     valid = np.zeros(n, np.int32)
     N.check(N.lib().dcl_crop_draw_keyed_host(n, int(npoint), cnt.ctypes.data_as(C.c_void_p), int(min_valid), int(bool(keep_sparse)),
-                                             C.c_uint64(int(seed) & _U64),
+                                             int(seed) & _U64,
                                              C.c_void_p(0) if ks is None else ks.ctypes.data_as(C.c_void_p),
                                              idx.ctypes.data_as(C.c_void_p), valid.ctypes.data_as(C.c_void_p)),
             "crop_draw_keyed_host")
@@ -2615,11 +2510,11 @@ def crop_draw_keyed_host(counts, npoint, seed, keys, min_valid=32, keep_sparse=T
 def crop_draw_keys_host(seed, frame, inst, s, n):
     """base(seed, frame, inst, s) and key(0..n-1) of the draw's generator (dcl_crop_draw_keys_host) -> (int, uint64 array)"""
     import numpy as np
-    base = C.c_uint64(0)
+    base = np.zeros(1, np.uint64)
     keys = np.zeros(int(n), np.uint64)
-    N.check(N.lib().dcl_crop_draw_keys_host(C.c_uint64(int(seed) & _U64), C.c_uint64(int(frame) & _U64), int(inst), int(s), int(n),
-                                            C.byref(base), keys.ctypes.data_as(C.c_void_p)), "crop_draw_keys_host")
-    return int(base.value), keys
+    N.check(N.lib().dcl_crop_draw_keys_host(int(seed) & _U64, int(frame) & _U64, int(inst), int(s), int(n),
+                                            base.ctypes.data_as(C.c_void_p), keys.ctypes.data_as(C.c_void_p)), "crop_draw_keys_host")
+    return int(base[0]), keys
 
 
 def crop_sample_valid(xyz, rgb, sample_idx, counts, valid, half_extent0, unit, voxel_limit, min_valid=32):
@@ -2641,7 +2536,7 @@ def crop_sample_valid(xyz, rgb, sample_idx, counts, valid, half_extent0, unit, v
     coords = torch.empty((n * npoint, 4), dtype=torch.int64, device=dev)
     unit_a = (C.c_float * 3)(*[float(v) for v in unit])
     N.check(N.lib().dcl_crop_sample_valid(n, npoint, cap, N.ptr(xyz), N.ptr(rgb), N.ptr(sample_idx), N.ptr(counts), int(min_valid),
-                                          N.ptr(valid), _c_float(half_extent0), unit_a, int(voxel_limit), N.ptr(feats),
+                                          N.ptr(valid), half_extent0, unit_a, int(voxel_limit), N.ptr(feats),
                                           N.ptr(coords), N.stream()), "crop_sample_valid")
     return feats, coords
 
@@ -2661,7 +2556,7 @@ def crop_sample_valid_host(xyz, rgb, sample_idx, counts, valid, half_extent0, un
     unit_a = (C.c_float * 3)(*[float(v) for v in unit])
     p = lambda a: C.c_void_p(0) if a is None else a.ctypes.data_as(C.c_void_p)
     N.check(N.lib().dcl_crop_sample_valid_host(n, npoint, cap, p(x), p(c), p(idx), p(cnt), int(min_valid), p(val),
-                                               _c_float(half_extent0), unit_a, int(voxel_limit), p(feats), p(coords)),
+                                               half_extent0, unit_a, int(voxel_limit), p(feats), p(coords)),
             "crop_sample_valid_host")
     return feats, coords
 
@@ -2676,10 +2571,9 @@ def mask_box(label, value=1, padding=0):
     n = 1 if label.dim() == 2 else label.shape[0]
     H, W = label.shape[-2], label.shape[-1]
     out = torch.empty((n, 10), dtype=torch.int32, device=label.device)
-    nb = C.c_int64(0)
-    N.check(N.lib().dcl_mask_box_ws_bytes(n, H, W, C.byref(nb)), "mask_box_ws_bytes")
-    ws = torch.empty(max(int(nb.value) // 4, 1), dtype=torch.int32, device=label.device)
-    N.check(N.lib().dcl_mask_box(N.ptr(label), n, H, W, int(value), int(padding), N.ptr(out), N.ptr(ws), C.c_int64(nb.value),
+    nb = N.query("dcl_mask_box_ws_bytes", n, H, W)
+    ws = torch.empty(max(nb // 4, 1), dtype=torch.int32, device=label.device)
+    N.check(N.lib().dcl_mask_box(N.ptr(label), n, H, W, int(value), int(padding), N.ptr(out), N.ptr(ws), nb,
                                  N.stream()), "mask_box")
     return out
 
@@ -2735,7 +2629,7 @@ def pose_rows(R0, t_gt, jitter, aug_r):
     return rows.view(np.uint8).reshape(n, POSE_ROW_BYTES)
 
 
-POSE_ROW_BYTES = 112
+POSE_ROW_BYTES = N.define("DCL_CROP_POSE_ROW_BYTES")
 POSE_ROW = [("t_gt", "<f8", (3,)), ("R0", "<f4", (3, 3)), ("j", "<f4", (3,)), ("A", "<f4", (3, 3)), ("pad", "<f4")]
 
 
@@ -2770,9 +2664,7 @@ def crop_points_posed(depth, label, rgb, frame_idx, src, cams, pose, rgb_mean, h
     counts = torch.zeros((n, 3), dtype=torch.int32, device=dev)
     rot_gt = torch.empty((n, 3, 3), dtype=torch.float32, device=dev)
     trans_gt = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    ws_ints = C.c_int64(0)
-    N.check(N.lib().dcl_crop_points_ws_ints(n, int(cap), C.byref(ws_ints)), "crop_points_ws_ints")
-    ws = torch.empty(max(int(ws_ints.value), 1), dtype=torch.int32, device=dev)
+    ws = torch.empty(max(N.query("dcl_crop_points_ws_ints", n, int(cap)), 1), dtype=torch.int32, device=dev)
     mean_a = (C.c_double * 3)(*[float(v) for v in rgb_mean])
     he_a = (C.c_float * 3)(*[float(v) for v in half_extent])
     N.check(N.lib().dcl_crop_points_posed(N.ptr(depth), N.ptr(label), N.ptr(rgb), f, H, W, rgb.shape[3], n,
@@ -2799,10 +2691,10 @@ def crop_repose_host(points, pose_row, centroid):
 
 
 # ---- the LineMOD training loader's front end (csrc/crops_train_lm.hip)
-PASTE_PLAN_INTS = 16
+PASTE_PLAN_INTS = N.define("DCL_PASTE_PLAN_INTS")
 # columns of a paste plan row (include/dclnet_hip.h: dcl_occlude_paste)
 PASTE_PLAN = ("enabled", "other", "py0", "px0", "ph", "pw", "ty0", "tx0", "th", "tw", "rep_y", "rep_x", "rmin", "rmax", "cmin", "cmax")
-POSE_ROW64_BYTES = 192
+POSE_ROW64_BYTES = N.define("DCL_CROP_POSE_ROW64_BYTES")
 POSE_ROW64 = [("t_gt", "<f8", (3,)), ("R0", "<f8", (3, 3)), ("j", "<f8", (3,)), ("A", "<f8", (3, 3))]
 
 
@@ -2929,9 +2821,7 @@ def crop_points_posed64(depth, label, rgb, frame_idx, src, cams, pose, rgb_mean,
     counts = torch.zeros((n, 3), dtype=torch.int32, device=dev)
     rot_gt = torch.empty((n, 3, 3), dtype=torch.float32, device=dev)
     trans_gt = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    ws_ints = C.c_int64(0)
-    N.check(N.lib().dcl_crop_points_ws_ints(n, int(cap), C.byref(ws_ints)), "crop_points_ws_ints")
-    ws = torch.empty(max(int(ws_ints.value), 1), dtype=torch.int32, device=dev)
+    ws = torch.empty(max(N.query("dcl_crop_points_ws_ints", n, int(cap)), 1), dtype=torch.int32, device=dev)
     mean_a = (C.c_double * 3)(*[float(v) for v in rgb_mean])
     he_a = (C.c_double * 3)(*[float(v) for v in half_extent])
     N.check(N.lib().dcl_crop_points_posed64(N.ptr(depth), N.ptr(label), N.ptr(rgb), f, H, W, rgb.shape[3], n,
@@ -2972,8 +2862,8 @@ def rulebook_transpose(nbr, n_out, cap_in):
     return inv
 
 
-CONV_PAIRS_SPLIT = 512         # include/dclnet_hip.h: DCL_CONV_PAIRS_SPLIT, the pairs of one split of sparse_conv_wgrad_pairs
-CONV_PAIRS_HEAD = 96           # DCL_CONV_PAIRS_HEAD
+CONV_PAIRS_SPLIT = N.define("DCL_CONV_PAIRS_SPLIT")  # the pairs of one split of sparse_conv_wgrad_pairs
+CONV_PAIRS_HEAD = N.define("DCL_CONV_PAIRS_HEAD")
 CONV_WGRAD_FORMS = ("rows", "pairs")
 
 
@@ -3010,17 +2900,15 @@ def conv_pairs(nbr, n_out, n_in, check=False):
     P = ConvPairs()
     P.kvol, P.n_out, P.n_in = kvol, n_out, n_in
     P.max_pairs = kvol * min(n_in, n_out)
-    ms, wb = C.c_int32(0), C.c_int64(0)
-    N.check(N.lib().dcl_conv_pairs_max_splits(P.max_pairs, kvol, C.byref(ms)), "conv_pairs_max_splits")
-    N.check(N.lib().dcl_conv_pairs_ws_bytes(kvol, n_out, C.byref(wb)), "conv_pairs_ws_bytes")
-    P.max_splits = int(ms.value)
+    P.max_splits = N.query("dcl_conv_pairs_max_splits", P.max_pairs, kvol, ctype=C.c_int32)
+    wb = N.query("dcl_conv_pairs_ws_bytes", kvol, n_out)
     P.head = torch.empty(CONV_PAIRS_HEAD, dtype=torch.int32, device=dev)
     lists = torch.empty((2, max(P.max_pairs, 1)), dtype=torch.int32, device=dev)
     P.pair_in, P.pair_out = lists[0], lists[1]
     P.split_tab = torch.empty((P.max_splits, 4), dtype=torch.int32, device=dev)
-    ws = torch.empty(max(int(wb.value) // 4, 1), dtype=torch.int32, device=dev)
+    ws = torch.empty(max(wb // 4, 1), dtype=torch.int32, device=dev)
     N.check(N.lib().dcl_conv_pairs(N.ptr(nbr), cap, kvol, n_out, n_in, P.max_pairs, N.ptr(P.head), N.ptr(P.pair_in),
-                                   N.ptr(P.pair_out), N.ptr(P.split_tab), N.ptr(ws), C.c_int64(ws.numel() * 4), N.stream()),
+                                   N.ptr(P.pair_out), N.ptr(P.split_tab), N.ptr(ws), ws.numel() * 4, N.stream()),
             "conv_pairs")
     if check:
         over = int(P.head[61])
@@ -3039,15 +2927,14 @@ def conv_pairs_host(nbr, n_out, n_in, max_pairs=None):
     kvol, cap = nbr.shape
     if max_pairs is None:
         max_pairs = kvol * min(int(n_in), int(n_out))
-    ms = C.c_int32(0)
-    N.check(N.lib().dcl_conv_pairs_max_splits(int(max_pairs), kvol, C.byref(ms)), "conv_pairs_max_splits")
+    ms = N.query("dcl_conv_pairs_max_splits", int(max_pairs), kvol, ctype=C.c_int32)
     head = np.full(CONV_PAIRS_HEAD, -1, np.int32)
     pin, pout = np.full(max(max_pairs, 1), -1, np.int32), np.full(max(max_pairs, 1), -1, np.int32)
-    tab = np.full((ms.value, 4), -1, np.int32)
+    tab = np.full((ms, 4), -1, np.int32)
     vp = lambda a: a.ctypes.data_as(C.c_void_p)
     N.check(N.lib().dcl_conv_pairs_host(vp(nbr), cap, kvol, int(n_out), int(n_in), int(max_pairs), vp(head), vp(pin), vp(pout),
                                         vp(tab)), "conv_pairs_host")
-    return dict(head=head, pair_in=pin, pair_out=pout, split_tab=tab, max_pairs=int(max_pairs), max_splits=int(ms.value))
+    return dict(head=head, pair_in=pin, pair_out=pout, split_tab=tab, max_pairs=int(max_pairs), max_splits=ms)
 
 
 def sparse_conv_wgrad_pairs(feat, dout, pairs, cin, cout):
@@ -3203,9 +3090,8 @@ def sparse_conv_backward(feat, W, dout, nbr, n_out, subm, need_dx=True, wgrad="r
     else:
         dW = torch.zeros((kvol, cin, cout), dtype=torch.float32, device=dev)
         if n_out > 0 and n_in > 0:                                 # (no input rows: no pair, dW = 0 -- and no feat pointer)
-            splits = C.c_int32(0)
-            N.check(N.lib().dcl_sparse_conv_wgrad_splits(int(n_out), C.byref(splits)), "wgrad_splits")
-            partial = torch.empty(splits.value * kvol * cin * cout, dtype=torch.float32, device=dev)
+            splits = N.query("dcl_sparse_conv_wgrad_splits", int(n_out), what="wgrad_splits", ctype=C.c_int32)
+            partial = torch.empty(splits * kvol * cin * cout, dtype=torch.float32, device=dev)
             N.check(N.lib().dcl_sparse_conv_wgrad(N.ptr(feat), N.ptr(nbr), cap, int(n_out), N.ptr(dout), cin, cout, kvol,
                                                   N.ptr(partial), N.ptr(dW), N.stream()), "sparse_conv_wgrad")
     if need_dx:
@@ -3247,10 +3133,9 @@ def three_interpolate_grad_sp(grad_out, idx, weight, m):
     idx, weight = N.i32c(idx), N.f32c(weight)
     assert tuple(idx.shape) == (n, 3) and tuple(weight.shape) == (n, 3)
     gp = torch.empty((m, c), dtype=torch.float32, device=grad_out.device)
-    ws, nb = _pn_grad_ws(N.lib().dcl_three_interpolate_grad_sp_ws_bytes, (c, n, m), grad_out.device,
-                         "three_interpolate_grad_sp")
-    N.check(N.lib().dcl_three_interpolate_grad_sp_ordered(c, n, m, N.ptr(grad_out), C.c_int64(stride), N.ptr(idx),
-                                                          N.ptr(weight), N.ptr(gp), N.ptr(ws), C.c_int64(nb), N.stream()),
+    ws, nb = _pn_grad_ws("dcl_three_interpolate_grad_sp_ws_bytes", (c, n, m), grad_out.device)
+    N.check(N.lib().dcl_three_interpolate_grad_sp_ordered(c, n, m, N.ptr(grad_out), stride, N.ptr(idx),
+                                                          N.ptr(weight), N.ptr(gp), N.ptr(ws), nb, N.stream()),
             "three_interpolate_grad_sp_ordered")
     return gp
 
@@ -3266,10 +3151,9 @@ def three_interpolate_grad_sp_atomic(grad_out, idx, weight, m):
     return gp
 
 
-def _pn_grad_ws(query, sizes, dev, what):
-    nbytes = C.c_int64(0)
-    N.check(query(*sizes, C.byref(nbytes)), what + "_ws_bytes")
-    return torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev), nbytes.value
+def _pn_grad_ws(sym, sizes, dev):
+    nbytes = N.query(sym, *sizes)
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), nbytes
 
 
 def _pn_grad_points(grad_points, shape, dev):
@@ -3287,10 +3171,9 @@ def group_points_grad(grad_out, idx, n, grad_points=None):
     B, c, npoint, ns = grad_out.shape
     assert tuple(idx.shape) == (B, npoint, ns)
     gp = _pn_grad_points(grad_points, (B, c, int(n)), grad_out.device)
-    ws, nb = _pn_grad_ws(N.lib().dcl_group_points_grad_ws_bytes, (B, c, int(n), npoint, ns), grad_out.device,
-                         "group_points_grad")
+    ws, nb = _pn_grad_ws("dcl_group_points_grad_ws_bytes", (B, c, int(n), npoint, ns), grad_out.device)
     N.check(N.lib().dcl_group_points_grad(B, c, int(n), npoint, ns, N.ptr(grad_out), N.ptr(idx), N.ptr(gp), N.ptr(ws),
-                                          C.c_int64(nb), N.stream()), "group_points_grad")
+                                          nb, N.stream()), "group_points_grad")
     return gp
 
 
@@ -3301,10 +3184,9 @@ def gather_points_grad(grad_out, idx, n, grad_points=None):
     B, c, npoint = grad_out.shape
     assert tuple(idx.shape) == (B, npoint)
     gp = _pn_grad_points(grad_points, (B, c, int(n)), grad_out.device)
-    ws, nb = _pn_grad_ws(N.lib().dcl_gather_points_grad_ws_bytes, (B, c, int(n), npoint), grad_out.device,
-                         "gather_points_grad")
+    ws, nb = _pn_grad_ws("dcl_gather_points_grad_ws_bytes", (B, c, int(n), npoint), grad_out.device)
     N.check(N.lib().dcl_gather_points_grad(B, c, int(n), npoint, N.ptr(grad_out), N.ptr(idx), N.ptr(gp), N.ptr(ws),
-                                           C.c_int64(nb), N.stream()), "gather_points_grad")
+                                           nb, N.stream()), "gather_points_grad")
     return gp
 
 
@@ -3316,10 +3198,9 @@ def three_interpolate_grad(grad_out, idx, weight, m, grad_points=None):
     B, c, n = grad_out.shape
     assert tuple(idx.shape) == (B, n, 3) and tuple(weight.shape) == (B, n, 3)
     gp = _pn_grad_points(grad_points, (B, c, int(m)), grad_out.device)
-    ws, nb = _pn_grad_ws(N.lib().dcl_three_interpolate_grad_ws_bytes, (B, c, n, int(m)), grad_out.device,
-                         "three_interpolate_grad")
+    ws, nb = _pn_grad_ws("dcl_three_interpolate_grad_ws_bytes", (B, c, n, int(m)), grad_out.device)
     N.check(N.lib().dcl_three_interpolate_grad(B, c, n, int(m), N.ptr(grad_out), N.ptr(idx), N.ptr(weight), N.ptr(gp),
-                                               N.ptr(ws), C.c_int64(nb), N.stream()), "three_interpolate_grad")
+                                               N.ptr(ws), nb, N.stream()), "three_interpolate_grad")
     return gp
 
 
@@ -3334,15 +3215,13 @@ def voxelize_bp(d_out, map_rule, n_points, mode=4):
 
 
 # ------------------------------------------------------------------------------------ Linear + ReLU stacks: training side
-WGRAD_ROWS = 512               # include/dclnet_hip.h: DCL_WGRAD_ROWS, the rows of one split of linear_wgrad / relu_bwd
+WGRAD_ROWS = N.define("DCL_WGRAD_ROWS")             # the rows of one split of linear_wgrad / relu_bwd
 
 
 def linear_wgrad_splits(M):
     """how many row splits linear_wgrad / relu_bwd cut M rows into: max(1, ceil(M / WGRAD_ROWS)), a function of M alone
     (needs no GPU)"""
-    splits = C.c_int32(0)
-    N.check(N.lib().dcl_linear_wgrad_splits(int(M), C.byref(splits)), "linear_wgrad_splits")
-    return int(splits.value)
+    return N.query("dcl_linear_wgrad_splits", int(M), ctype=C.c_int32)
 
 
 def _rows2d(t, what):
@@ -3368,8 +3247,8 @@ def linear_wgrad(a, b, out=None):
     _rows2d(out, "out")
     assert tuple(out.shape) == (P, Q)
     partial = torch.empty(linear_wgrad_splits(M) * P * Q, dtype=torch.float32, device=a.device)
-    N.check(N.lib().dcl_linear_wgrad(N.ptr(a), C.c_int64(_pitch(a)), N.ptr(b), C.c_int64(_pitch(b)), int(M), int(P), int(Q),
-                                     N.ptr(partial), N.ptr(out), C.c_int64(_pitch(out)), N.stream()), "linear_wgrad")
+    N.check(N.lib().dcl_linear_wgrad(N.ptr(a), _pitch(a), N.ptr(b), _pitch(b), int(M), int(P), int(Q),
+                                     N.ptr(partial), N.ptr(out), _pitch(out), N.stream()), "linear_wgrad")
     return out
 
 
@@ -3390,17 +3269,17 @@ def relu_bwd(h, g=None, roww=None, gpool=None, rows_per_crop=None, out=None):
         assert roww is None and gpool is None, "either g or (roww, gpool, rows_per_crop)"
         _rows2d(g, "g")
         assert tuple(g.shape) == (M, P)
-        form = (N.ptr(g), C.c_int64(_pitch(g)), None, None, C.c_int64(0), 0)
+        form = (N.ptr(g), _pitch(g), None, None, 0, 0)
     else:
         assert roww is not None and gpool is not None and rows_per_crop, "either g or (roww, gpool, rows_per_crop)"
         _rows2d(gpool, "gpool")
         rows_per_crop = int(rows_per_crop)
         assert roww.dtype == torch.float32 and roww.is_contiguous() and roww.numel() == M
         assert gpool.shape[1] == P and gpool.shape[0] * rows_per_crop >= M
-        form = (None, C.c_int64(0), N.ptr(roww), N.ptr(gpool), C.c_int64(_pitch(gpool)), rows_per_crop)
+        form = (None, 0, N.ptr(roww), N.ptr(gpool), _pitch(gpool), rows_per_crop)
     partial = torch.empty(linear_wgrad_splits(M) * P, dtype=torch.float32, device=h.device)
     db = torch.empty(P, dtype=torch.float32, device=h.device)
-    N.check(N.lib().dcl_relu_bwd(N.ptr(h), C.c_int64(_pitch(h)), *form, int(M), int(P), N.ptr(out), C.c_int64(_pitch(out)),
+    N.check(N.lib().dcl_relu_bwd(N.ptr(h), _pitch(h), *form, int(M), int(P), N.ptr(out), _pitch(out),
                                  N.ptr(partial), N.ptr(db), N.stream()), "relu_bwd")
     return out, db
 
@@ -3410,5 +3289,5 @@ def linear_pool_dma(x, Wt, bias, roww, relu=True, part=None, rows_per_crop=None,
     training forward calls, whose weights change every step (no bf16 pieces to keep in step)."""
     N.need_cuda(x, Wt, roww)
     M, K = x.shape
-    return _linear_pool(N.lib().dcl_linear_pool_fwd, "linear_pool_fwd", x, (N.ptr(Wt), C.c_int64(_pitch(Wt))), K, Wt.shape[1],
+    return _linear_pool(N.lib().dcl_linear_pool_fwd, "linear_pool_fwd", x, (N.ptr(Wt), _pitch(Wt)), K, Wt.shape[1],
                         bias, roww, relu, part, rows_per_crop, w_stride)
