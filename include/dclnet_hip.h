@@ -774,7 +774,9 @@ int dcl_three_interpolate_grad_sp_ws_bytes(int c, int n, int m, int64_t *bytes_h
 int dcl_three_interpolate_grad_sp_ordered(int c, int n, int m, const float *grad_out, int64_t grad_stride,
                                           const int32_t *idx, const float *weight, float *grad_points,
                                           void *ws, int64_t ws_bytes, dclStream_t stream);
-/* voxelize_bp (voxelize.cu:35-50): d_feats[rules[v][1+i]] += (average ? 1/n_v : 1) * d_out[v]; d_feats ZEROED (N,C).   */
+/* voxelize_bp (voxelize.cu:35-50): d_feats[rules[v][1+i]] += (average ? 1/n_v : 1) * d_out[v]; d_feats ZEROED (N,C).
+ * The adds are atomic, as in the reference: a point that several voxels list receives them in an unspecified order (its sum
+ * may differ in the last bit from call to call).  A voxelisation's rules list every point once: one add, the same bits.  */
 int dcl_voxelize_bp(const float *d_out, const int32_t *rules, float *d_feats_zeroed, int n_rows, int max_active, int c,
                     int average, dclStream_t stream);
 
