@@ -46,6 +46,8 @@ int dcl_internal_readout_one_launch(int n, const float *points_b4, const DclRead
                                     int32_t *idx, float *out, int ld, dclStream_t stream);
 int dcl_internal_readout_interpolate(int n, const DclReadoutLevels &L, const int32_t *idx, const float *dist2, float *out,
                                      int ld, dclStream_t stream);
+int dcl_internal_readout_interpolate_fold(int n, const DclReadoutLevels &L, int nfold, const int32_t *idx, const float *dist2,
+                                          float *out, int ld, float *fw, int32_t *fi, dclStream_t stream);
 int dcl_internal_sparse_avgpool_fwd(const float *feat, const DclNbrSrc &nbr, int cap, const int32_t *n_out_dev,
                                     int n_out_host, int c, int kvol, float *out, int32_t *rf, dclStream_t stream);
 int dcl_three_nn_sp_voxels(int n, int m, const float *unknown, const int32_t *known_indices, float ve, float off,
@@ -656,6 +658,30 @@ static int point_features(int n, const float *points_b4, int batch, int S, int V
     col += c;
   }
   return 0;
+}
+
+// The read-out with its nfold deepest levels left to the GEMM that consumes it (dcl_linear_split_gather_fwd): always the two
+// launches -- all searches (the lanes per query follow n as in dcl_point_features: the same keys, the same bits), then the
+// interpolation of the first 4 - nfold levels together with the folded levels' weights and neighbour rows.
+DCL_API int dcl_point_features_fold(int n, const float *points_b4, int batch, int S, int V0, void *ws, const int32_t *counts_host,
+                                    const int32_t *channels_host, const float *const *level_feats, const float *voxel_extent_host,
+                                    float offset, int nfold, float *out, int ld, float *fw, int32_t *fi, void *tmp,
+                                    int64_t tmp_bytes, dclStream_t stream) {
+  GeoLayout L;
+  DCL_CHECK_ARG(n >= 0 && points_b4 && ws && counts_host && channels_host && level_feats && voxel_extent_host && out && fw && fi &&
+                tmp && (nfold == 1 || nfold == 2) && make_geo_layout(batch, S, V0, &L));
+  if (n == 0) return 0;
+  DclReadoutLevels R;
+  fill_readout_levels(L, ws, channels_host, level_feats, voxel_extent_host, &R);
+  const size_t blk = align_up((size_t)n * 48);
+  DCL_CHECK_ARG(tmp_bytes >= (int64_t)(2 * blk));
+  DCL_CHECK_ARG(dcl_internal_readout_fused_ok(R, R.col[kLevels - 1] + R.c[kLevels - 1], true));
+  DCL_CHECK_ARG(ld % 4 == 0 && R.col[kLevels - nfold] <= ld);
+  float *d4 = at<float>(tmp, 0);
+  int32_t *i4 = at<int32_t>(tmp, blk);
+  int rc = dcl_internal_readout_neighbours(n, points_b4, R, batch, offset, d4, i4, stream);
+  if (rc) return rc;
+  return dcl_internal_readout_interpolate_fold(n, R, nfold, i4, d4, out, ld, fw, fi, stream);
 }
 
 // ---- the read-out in two halves (searches | interpolation), see include/dclnet_hip.h

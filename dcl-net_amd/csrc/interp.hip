@@ -306,11 +306,16 @@ __global__ __launch_bounds__(256) void k_three_nn_grid_levels(int n, const float
 // read once, much later, by the disengage GEMM: no point in allocating them in L2).  Same arithmetic, same bits.
 constexpr int kInterpPts = 32;
 // one block of kInterpPts points (p0 ..) by NT threads: weights into LDS, then the 480 channels
-template <int NT>
+// FOLD (dcl_point_features_fold): the FOLD deepest levels are not interpolated -- their normalised weights and neighbour rows,
+// the same values the interpolation would use, leave as fw / fi [FOLD][n][3] for the GEMM that folds them
+// (csrc/linear_split.hip, EPI 4) -- and `out` gets the columns of the first 4 - FOLD levels only.
+template <int NT, int FOLD = 0>
 __device__ __forceinline__ void interpolate_block(int n, int p0, const DclReadoutLevels &L, const int32_t *__restrict__ idx,
                                                   const float *__restrict__ dist2, float *__restrict__ out, int ld,
-                                                  float (*s_w)[3], int32_t (*s_i)[3]) {
-  const int q0 = L.c[0] >> 2, q1 = q0 + (L.c[1] >> 2), q2 = q1 + (L.c[2] >> 2), qn = q2 + (L.c[3] >> 2);
+                                                  float (*s_w)[3], int32_t (*s_i)[3], float *__restrict__ fw = nullptr,
+                                                  int32_t *__restrict__ fi = nullptr) {
+  const int q0 = L.c[0] >> 2, q1 = q0 + (L.c[1] >> 2), q2 = q1 + (L.c[2] >> 2);
+  const int qn = FOLD == 2 ? q1 : FOLD == 1 ? q2 : q2 + (L.c[3] >> 2);
   if (threadIdx.x < kInterpPts * 4) {
     const int pl = threadIdx.x / 4, m = threadIdx.x & 3, p = p0 + pl;
     if (p < n) {
@@ -318,8 +323,14 @@ __device__ __forceinline__ void interpolate_block(int n, int p0, const DclReadou
       const float r0 = 1.0f / (sqrtf(dist2[o]) + 1e-8f), r1 = 1.0f / (sqrtf(dist2[o + 1]) + 1e-8f),
                   r2 = 1.0f / (sqrtf(dist2[o + 2]) + 1e-8f);
       const float norm = (r0 + r1) + r2;
-      s_w[threadIdx.x][0] = r0 / norm; s_w[threadIdx.x][1] = r1 / norm; s_w[threadIdx.x][2] = r2 / norm;
-      s_i[threadIdx.x][0] = idx[o]; s_i[threadIdx.x][1] = idx[o + 1]; s_i[threadIdx.x][2] = idx[o + 2];
+      if (FOLD > 0 && m >= 4 - FOLD) {
+        const size_t f = ((size_t)(m - (4 - FOLD)) * n + p) * 3;
+        fw[f] = r0 / norm; fw[f + 1] = r1 / norm; fw[f + 2] = r2 / norm;
+        fi[f] = idx[o]; fi[f + 1] = idx[o + 1]; fi[f + 2] = idx[o + 2];
+      } else {
+        s_w[threadIdx.x][0] = r0 / norm; s_w[threadIdx.x][1] = r1 / norm; s_w[threadIdx.x][2] = r2 / norm;
+        s_i[threadIdx.x][0] = idx[o]; s_i[threadIdx.x][1] = idx[o + 1]; s_i[threadIdx.x][2] = idx[o + 2];
+      }
     }
   }
   __syncthreads();
@@ -345,15 +356,19 @@ __device__ __forceinline__ void interpolate_block(int n, int p0, const DclReadou
     __builtin_nontemporal_store(v, reinterpret_cast<f4 *>(out + (size_t)(p0 + pl) * ld + L.col[m]) + q);
   }
 }
+// nfold (uniform): 0 = all four levels; 1 / 2 = the folded forms (interpolate_block: FOLD)
 __global__ __launch_bounds__(256) void k_three_interpolate_levels(int n, const DclReadoutLevels L,
                                                                   const int32_t *__restrict__ idx,
                                                                   const float *__restrict__ dist2, float *__restrict__ out,
-                                                                  int ld) {
+                                                                  int ld, int nfold, float *__restrict__ fw,
+                                                                  int32_t *__restrict__ fi) {
   __shared__ float s_w[kInterpPts * 4][3];
   __shared__ int32_t s_i[kInterpPts * 4][3];
   for (int p0 = blockIdx.x * kInterpPts; p0 < n; p0 += gridDim.x * kInterpPts) {
     __syncthreads();
-    interpolate_block<256>(n, p0, L, idx, dist2, out, ld, s_w, s_i);
+    if (nfold == 0) interpolate_block<256>(n, p0, L, idx, dist2, out, ld, s_w, s_i);
+    else if (nfold == 1) interpolate_block<256, 1>(n, p0, L, idx, dist2, out, ld, s_w, s_i, fw, fi);
+    else interpolate_block<256, 2>(n, p0, L, idx, dist2, out, ld, s_w, s_i, fw, fi);
   }
 }
 
@@ -902,7 +917,19 @@ int dcl_internal_readout_interpolate(int n, const DclReadoutLevels &L, const int
   const long long quads = (long long)n * ((L.c[0] + L.c[1] + L.c[2] + L.c[3]) / 4);
   (void)quads;
   hipLaunchKernelGGL(k_three_interpolate_levels, dim3(dcl_grid_1d(n, kInterpPts, 256 * 32)), dim3(256), 0,
-                     (hipStream_t)stream, n, L, idx, dist2, out, ld);
+                     (hipStream_t)stream, n, L, idx, dist2, out, ld, 0, (float *)nullptr, (int32_t *)nullptr);
+  DCL_LAUNCH_CHECK();
+  return 0;
+}
+
+// the interpolation of the first 4 - nfold levels + the weights / neighbour rows of the others (dcl_point_features_fold);
+// L.col / L.c of the written levels must fit ld (the caller checks: dcl_internal_readout_fused_ok on those levels)
+int dcl_internal_readout_interpolate_fold(int n, const DclReadoutLevels &L, int nfold, const int32_t *idx, const float *dist2,
+                                          float *out, int ld, float *fw, int32_t *fi, dclStream_t stream) {
+  DCL_CHECK_ARG(n > 0 && idx && dist2 && out && fw && fi && (nfold == 1 || nfold == 2) && ld % 4 == 0);
+  for (int m = 0; m < 4; ++m) DCL_CHECK_ARG(L.c[m] > 0 && L.c[m] % 4 == 0 && L.col[m] % 4 == 0 && (m >= 4 - nfold || L.col[m] + L.c[m] <= ld));
+  hipLaunchKernelGGL(k_three_interpolate_levels, dim3(dcl_grid_1d(n, kInterpPts, 256 * 32)), dim3(256), 0, (hipStream_t)stream, n, L,
+                     idx, dist2, out, ld, nfold, fw, fi);
   DCL_LAUNCH_CHECK();
   return 0;
 }

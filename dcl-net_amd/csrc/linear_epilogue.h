@@ -49,6 +49,83 @@ __device__ __forceinline__ void lin_epi_store(const f32x16 (&acc)[MB][NB], const
   }
 }
 
+// EPI 4 (split core):  y = act(acc + bias + sum over the folded levels l, ascending, and i = 0, 1, 2 of fw[l][row][i] * G_l[fi[l][row][i]][col])
+// -- one fmaf chain per output in exactly that order, so the bits are the same on every run.  The read-out's deep levels enter the
+// first disengage layer this way: G_l = F_l W[col_l ...] has a few thousand rows (a few hundred per crop: they stay in the L2 of
+// the XCD that owns the row block), and three fused multiply-adds on its rows replace the level's K columns of the big GEMM.
+// rw: the wave's 64 rows x kFoldMax levels x 8 dwords in LDS, {w0, w1, w2, -, i0, i1, i2, -} per row and level (staged by the
+// kernel).  A row's weights and indices are uniform over a lane half: LDS broadcasts; a load covers 128 contiguous bytes of one row
+// of G_l per lane half, the shape of the stores.
+// The loads are what the epilogue waits for (a row's twelve per level, issued and awaited row by row, made it a chain of 64 L2
+// round trips per tile), so it is a software pipeline in straight-line code: a step = 24 loads (one row of two levels, two rows of
+// one), the next step's loads are issued before this step's sums and stores, and nothing is predicated -- NFOLD and WHOLE are
+// template arguments, and a ragged tile loads from its last valid column (rows >= M carry a valid row's indices) and only
+// predicates its stores.
+constexpr int kFoldMax = 2;
+template <bool NT, int NFOLD, bool WHOLE, int MB, int NB, class Args>
+__device__ __forceinline__ void lin_epi_gather_store(const f32x16 (&acc)[MB][NB], const Args &a, const float *rw, int wrow0, int wcol0,
+                                                     int r, int h) {
+  static_assert(NFOLD >= 1 && NFOLD <= kFoldMax, "folded levels");
+  constexpr int RS = NFOLD == 1 ? 2 : 1, STEPS = MB * 16 / RS;             // rows per step; steps
+  float *__restrict__ y = a.y;
+  float bias[NB];
+  int gcol[NB];
+  bool cok[NB];
+#pragma unroll
+  for (int n = 0; n < NB; ++n) {
+    const int co = wcol0 + n * 32 + r;
+    cok[n] = WHOLE || co < a.N;
+    bias[n] = (a.bias && cok[n]) ? a.bias[co] : 0.0f;
+    gcol[n] = WHOLE ? co : min(co, a.N - 1);
+  }
+  float q[2][RS][NFOLD][3][NB], wq[2][RS][NFOLD][3];
+  auto fetch = [&](int s, int buf) {
+#pragma unroll
+    for (int j = 0; j < RS; ++j) {
+      const int t = s * RS + j, rl = (t >> 4) * 32 + rowmap(t & 15, h);
+#pragma unroll
+      for (int l = 0; l < NFOLD; ++l) {
+        const float4 w4 = *reinterpret_cast<const float4 *>(rw + (l * 64 + rl) * 8);
+        const int4 i4 = *reinterpret_cast<const int4 *>(rw + (l * 64 + rl) * 8 + 4);
+        const int rows3[3] = {i4.x, i4.y, i4.z};
+        wq[buf][j][l][0] = w4.x; wq[buf][j][l][1] = w4.y; wq[buf][j][l][2] = w4.z;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          const float *__restrict__ g = a.G[l] + (size_t)rows3[i] * a.ldg[l];
+#pragma unroll
+          for (int n = 0; n < NB; ++n) q[buf][j][l][i][n] = g[gcol[n]];
+        }
+      }
+    }
+  };
+  fetch(0, 0);
+#pragma unroll
+  for (int s = 0; s < STEPS; ++s) {
+    if (s + 1 < STEPS) fetch(s + 1, (s + 1) & 1);
+#pragma unroll
+    for (int j = 0; j < RS; ++j) {
+      const int t = s * RS + j, m = t >> 4, e = t & 15;
+      const int orow = wrow0 + m * 32 + rowmap(e, h);
+#pragma unroll
+      for (int n = 0; n < NB; ++n) {
+        float v = acc[m][n][e] + bias[n];
+#pragma unroll
+        for (int l = 0; l < NFOLD; ++l)
+#pragma unroll
+          for (int i = 0; i < 3; ++i) v = __fmaf_rn(wq[s & 1][j][l][i], q[s & 1][j][l][i][n], v);
+        if (a.relu) v = fmaxf(v, 0.0f);
+        float *yp = y + (size_t)orow * a.ldy + (wcol0 + n * 32 + r);
+        if constexpr (WHOLE) {
+          if constexpr (NT) __builtin_nontemporal_store(v, yp);
+          else *yp = v;
+        } else {
+          if (orow < a.M && cok[n]) *yp = v;
+        }
+      }
+    }
+  }
+}
+
 // EPI 1:  a wave's weighted column sums  sum over its 32 MB rows j of  w[j] * act(acc[j][c] + bias[c])  -- in registers, one
 // fmaf chain per lane half over its rows in register order, then half 0 + half 1 -- written by lane half 0 to red_row[column
 // inside the tile].  wts: the tile's row weights in LDS; wrow / wcol: the wave's first row / column INSIDE the tile; col0: the

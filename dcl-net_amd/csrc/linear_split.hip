@@ -46,6 +46,13 @@ struct LinSplitArgs {
   const float *b3;
   long long ldp;
   int xcd_remap;
+  // EPI 4: the folded read-out levels (linear_epilogue.h: lin_epi_gather_store)
+  const float *fw;       // [nfold][fstride]: three weights per row
+  const int32_t *fi;     // [nfold][fstride]: three rows of G[l] per row
+  long long fstride;
+  const float *G[kFoldMax];
+  long long ldg[kFoldMax];
+  int nfold;
 };
 
 // weight pieces in tile order: [K/16 chunks][ceil(N/128) column tiles][3 pieces][128 columns][2 halves of the 16 k][8 bf16], the
@@ -238,6 +245,36 @@ __global__ __launch_bounds__(256, 2) void k_linear_split(const LinSplitArgs a) {
       const bool whole = row0 + kSpBM <= a.M && col0 + kSpBN <= a.N;
       // (whole tiles leave by non-temporal stores: an activation of hundreds of MB, read once by the next layer, from HBM anyway)
       lin_epi_store<true>(acc, a, whole, row0 + wave * 64, col0, r, h);
+    } else if constexpr (EPI == 4) {
+      // folded read-out levels: the wave's 64 rows of fw / fi go through its OWN x rows of stage 0 (4 KiB that only this wave
+      // DMAs into and reads; its reads of the last chunk are done and it issues the next tile's DMA itself): no barrier
+      float *rw = reinterpret_cast<float *>(sp_lds + wave * 64 * 64);
+      static_assert(kFoldMax * 64 * 8 * 4 <= 64 * 64, "a wave's weights and indices fit its x rows of one stage");
+      {
+        const int row = min(row0 + wave * 64 + lane, a.M - 1);             // (rows >= M: a valid row's, never stored)
+#pragma unroll
+        for (int l = 0; l < kFoldMax; ++l) {
+          if (l >= a.nfold) break;
+          const size_t o = (size_t)l * a.fstride + (size_t)row * 3;
+          float4 w4;
+          int4 i4;
+          w4.x = a.fw[o]; w4.y = a.fw[o + 1]; w4.z = a.fw[o + 2]; w4.w = 0.0f;
+          i4.x = a.fi[o]; i4.y = a.fi[o + 1]; i4.z = a.fi[o + 2]; i4.w = 0;
+          *reinterpret_cast<float4 *>(rw + (l * 64 + lane) * 8) = w4;
+          *reinterpret_cast<int4 *>(rw + (l * 64 + lane) * 8 + 4) = i4;
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the wave's own writes, read back by its other lanes
+      __builtin_amdgcn_wave_barrier();
+      const bool whole = row0 + kSpBM <= a.M && col0 + kSpBN <= a.N;
+      const int wrow0 = row0 + wave * 64;
+      if (a.nfold == 1) {
+        if (whole) lin_epi_gather_store<true, 1, true>(acc, a, rw, wrow0, col0, r, h);
+        else lin_epi_gather_store<true, 1, false>(acc, a, rw, wrow0, col0, r, h);
+      } else {
+        if (whole) lin_epi_gather_store<true, 2, true>(acc, a, rw, wrow0, col0, r, h);
+        else lin_epi_gather_store<true, 2, false>(acc, a, rw, wrow0, col0, r, h);
+      }
     } else if constexpr (EPI == 3) {
       // attention-V epilogue: the activation leaves the kernel AS the three bf16 pieces the attention's P.V product reads
       // (csrc/dense.hip: k_cross_attn_split; layout of k_attn_split_v, which this makes unnecessary for these channels) and is
@@ -363,6 +400,26 @@ DCL_API int dcl_linear_split_pool_fwd(const float *x, int64_t ldx, const void *p
   LinSplitArgs a{x, (const unsigned char *)planes, bias, nullptr, ldx, 0, M, N, K, relu, roww, rows_per_crop, w_stride, part, nullptr, ldp,
                  (int)g_sp_xcd};
   int rc = launch_linear_split<1>(a, (hipStream_t)stream);
+  if (rc) return rc;
+  DCL_LAUNCH_CHECK();
+  return 0;
+}
+
+DCL_API int dcl_linear_split_gather_fwd(const float *x, int64_t ldx, const void *planes, const float *bias, int nfold, const float *fw,
+                                        const int32_t *fi, int64_t level_stride, const float *const *G_host, const int64_t *ldg_host,
+                                        float *y, int64_t ldy, int M, int N, int K, int relu, dclStream_t stream) {
+  DCL_CHECK_ARG(M >= 0 && N > 0 && K > 0 && x && planes && y && ldx >= K && ldy >= N);
+  DCL_CHECK_ARG(nfold >= 1 && nfold <= kFoldMax && fw && fi && G_host && ldg_host && level_stride >= 3 * (int64_t)M);
+  for (int l = 0; l < nfold; ++l) DCL_CHECK_ARG(G_host[l] && ldg_host[l] >= N);
+  DCL_CHECK_ARG(lin_split_ok(x, ldx, planes, K));
+  if (M == 0) return 0;
+  LinSplitArgs a{x, (const unsigned char *)planes, bias, y, ldx, ldy, M, N, K, relu, nullptr, 1, 0, nullptr, nullptr, 0, (int)g_sp_xcd};
+  a.fw = fw;
+  a.fi = fi;
+  a.fstride = level_stride;
+  a.nfold = nfold;
+  for (int l = 0; l < nfold; ++l) { a.G[l] = G_host[l]; a.ldg[l] = ldg_host[l]; }
+  int rc = launch_linear_split<4>(a, (hipStream_t)stream);
   if (rc) return rc;
   DCL_LAUNCH_CHECK();
   return 0;

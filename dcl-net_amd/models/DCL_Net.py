@@ -449,6 +449,16 @@ class Network(nn.Module):
                 ops.prepare_linear(W1t)
                 for Wt, _ in second:
                     ops.prepare_linear(Wt)
+                # the first layer with the read-out's deepest levels folded through it (ops.READOUT_FOLD, _readout): per number
+                # of folded levels the rows of W1t the read-out still feeds, W1t[:K0], and the folded levels' row blocks
+                # W1t[col_m : col_m + c_m], which turn a level's few thousand rows into G_m = F_m @ W1t[col_m ...] once per
+                # call.  Row-slice VIEWS of W1t, prepared like it -- and kept here: the registry holds weak references
+                col = np.cumsum((0,) + ops.BACKBONE_CHANNELS[2::2]).tolist()
+                f["dis_fold_" + side] = {nf: (W1t[:col[4 - nf]], [W1t[col[m]:col[m + 1]] for m in range(4 - nf, 4)])
+                                         for nf in (1, 2)}
+                for W0, blocks in f["dis_fold_" + side].values():
+                    for Wt in [W0] + blocks:
+                        ops.prepare_linear(Wt)
             for name in ("regressor_conf", "regressor_conf_bi", "regressor_Xo", "regressor_Yc"):
                 for Wt, _ in f[name][:2]:
                     ops.prepare_linear(Wt)
@@ -664,11 +674,33 @@ class Network(nn.Module):
                               d["v2p_maps"].to(dev, non_blocking=True).int().contiguous(), occ[s])
                 pb4[s] = torch.cat([self._crop_ids(dev, b, bc, npts[s]), side_in[s][0][:, 4:7]], 1)   # (crop in its chunk, xyz)
                 vox[s] = ops.voxelize_fp(side_in[s][0], side_in[s][1], self.voxelization_mode)   # all crops at once
-                pf[s] = torch.empty((b * npts[s], 480), dtype=torch.float32, device=dev)   # read on `main`
+                # (a folded side's read-out writes the first levels' columns only: _readout_fold, readout() below)
+                nf = self._readout_fold(b * npts[s], K)
+                pf[s] = torch.empty((b * npts[s], ops.READOUT_FOLD_K0[nf] if nf else 480), dtype=torch.float32, device=dev)   # read on `main`
+                if nf and ops.prepared_linear(f["dis_fold_" + dis_of[s]][nf][0], pf[s]) is None:
+                    nf, pf[s] = 0, torch.empty((b * npts[s], 480), dtype=torch.float32, device=dev)
+                fold[s] = nf
             if not single:
                 pf[s].record_stream(main)
                 side_in[s][0].record_stream(main)                      # `pts` below is handed to the caller
             pts[s] = side_in[s][0][:, 4:7].reshape(b, npts[s], 3)
+        dis_of = {"inp": "Xc", "tmp": "Yo"}
+        fold, folded = {}, {}
+        def readout(s, run, rows=slice(None)):
+            """a side's read-out, on its own stream behind its features.  A folded side (fold[s] levels; the whole batch in this
+            one call) first turns each folded level into G = F @ W1t[the level's rows] -- a few thousand rows -- and its read-out
+            hands the level's interpolation weights and neighbour rows to the first disengage GEMM instead of its channels"""
+            nf = fold[s]
+            if not nf:
+                run.point_features(pb4[s][rows], extents, off, out=pf[s][rows])
+                return
+            W0, blocks = f["dis_fold_" + dis_of[s]][nf]
+            G = [ops.linear(run.levels[4 - nf + j], Wt) for j, Wt in enumerate(blocks)]
+            _, fw, fi = run.point_features_fold(pb4[s], extents, off, nf, out=pf[s])
+            folded[s] = (fw, fi, G, W0)
+            if not single:
+                for t in [fw, fi] + G:
+                    t.record_stream(main)
         mark("geometry issued")
         unit = self.unit_voxel_extent
         assert unit[0] == unit[1] == unit[2], "anisotropic voxels: use fused=False"
@@ -702,13 +734,13 @@ class Network(nn.Module):
                 if not single:
                     for t in runs["tmp", 0].levels:
                         t.record_stream(s_tmp)
-                runs["inp", 0].point_features(pb4["inp"], extents, off, out=pf["inp"])
+                readout("inp", runs["inp", 0])
                 done["inp", 0] = torch.cuda.Event()
                 done["inp", 0].record(s_inp)
             with torch.cuda.stream(s_tmp):
                 if not single:
                     s_tmp.wait_event(feat_done)
-                runs["tmp", 0].point_features(pb4["tmp"], extents, off, out=pf["tmp"])
+                readout("tmp", runs["tmp", 0])
                 done["tmp", 0] = torch.cuda.Event()
                 done["tmp", 0].record(s_tmp)
         paired = bool(done)
@@ -740,7 +772,7 @@ class Network(nn.Module):
                 for c in range(K):
                     rows = slice(c * bc * n, (c + 1) * bc * n)
                     runs[side, c].features(vox[side], *f[bb + "_ptrs"])
-                    runs[side, c].point_features(pb4[side][rows], extents, off, out=pf[side][rows])
+                    readout(side, runs[side, c], rows)
                     done[side, c] = torch.cuda.Event()
                     done[side, c].record(sstream[side])
         act = {}
@@ -760,7 +792,7 @@ class Network(nn.Module):
                     continue
                 main.wait_event(done[key, c])
                 rows = slice(c * bc * npts[key], (c + 1) * bc * npts[key])
-                self._disengage(f, side, pf[key][rows], act, rows)
+                self._disengage(f, side, pf[key][rows], act, rows, fold=folded.get(key))
         for st in sstream.values():
             main.wait_stream(st)
         # (launch by launch too, the tail's two directions run side by side -- on the observed side's stream, idle by now --
@@ -847,11 +879,29 @@ class Network(nn.Module):
         return {"fuse2": fuse_buf, "conf_in2": conf_in, "Yop2": fuse_buf[:, 256:], "Yom2": conf_in[:, 64:],
                 "Yop1": v1, "Yom1": new(64), "planes1": planes}
 
-    def _disengage(self, f, side, pf_rows, act, rows=slice(None)):
+    def _readout_fold(self, n, K):
+        """how many of the read-out's deepest levels a side of n points folds through its first disengage GEMM (ops.READOUT_FOLD;
+        0 = none: today's route and today's bits).  By shape only: inference, the whole batch in one call (K = 1 chunk), the
+        read-out in its two-launch form; the caller adds that the first layer takes the split-bf16 core (ops.prepared_linear)"""
+        nf = ops.READOUT_FOLD
+        if nf not in (1, 2) or self.mode != "test" or K != 1 or n < ops.READOUT_FOLD_MIN_POINTS:
+            return 0
+        return nf
+
+    def _disengage(self, f, side, pf_rows, act, rows=slice(None), fold=None):
         """the four disengage stacks of one side on a block of points: one shared 480->1024 GEMM (BN folded), then the four
-        second layers, written into rows `rows` of the activation buffers in `act`"""
+        second layers, written into rows `rows` of the activation buffers in `act`.  fold = (fw, fi, G, W0) of a folded read-out
+        (_forward_fused: readout): pf_rows then holds the first levels' columns only, and the first layer is the GEMM over them
+        with the folded levels' sums as its epilogue"""
         W1t, t1, second = f["dis_" + side]
-        H = self._lin_relu(pf_rows, W1t, t1)                                # (rows, 1024): 4 stacks at once
+        if fold is not None:
+            fw, fi, G, W0 = fold
+            sw = ops.prepared_linear(W0, pf_rows)
+            if sw is None:
+                raise RuntimeError("folded read-out: the first disengage layer of %s no longer takes the split-bf16 core" % side)
+            H = ops.linear_split_gather(pf_rows, sw, t1, fw, fi, G, relu=True)
+        else:
+            H = self._lin_relu(pf_rows, W1t, t1)                            # (rows, 1024): 4 stacks at once
         if pf_rows.shape[0] <= self.GROUP_ROWS:                             # a handful of crops: the four layers in ONE launch
             ops.linear_group([(H[:, 256 * j:256 * (j + 1)], second[j][0], second[j][1], True, act[side + tag][rows])
                               for j, (tag, _) in enumerate(self._DIS_TAGS)])

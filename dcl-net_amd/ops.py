@@ -584,6 +584,29 @@ class BackboneRun(object):
                                            out.stride(0), N.ptr(tmp), tmp_bytes, N.stream()), "point_features")
         return out
 
+    def point_features_fold(self, points_b4, voxel_extents, offset, nfold, out=None):
+        """point_features with its nfold (1 or 2) deepest levels left to the GEMM that consumes the read-out (linear_split_gather):
+        -> (out (n, 224 or 96): exactly the first columns of point_features; fw (nfold, n, 3) float32: the folded levels'
+        normalised interpolation weights; fi (nfold, n, 3) int32: their neighbour rows), folded levels ascending.  Always the
+        two-launch read-out (csrc/backbone.hip: dcl_point_features_fold)."""
+        assert nfold in (1, 2)
+        n = points_b4.shape[0]
+        dev = points_b4.device
+        K0 = sum(BACKBONE_CHANNELS[2 * m + 2] for m in range(4 - nfold))
+        if out is None:
+            out = torch.empty((n, K0), dtype=torch.float32, device=dev)
+        assert out.shape == (n, K0) and out.dtype == torch.float32 and out.stride(1) == 1
+        fw = torch.empty((nfold, n, 3), dtype=torch.float32, device=dev)
+        fi = torch.empty((nfold, n, 3), dtype=torch.int32, device=dev)
+        tmp_bytes = 2 * (((n * 48) + 255) // 256 * 256)                       # dist2 + idx of the 4 levels
+        tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=dev)
+        ve = (C.c_float * 4)(*[float(v) for v in voxel_extents])
+        N.check(N.lib().dcl_point_features_fold(n, N.ptr(points_b4), self.batch, self.S, self.V0, N.ptr(self.ws), self.ccounts,
+                                                self.chan, _ptr_array(self.levels), ve, offset, int(nfold), N.ptr(out),
+                                                out.stride(0), N.ptr(fw), N.ptr(fi), N.ptr(tmp), tmp_bytes, N.stream()),
+                "point_features_fold")
+        return out, fw, fi
+
     def point_neighbours(self, points_b4, voxel_extents, offset):
         """first half of point_features: the four 3-NN searches (need geometry + counts only, not the level features).
         Returns (dist2, idx), each (4, n, 3)."""
@@ -1988,6 +2011,33 @@ def linear_split(x, sw, bias=None, relu=False, out=None):
     out = _layer_io(x, K, n, bias, out)
     N.check(N.lib().dcl_linear_split_fwd(N.ptr(x), _pitch(x), N.ptr(sw.planes), N.ptr(bias), N.ptr(out), _pitch(out),
                                          int(M), int(n), int(K), int(bool(relu)), N.stream()), "linear_split_fwd")
+    return out
+
+
+READOUT_FOLD = 2               # deepest read-out levels folded through the first disengage GEMM: 0 = none (read-out of 480 columns, K = 480
+                               # GEMM), 1 = the 256-channel level, 2 = the 128- and 256-channel levels (same-job A/B, tools/ab_readout_fold.py,
+                               # profiles/readout_fold.txt: stress step 14.63 / 13.77 / 13.40 ms for 0 / 1 / 2)
+READOUT_FOLD_MIN_POINTS = 40961   # ... for sides of at least this many points (below: the one-launch read-out, which is not folded)
+READOUT_FOLD_K0 = {1: 224, 2: 96}                      # columns the read-out still writes = K of the first layer's GEMM
+
+
+def linear_split_gather(x, sw, bias, fw, fi, G, relu=False, out=None):
+    """act(x @ sw.Wt + bias + sum_l sum_i fw[l, m, i] * G[l][fi[l, m, i]]) per row m, on the split-bf16 core with the sums over
+    the folded levels as its epilogue (csrc/linear_split.hip, EPI 4): per output ONE fmaf chain, levels ascending, i = 0, 1, 2.
+    fw (L, M, 3) float32, fi (L, M, 3) int32, G: L = 1 or 2 matrices (R_l, N) with dense rows of any pitch.  Every fi[l] must
+    index inside G[l] (not checked)."""
+    N.need_cuda(x, fw, fi, *G)
+    M, K, n = x.shape[0], sw.K, sw.n
+    out = _layer_io(x, K, n, bias, out)
+    L = len(G)
+    assert L in (1, 2) and fw.shape == (L, M, 3) and fi.shape == (L, M, 3) and fw.is_contiguous() and fi.is_contiguous()
+    assert fw.dtype == torch.float32 and fi.dtype == torch.int32
+    for g in G:
+        assert g.dim() == 2 and g.shape[1] == n and g.dtype == torch.float32 and (g.stride(1) == 1 or n == 1) and g.shape[0] > 0
+    N.check(N.lib().dcl_linear_split_gather_fwd(N.ptr(x), _pitch(x), N.ptr(sw.planes), N.ptr(bias), L, N.ptr(fw), N.ptr(fi),
+                                                3 * int(M), _ptr_array(list(G)), (C.c_int64 * L)(*[_pitch(g) for g in G]),
+                                                N.ptr(out), _pitch(out), int(M), int(n), int(K), int(bool(relu)), N.stream()),
+            "linear_split_gather_fwd")
     return out
 
 

@@ -37,7 +37,8 @@ const char *dcl_last_error(void);
  *      new: dcl_linear_dma_fwd, dcl_linear_pool_fwd, dcl_linear_rowdot_fwd, dcl_conf_softmax, dcl_pool_finish2,
  *      dcl_linear_split_weight(_bytes), dcl_linear_split_fwd / _pool_fwd / _rowdot_fwd / _vpieces_fwd, dcl_cross_attention_ws3
  *      (+ _planes_bytes, _split_crops); later additions (no change to existing entries): dcl_conv_split_weight(_bytes),
- *      dcl_sparse_conv_fwd_sides, dcl_backbone_features_split / _cap_split / _pair_split */
+ *      dcl_sparse_conv_fwd_sides, dcl_backbone_features_split / _cap_split / _pair_split, dcl_point_features_fold,
+ *      dcl_linear_split_gather_fwd */
 #define DCL_ABI_VERSION 2
 int dcl_abi_version(void);
 
@@ -332,6 +333,16 @@ int dcl_point_features(int n, const float *points_b4, int batch, int S, int V0, 
                        const int32_t *counts_host, const int32_t *channels_host,
                        const float *const *level_feats_host, const float *voxel_extent_host, float offset,
                        float *out, int ld, void *tmp, int64_t tmp_bytes, dclStream_t stream);
+/* dcl_point_features with its nfold (1 or 2) deepest levels left to the GEMM that consumes the read-out
+ * (dcl_linear_split_gather_fwd): out (n, ld) gets the columns of the first 4 - nfold levels only -- bit for bit the first
+ * columns of dcl_point_features -- and for folded level l = 0 .. nfold - 1 (level 4 - nfold + l) the call returns
+ * fw[l][n][3], the normalised inverse-distance weights the interpolation would have used (the same expressions, the same
+ * bits), and fi[l][n][3], the rows of that level's features they weigh.  Always two launches (all searches, then the
+ * interpolation); tmp >= 2*align256(48n) bytes.                                                                      */
+int dcl_point_features_fold(int n, const float *points_b4, int batch, int S, int V0, void *ws, const int32_t *counts_host,
+                            const int32_t *channels_host, const float *const *level_feats_host,
+                            const float *voxel_extent_host, float offset, int nfold, float *out, int ld, float *fw,
+                            int32_t *fi, void *tmp, int64_t tmp_bytes, dclStream_t stream);
 /* The same read-out in two halves, so that a caller can overlap the searches with the convolutions: the 3-NN searches
  * need the level geometry only (dcl_backbone_geometry), the interpolation needs the level features.
  * dist2 / idx: 4 level blocks of n*3 entries each (level-major).  Results are identical to dcl_point_features.
@@ -609,6 +620,18 @@ int dcl_linear_split_fwd(const float *x, int64_t ldx, const void *planes, const 
 int dcl_linear_split_pool_fwd(const float *x, int64_t ldx, const void *planes, const float *bias, const float *roww,
                               int rows_per_crop, int64_t w_stride, float *part, int64_t ldp, int M, int N, int K, int relu,
                               dclStream_t stream);
+/* dcl_linear_split_fwd with gathered rows added in its epilogue (a read-out whose deepest levels are folded through the layer:
+ * dcl_point_features_fold):
+ *     y[m][c] = act(fma(fw[l][m][2], G_l[fi[l][m][2]][c], fma(fw[l][m][1], G_l[fi[l][m][1]][c], fma(fw[l][m][0], G_l[fi[l][m][0]][c], ...
+ *               (x Wt)[m][c] + bias[c]))))            levels l = 0 .. nfold - 1 in ascending order, nfold = 1 or 2
+ * -- one fused-multiply-add chain per output in that fixed order, no atomics: the same bits on every run.  fw / fi: level l's
+ * three weights / rows of row m at element l * level_stride + 3 m (level_stride >= 3 M); G_host[l]: (R_l, N) fp32 with row pitch
+ * ldg_host[l] >= N (both arrays are host memory).  THE CALLER'S CONTRACT: every fi[l][m][i], m < M, is a row of G_l, 0 <= fi < R_l
+ * -- the kernel cannot check it and reads wherever it points.  Error: dcl_linear_split_fwd's for the product, one rounding per
+ * added term.  A non-finite value in a row of G_l reaches exactly the outputs of the rows m that name it (0 behind a ReLU for NaN). */
+int dcl_linear_split_gather_fwd(const float *x, int64_t ldx, const void *planes, const float *bias, int nfold, const float *fw,
+                                const int32_t *fi, int64_t level_stride, const float *const *G_host, const int64_t *ldg_host,
+                                float *y, int64_t ldy, int M, int N, int K, int relu, dclStream_t stream);
 /* y = act(x Wt + bias) written AS the attention's V pieces (N <= 320 channels from channel 0, rows = keys of crop row /
  * rows_per_crop, rows_per_crop % 256 == 0 = M / crops): `vplanes` = the `planes` scratch of the dcl_cross_attention_ws3 call that
  * consumes it with V1 = NULL. */
