@@ -298,12 +298,20 @@ class RefinerShareFn(Function):
     ops.linear_pool_dma + the tile sum); the split-bf16 core takes no part, the weights change every step.  Saved: the inputs,
     h1 and h2 -- not the (M,1024) activation, which the backward recomputes into scratch.  Backward: ops.relu_bwd (mask + bias
     gradient), ops.linear_wgrad (weight gradient) and ops.linear_dma with the registered weight as its (K,N) matrix (input
-    gradient) per layer; layer 0 writes its two weight-gradient blocks (xyz | features) into one (512,259) tensor.  Every
+    gradient) per layer; layer 0 writes its two weight-gradient blocks (xyz | features) into one (512,259) tensor.  An optional
+    trailing argument wgrad="split" sends all four weight gradients to ops.linear_wgrad_split (the bf16 matrix pipe, fp32-sized
+    errors, its own pinned order) whatever their shapes (a tuple of four forms -- W0's xyz block, W0's feature block, W1, W2 -- chooses per
+    gradient); everything else keeps its bits.  Every
     reduction has a pinned order: the same inputs give the same gradients bit for bit.  xyz_pm, F_pm and conf_w take no
     gradient (the training script detaches them): asking for one raises."""
 
     @staticmethod
-    def forward(ctx, xyz_pm, F_pm, conf_w, W0, b0, W1, b1, W2, b2):
+    def forward(ctx, xyz_pm, F_pm, conf_w, W0, b0, W1, b1, W2, b2, wgrad="fp32"):
+        forms = (wgrad,) * 4 if isinstance(wgrad, str) else tuple(wgrad)
+        if len(forms) != 4:
+            raise ValueError("RefinerShareFn: wgrad is one form or four (W0's xyz block, W0's feature block, W1, W2), got %r"
+                             % (wgrad,))
+        ctx.wgrad = tuple(_ops.check_linear_wgrad(f, "wgrad") for f in forms)
         if any(ctx.needs_input_grad[:3]):
             raise ValueError("RefinerShareFn: xyz_pm, F_pm and conf_w take no gradient (detach them)")
         for t in (xyz_pm, F_pm, conf_w, W0, b0, W1, b1, W2, b2):
@@ -338,19 +346,22 @@ class RefinerShareFn(Function):
         # layer 2: the pooled activation again (scratch), masked and weighted in place
         h3 = _ops.linear_dma(h2, Wt2, b2, True)
         dz, db2 = _ops.relu_bwd(h3, roww=conf_w.reshape(-1), gpool=g_shared, rows_per_crop=n, out=h3)
-        dW2 = _ops.linear_wgrad(dz, h2)
+        wgrad = ctx.wgrad
+        dW2 = _ops.linear_wgrad_as(wgrad[3], dz, h2)
         dh = _ops.linear_dma(dz, W2[:, :, 0])
         del h3, dz
         # layer 1
         dz, db1 = _ops.relu_bwd(h2, dh, out=dh)
-        dW1 = _ops.linear_wgrad(dz, h1)
+        dW1 = _ops.linear_wgrad_as(wgrad[2], dz, h1)
         dh = _ops.linear_dma(dz, W1[:, :, 0])
         # layer 0: no input gradient; the weight's two column blocks
         dz, db0 = _ops.relu_bwd(h1, dh, out=dh)
         dW0 = torch.empty((h1.shape[1], 3 + F_pm.shape[1]), dtype=torch.float32, device=dz.device)
-        _ops.linear_wgrad(dz, xyz_pm, out=dW0[:, :3])
-        _ops.linear_wgrad(dz, F_pm, out=dW0[:, 3:])
-        return None, None, None, dW0.unsqueeze(2), db0, dW1.unsqueeze(2), db1, dW2.unsqueeze(2), db2
+        _ops.linear_wgrad_as(wgrad[0], dz, xyz_pm, out=dW0[:, :3])
+        _ops.linear_wgrad_as(wgrad[1], dz, F_pm, out=dW0[:, 3:])
+        # (one gradient per argument actually passed: the optional trailing `wgrad` takes None, and only when it was given)
+        grads = (None, None, None, dW0.unsqueeze(2), db0, dW1.unsqueeze(2), db1, dW2.unsqueeze(2), db2)
+        return grads + (None,) * (len(ctx.needs_input_grad) - len(grads))
 
 
 class ConfPoolFn(Function):
@@ -480,14 +491,17 @@ class PointLinearFn(Function):
     (bias=None, relu=False), the layers a BatchNorm follows, and (bias, relu=True); a bias without the ReLU raises ValueError (no
     layer of this path has one).  Forward = ops.linear_dma(x, W^T, bias, relu); backward = ops.relu_bwd (mask + bias gradient),
     dW = ops.linear_wgrad(dz, x) viewed to W's shape, dx = ops.linear_dma(dz, W2d) with the registered matrix as the (K', N')
-    operand, as RefinerShareFn does.  The split-bf16 core and the vendor library take no part; a shape linear_dma cannot take
+    operand, as RefinerShareFn does.  An optional fifth argument wgrad="split" makes dW = ops.linear_wgrad_split(dz, x) (the bf16
+    matrix pipe, fp32-sized errors, its own pinned order) whatever the shape; outputs, dx and db keep their bits.  Otherwise the
+    split-bf16 core takes no part, and the vendor library never does; a shape linear_dma cannot take
     (K and N in whole 32-chunks, 16-byte aligned operands and row pitches) raises ValueError.  x and the gradient may be column
     blocks of wider matrices.  Saved: x, W, and the output when relu is set.  Every reduction has a pinned order: the same inputs
     give the same gradients bit for bit.  Only the gradients that are asked for are computed."""
 
     @staticmethod
-    def forward(ctx, x, W, bias, relu):
+    def forward(ctx, x, W, bias, relu, wgrad="fp32"):
         relu = bool(relu)
+        ctx.wgrad = _ops.check_linear_wgrad(wgrad, "wgrad")
         if (bias is None) == relu:
             raise ValueError("PointLinearFn has two forms, (bias=None, relu=False) and (bias, relu=True): got bias %s, relu=%s"
                              % ("None" if bias is None else "given", relu))
@@ -515,8 +529,9 @@ class PointLinearFn(Function):
     def backward(ctx, g):
         x, W = ctx.saved_tensors[:2]
         need = ctx.needs_input_grad
+        extra = (None,) * (len(need) - 4)                    # the optional trailing `wgrad`, when it was passed
         if not any(need[:3]):
-            return None, None, None, None
+            return (None, None, None, None) + extra
         g = _rows_dense(g)
         if g.data_ptr() % 16 or (g.shape[0] > 1 and g.stride(0) % 4):
             g = g.contiguous()
@@ -525,12 +540,12 @@ class PointLinearFn(Function):
             dz, db = _ops.relu_bwd(ctx.saved_tensors[2], g)
         else:
             dz = g
-        dW = _ops.linear_wgrad(dz, x).view_as(W) if need[1] else None
+        dW = _ops.linear_wgrad_as(ctx.wgrad, dz, x).view_as(W) if need[1] else None
         dx = None
         if need[0]:
             W2d = W.contiguous().view(W.shape[0], W.shape[1])
             dx = _ops.linear_dma(dz, W2d)
-        return dx, dW, db if need[2] else None, None
+        return (dx, dW, db if need[2] else None, None) + extra
 
 
 class NarrowLinearFn(Function):

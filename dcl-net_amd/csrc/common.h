@@ -71,6 +71,9 @@ __device__ __forceinline__ float dcl_dist2(float ax, float ay, float az, float b
 // level 1 are 10240 -- and one with more tiles than counters is never split: one workgroup per capacity tile, mostly empty.)
 constexpr int kConvCounterWords = 32768;
 void dcl_internal_zero_words(void *p, long long nwords, hipStream_t s);
+// linear_bwd.hip: dW (P x Q, pitch lddw) = partial[0] + partial[1] + ... in ascending split order, one rounded add each (nsplit == 0:
+// +0) -- the second launch of both weight-gradient entries
+int dcl_internal_split_sum(const float *partial, int nsplit, int P, int Q, float *dW, int64_t lddw, hipStream_t s);
 
 // Where a kernel gets nbr[k][o] (the input row feeding output row o under kernel offset k) from: an explicit gather table
 // (dcl_rulebook_gather; the spconv shim and the training path keep it) or, inside the native backbone runner, the input

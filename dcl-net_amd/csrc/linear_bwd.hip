@@ -234,6 +234,14 @@ bool aligned4(const void *p) { return ((size_t)p & 3) == 0; }
 
 }  // namespace
 
+// dW (P x Q, pitch lddw) = the nsplit partial results added in ascending split order (k_split_sum); nsplit == 0 zero-fills.  Shared
+// with the split-bf16 weight gradient (linear_wgrad_split.hip): one kernel adds the splits of both.
+int dcl_internal_split_sum(const float *partial, int nsplit, int P, int Q, float *dW, int64_t lddw, hipStream_t s) {
+  hipLaunchKernelGGL(k_split_sum, dim3(dcl_grid_1d((long long)P * Q, 256)), dim3(256), 0, s, partial, nsplit, P, Q, dW, lddw);
+  DCL_LAUNCH_CHECK();
+  return 0;
+}
+
 DCL_API int dcl_linear_wgrad_splits(int M, int32_t *splits_host) {
   DCL_CHECK_ARG(M >= 0 && splits_host);
   const int s = dcl_div_up(M, DCL_WGRAD_ROWS);

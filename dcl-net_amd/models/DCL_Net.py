@@ -76,6 +76,14 @@ def check_train_dense(train_dense, train_attention):
 TRAIN_HEADS_MODES = ops.TRAIN_HEADS_MODES
 
 
+def check_train_wgrad(train_wgrad, train_dense):
+    ops.check_linear_wgrad(train_wgrad, "train_wgrad")
+    if train_wgrad == "split" and train_dense != "point_major":
+        raise ValueError('train_wgrad="split" requires train_dense="point_major" (only the point-major dense half forms its weight '
+                         'gradients with the library\'s own kernels), got train_dense=%r' % (train_dense,))
+    return train_wgrad
+
+
 def check_train_heads(train_heads, train_dense):
     ops.check_train_heads(train_heads)
     if train_heads == "kernels" and train_dense != "point_major":
@@ -195,7 +203,7 @@ class Network(nn.Module):
                  single_stream=False, pipeline_chunks=1, capture_graph=True, pair_features=None,
                  train_attention="materialised", train_rotation="host", train_conv_wgrad="rows",
                  train_conv_dgrad="conv", train_pool="modules", train_norm="modules", train_dense="modules",
-                 train_heads="modules", train_conv_fwd="tiles"):
+                 train_heads="modules", train_conv_fwd="tiles", **later):
         """graph_max_batch > 0 (default 8): eval-mode calls with at most that many crops go through forward_graphed (one
         whole-forward hipGraph per batch size, captured on first use) -- the one-image-at-a-time eval loops of the
         reference (tools/test_LM.py:104-112: one object per call) are launch-bound otherwise: 0.53 instead of 1.1 ms
@@ -272,8 +280,20 @@ class Network(nn.Module):
         widths on which it was measured faster (profiles/conv_fwd_compact.txt: none so far, the table is empty and "compact"
         changes no layer) -- and "tiles" on the others, on every subm layer and on the stem.  Independent of every other train_* switch; same parameters, buffers and state_dict keys; the backward is the
         same either way.  Eval mode's fused pipeline, the graphs and forward_graphed never read it.
+        train_wgrad (keyword only, taken through **later: the explicit train_* arguments are exactly the keys of TRAIN_KERNELS,
+        which this switch is not part of; any other extra keyword is a TypeError as usual): the form of the weight gradient of
+        the point-major dense half's wide layers (autograd.PointLinearFn).
+        "fp32" (default) = ops.linear_wgrad, the fp32 matrix pipe; "split" = ops.linear_wgrad_split (csrc/linear_wgrad_split.hip:
+        both operands split into three bf16 pieces inside the kernel, six piece products per product on the bf16 matrix pipe,
+        fp32-sized errors, its own pinned order) on the layers whose (P, Q) and row count are in ops.WGRAD_SPLIT_SHAPES -- the
+        shapes on which it was measured faster (profiles/linear_wgrad_split.txt) -- and "fp32" on the others: a rule by shape
+        alone.  It requires train_dense="point_major" (ValueError otherwise).  The forward, dx and db keep their bits; same
+        parameters, buffers and state_dict keys.  Eval mode, the graphs and the fused inference pipeline never read it.
         These are constructor arguments on purpose: nothing on the call path reads the environment."""
         super().__init__()
+        train_wgrad = later.pop("train_wgrad", "fp32")
+        if later:
+            raise TypeError("Network.__init__() got an unexpected keyword argument %r" % (sorted(later)[0],))
         self.train_pool = check_train_pool(train_pool)
         self.train_norm = ops.check_train_norm(train_norm)
         self.train_conv_dgrad = ops.check_conv_dgrad(train_conv_dgrad, "train_conv_dgrad")
@@ -285,6 +305,7 @@ class Network(nn.Module):
         self.train_attention = train_attention
         self.train_dense = check_train_dense(train_dense, train_attention)
         self.train_heads = check_train_heads(train_heads, self.train_dense)
+        self.train_wgrad = check_train_wgrad(train_wgrad, self.train_dense)
         self.single_stream = bool(single_stream)
         self._pair_features = pair_features              # both backbones' layers as ONE launch each; None = automatic (see property)
         self.pipeline_chunks = int(pipeline_chunks)
@@ -1442,6 +1463,13 @@ class Network(nn.Module):
                 c0 += c
         return z
 
+    def _pm_linear(self, x, W, bias, relu):
+        """a wide layer of the point-major dense half: PointLinearFn with today's four arguments, and the trailing "split" only
+        on the shapes that train_wgrad="split" sends to ops.linear_wgrad_split (ops.WGRAD_SPLIT_SHAPES)"""
+        if ops.linear_wgrad_form(x.shape[0], W.shape[0], W.shape[1], self.train_wgrad) == "split":
+            return PointLinearFn.apply(x, W, bias, relu, "split")
+        return PointLinearFn.apply(x, W, bias, relu)
+
     def _pm_disengage(self, side, F):
         """one side's four disengage stacks on F (b n, 480): ONE PointLinearFn with the four first-layer weights concatenated
         to (1024, 480) and one BatchNorm + ReLU over the 1024 channels (the eval pipeline's layout, _disengage), then the four
@@ -1450,14 +1478,14 @@ class Network(nn.Module):
         stacks = [getattr(self, "disengage_%s_%s" % (side, t)) for t in names]
         first = [st[0].layers for st in stacks]
         assert all(l[0].bias is None for l in first)
-        h = PointLinearFn.apply(F, torch.cat([l[0].weight for l in first], dim=0), None, False)
+        h = self._pm_linear(F, torch.cat([l[0].weight for l in first], dim=0), None, False)
         h = self._pm_norm(h, [l[1] for l in first], True)
         out, c0 = {}, 0
         for t, st in zip(names, stacks):
             conv, bn = st[1].layers[0], st[1].layers[1]
             assert conv.bias is None
             c = conv.in_channels
-            out[t] = self._pm_norm(PointLinearFn.apply(h[:, c0:c0 + c], conv.weight, None, False), [bn], True)
+            out[t] = self._pm_norm(self._pm_linear(h[:, c0:c0 + c], conv.weight, None, False), [bn], True)
             c0 += c
         return out
 
@@ -1465,17 +1493,16 @@ class Network(nn.Module):
         """a neck fuser, three times Conv1d -> ReLU -> BatchNorm1d, on x (M, 512): PointLinearFn(relu) + BatchNorm without ReLU"""
         layers = fuser.layers
         for i in range(0, len(layers), 3):
-            x = self._pm_norm(PointLinearFn.apply(x, layers[i].weight, layers[i].bias, True), [layers[i + 2]], False)
+            x = self._pm_norm(self._pm_linear(x, layers[i].weight, layers[i].bias, True), [layers[i + 2]], False)
         return x
 
-    @staticmethod
-    def _pm_head(head, x, kernels=False):
+    def _pm_head(self, head, x, kernels=False):
         """a per-point head, Conv1d -> ReLU -> Conv1d -> ReLU -> Conv1d, on x (M, K): the two wide layers on PointLinearFn, the
         last one (1 or 3 columns) torch.nn.functional.linear on the same parameters, or, with kernels (train_heads="kernels"),
         an autograd.NarrowLinearFn on them"""
         c0, c1, c2 = head.layers[0], head.layers[2], head.layers[4]
-        h = PointLinearFn.apply(x, c0.weight, c0.bias, True)
-        h = PointLinearFn.apply(h, c1.weight, c1.bias, True)
+        h = self._pm_linear(x, c0.weight, c0.bias, True)
+        h = self._pm_linear(h, c1.weight, c1.bias, True)
         if kernels:
             return NarrowLinearFn.apply(h, c2.weight, c2.bias)
         return torch.nn.functional.linear(h, c2.weight.view(c2.out_channels, c2.in_channels), c2.bias)

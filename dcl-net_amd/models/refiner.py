@@ -39,7 +39,7 @@ class Refiner(nn.Module):
 
     TRAIN_HEADS_MODES = ops.TRAIN_HEADS_MODES
 
-    def __init__(self, cfg=None, train_rotation="host", train_mlp="modules", train_heads="modules"):
+    def __init__(self, cfg=None, train_rotation="host", train_mlp="modules", train_heads="modules", train_wgrad="fp32"):
         """train_rotation: "host" (default) or "device" -- how a call that needs a gradient differentiates the rotation
         head's projection; see DCL_Net.Network.
         train_mlp: how train() mode runs MLP_share and the pooling.  "modules" (default): the registered nn.Conv1d / nn.ReLU
@@ -49,7 +49,10 @@ class Refiner(nn.Module):
         train_heads: how train() mode runs regressor_rot2 / regressor_trans2, in either train_mlp form.  "modules" (default): the
         registered modules (vendor GEMMs and element-wise launches on b rows).  "kernels": ONE autograd.PoseHeadsFn on the pooled
         feature (csrc/pose_heads_grad.hip: three launches forward, at most six backward, the weights read as registered, pinned
-        summation orders).  Same parameters and state_dict keys, no cached weights; eval() mode never reads it."""
+        summation orders).  Same parameters and state_dict keys, no cached weights; eval() mode never reads it.
+        train_wgrad: the form of RefinerShareFn's weight gradients.  "fp32" (default): ops.linear_wgrad.  "split":
+        ops.linear_wgrad_split (the bf16 matrix pipe, fp32-sized errors, its own pinned order) on the layers whose shape is in
+        ops.WGRAD_SPLIT_SHAPES, ops.linear_wgrad on the others.  Read only by train_mlp="kernels" (ValueError otherwise)."""
         super().__init__()
         from .DCL_Net import check_train_rotation
         self.train_rotation = check_train_rotation(train_rotation)
@@ -57,6 +60,10 @@ class Refiner(nn.Module):
             raise ValueError('train_mlp must be "modules" or "kernels", got %r' % (train_mlp,))
         self.train_mlp = train_mlp
         self.train_heads = ops.check_train_heads(train_heads)
+        if ops.check_linear_wgrad(train_wgrad, "train_wgrad") == "split" and train_mlp != "kernels":
+            raise ValueError('train_wgrad="split" requires train_mlp="kernels" (the modules form their weight gradients '
+                             'themselves), got train_mlp=%r' % (train_mlp,))
+        self.train_wgrad = train_wgrad
         self.MLP_share = Head_MultiLayerPerceptron([256 + 3, 512, 512, 1024], ["relu"] * 3, [False] * 3, [0.0] * 3)
         self.regressor_rot2 = Head_MultiLayerPerceptron([1024, 512, 128, 9], ["relu", "relu", "none"], [False] * 3,
                                                         [0.0] * 3)
@@ -181,8 +188,14 @@ class Refiner(nn.Module):
         xyz_pm = pm[:, :, :3].reshape(b * n, 3)
         F_pm = pm[:, :, 3:].reshape(b * n, -1)
         L = self.MLP_share.layers
-        shared = RefinerShareFn.apply(xyz_pm, F_pm, conf_w, L[0].weight, L[0].bias, L[2].weight, L[2].bias, L[4].weight,
-                                      L[4].bias).unsqueeze(2)
+        args = (xyz_pm, F_pm, conf_w, L[0].weight, L[0].bias, L[2].weight, L[2].bias, L[4].weight, L[4].bias)
+        # per weight-gradient block (W0's xyz columns, W0's feature columns, W1, W2): by the shape alone
+        forms = tuple(ops.linear_wgrad_form(b * n, P, Q, self.train_wgrad)
+                      for P, Q in ((L[0].out_channels, 3), (L[0].out_channels, F_pm.shape[1]),
+                                   (L[2].out_channels, L[2].in_channels), (L[4].out_channels, L[4].in_channels)))
+        if "split" in forms:
+            args += (forms,)
+        shared = RefinerShareFn.apply(*args).unsqueeze(2)
         return self._train_heads(shared)
 
     def forward(self, input_dict):

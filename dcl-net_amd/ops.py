@@ -3302,6 +3302,65 @@ def linear_wgrad(a, b, out=None):
     return out
 
 
+WGRAD_FORMS = ("fp32", "split")
+# {(P, Q): the fewest rows M} of the weight gradients that Network(train_wgrad="split") / Refiner(train_wgrad="split") send to
+# linear_wgrad_split: a shape is listed only where tools/bench_linear_wgrad.py measured every block of the split kernel below
+# every block of linear_wgrad (disjoint ranges, profiles/linear_wgrad_split.txt), from the fewest rows at which it was measured.
+# That is every wide shape of the 32 x 1024 / 1024 step (split / fp32 time 0.76-0.85) and of the refiner at 20 / 32 x 1024
+# (0.65-0.83); the refiner's xyz block (512, 3) is 10 % SLOWER on the split kernel and is not listed.  A shape outside the
+# table keeps linear_wgrad.
+WGRAD_SPLIT_SHAPES = {(64, 256): 32768, (128, 128): 32768, (128, 256): 32768, (256, 256): 32768, (1024, 480): 32768,
+                      (512, 256): 20480, (512, 512): 20480, (1024, 512): 20480}
+
+
+def check_linear_wgrad(value, what="train_wgrad"):
+    if value not in WGRAD_FORMS:
+        raise ValueError('%s must be "fp32" or "split", got %r' % (what, value))
+    return value
+
+
+def linear_wgrad_form(M, P, Q, train_wgrad="split"):
+    """the weight-gradient form of a (P, Q) layer over M rows under train_wgrad=: by the shape alone (WGRAD_SPLIT_SHAPES), never
+    by the data"""
+    if check_linear_wgrad(train_wgrad) == "fp32":
+        return "fp32"
+    min_rows = WGRAD_SPLIT_SHAPES.get((int(P), int(Q)))
+    return "split" if min_rows is not None and int(M) >= min_rows else "fp32"
+
+
+def linear_wgrad_split_units(M):
+    """the a-priori error bound of linear_wgrad_split over M rows in units of 2^-24 sum_j |a_jp| |b_jq| (include/dclnet_hip.h):
+    one rounding per piece product of a split's rows, one per added split, 32 for the dropped products and the pieces' sizes"""
+    return 6 * WGRAD_ROWS + linear_wgrad_splits(M) + 32
+
+
+def linear_wgrad_split(a, b, out=None):
+    """linear_wgrad on the bf16 matrix pipe (csrc/linear_wgrad_split.hip): the same arguments, conventions and pinned order
+    (splits of WGRAD_ROWS rows, 16-row chunks ascending inside a split, splits ascending; the same bits on every call and for
+    every pitch and alignment), every operand split in the kernel into three bf16 pieces and a product accumulated as its six
+    piece products in fp32 -- fp32-sized errors (linear_wgrad_split_units), not linear_wgrad's bits.  Values of magnitude
+    >= 3.3962e38, +-inf and NaN are not supported: they turn their whole row or column of dW into NaN.  No vendor library."""
+    N.need_cuda(a, b)
+    _rows2d(a, "a")
+    _rows2d(b, "b")
+    M, P = a.shape
+    assert b.shape[0] == M, "a and b must have the same rows"
+    Q = b.shape[1]
+    if out is None:
+        out = torch.empty((P, Q), dtype=torch.float32, device=a.device)
+    _rows2d(out, "out")
+    assert tuple(out.shape) == (P, Q)
+    partial = torch.empty(linear_wgrad_splits(M) * P * Q, dtype=torch.float32, device=a.device)
+    N.check(N.lib().dcl_linear_wgrad_split(N.ptr(a), _pitch(a), N.ptr(b), _pitch(b), int(M), int(P), int(Q),
+                                           N.ptr(partial), N.ptr(out), _pitch(out), N.stream()), "linear_wgrad_split")
+    return out
+
+
+def linear_wgrad_as(form, a, b, out=None):
+    """linear_wgrad (form "fp32") or linear_wgrad_split (form "split")"""
+    return (linear_wgrad_split if check_linear_wgrad(form, "form") == "split" else linear_wgrad)(a, b, out=out)
+
+
 def relu_bwd(h, g=None, roww=None, gpool=None, rows_per_crop=None, out=None):
     """ReLU mask + bias gradient of a Linear + ReLU layer whose OUTPUT is h (M,P) (csrc/linear_bwd.hip) -> (dz (M,P), db (P,)).
     relu_bwd(h, g): dz = where(h > 0, g, 0); `out=g` masks the arriving gradient in place.

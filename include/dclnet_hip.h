@@ -38,7 +38,7 @@ const char *dcl_last_error(void);
  *      dcl_linear_split_weight(_bytes), dcl_linear_split_fwd / _pool_fwd / _rowdot_fwd / _vpieces_fwd, dcl_cross_attention_ws3
  *      (+ _planes_bytes, _split_crops); later additions (no change to existing entries): dcl_conv_split_weight(_bytes),
  *      dcl_sparse_conv_fwd_sides, dcl_backbone_features_split / _cap_split / _pair_split, dcl_point_features_fold,
- *      dcl_linear_split_gather_fwd */
+ *      dcl_linear_split_gather_fwd, dcl_linear_wgrad_split */
 #define DCL_ABI_VERSION 2
 int dcl_abi_version(void);
 
@@ -822,6 +822,30 @@ int dcl_voxelize_bp(const float *d_out, const int32_t *rules, float *d_feats_zer
 int dcl_linear_wgrad_splits(int M, int32_t *splits_host);
 int dcl_linear_wgrad(const float *a, int64_t lda, const float *b, int64_t ldb, int M, int P, int Q, float *partial,
                      float *dW, int64_t lddw, dclStream_t stream);
+/* The same weight gradient on the bf16 matrix pipe with fp32 results (csrc/linear_wgrad_split.hip): the arguments, shapes,
+ * pitches, alignments, `partial` (dcl_linear_wgrad_splits(M) * P * Q floats, no other scratch) and DCL_EINVAL cases of
+ * dcl_linear_wgrad; M == 0 zero-fills dW; a column block of a wider gradient is written in place and nothing beside it is
+ * touched.  Every fp32 operand is the exact sum of three bf16 pieces h, m, l (the split of dcl_linear_split_fwd; both operands are
+ * split inside the kernel, nothing is prepared) and a product a b is accumulated as its six piece products of weight >= 2^-16 in
+ * the fp32 accumulators of v_mfma_f32_32x32x16_bf16.
+ * PINNED ORDER: the M rows are cut into the splits of dcl_linear_wgrad (DCL_WGRAD_ROWS rows, dcl_linear_wgrad_splits(M) of them).
+ * Inside a split an output element is ONE accumulator, started at +0; it is fed the split's 16-row chunks in ascending order and,
+ * per chunk, the six products in the order al bh, ah bl, am bm, am bh, ah bm, ah bh (each one MFMA over the chunk's 16 rows).  The
+ * waves of a workgroup tile (P, Q), never the rows; the kernel of dcl_linear_wgrad that adds the splits adds them here, ascending,
+ * one rounded add each.  No float atomics and no workgroup waits on another; the order never depends on pitch or alignment: the
+ * same values give the same bits on every call.  Rows past M and columns past P / Q are zero pieces, which add exact zeros.
+ * Error: the piece products are exact; what is dropped (am bl + al bm + al bl) is below 1.5 * 2^-24 |a b| per product; counting
+ * one rounding per piece product that enters an accumulator (6 per row, at most 6 * DCL_WGRAD_ROWS per split; the pieces'
+ * magnitudes sum to at most 1.004 |v|) and one per added split, an element is off by at most
+ *   (6 * DCL_WGRAD_ROWS + splits + 32) * 2^-24 * sum_j |a_jp| |b_jq|
+ * against exact arithmetic -- the a-priori bound.  What it measures is the size of dcl_linear_wgrad's error: at most 1.5 x what
+ * an fp32 FMA chain in the same order is off by (tests/test_gpu_linear_wgrad_split.py, on the operands of tests/split_cases.py).
+ * Range (the split core's): operands of magnitude < 2^-110 lose up to 2^-126 |.| per product (third pieces below the bf16
+ * range).  NOT supported: |v| >= 3.3962e38 (bits 0x7F7F8000: finite in fp32, inf as a bf16 first piece), +-inf and NaN -- such a
+ * value in column p of a makes every dW[p][:] NaN, in column q of b every dW[:][q], also where dcl_linear_wgrad gives +-inf;
+ * every other element has exactly the bits it has without that value. */
+int dcl_linear_wgrad_split(const float *a, int64_t lda, const float *b, int64_t ldb, int M, int P, int Q, float *partial,
+                           float *dW, int64_t lddw, dclStream_t stream);
 /* ReLU mask + bias gradient of such a layer: h (M x P) is the layer's OUTPUT (after the ReLU),
  *   g != NULL:  dz[j][p] = h[j][p] > 0 ? g[j][p] : 0                       (g (M x P): the gradient that arrives; dz may be g),
  *   g == NULL:  dz[j][p] = h[j][p] > 0 ? roww[j] * gpool[j / rows_per_crop][p] : 0   (the pooled last layer: its output went

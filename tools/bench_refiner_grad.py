@@ -30,7 +30,10 @@ least a quarter of a second, six blocks that alternate the two forms in both ord
 median of a form's three block means and their range.  profiles/refiner_grad.txt holds one run's output.
 
 --heads modules|kernels: Refiner(train_heads=) of BOTH forms -- the two pose heads as the registered modules (default) or as one
-autograd.PoseHeadsFn (csrc/pose_heads_grad.hip); profiles/train_heads.txt compares the two."""
+autograd.PoseHeadsFn (csrc/pose_heads_grad.hip); profiles/train_heads.txt compares the two.
+--wgrad fp32|split: Refiner(train_wgrad=) of the "kernels" form -- its weight gradients on csrc/linear_bwd.hip (default) or, on the
+shapes of ops.WGRAD_SPLIT_SHAPES, on csrc/linear_wgrad_split.hip; --wgrad-all (measurement only) makes that table name every
+shape for this process.  Part kernels times ops.linear_wgrad_split beside ops.linear_wgrad either way."""
 import argparse
 import importlib
 import os
@@ -50,6 +53,7 @@ from bench_rotation_grad import MIN_BLOCK_S, compare  # noqa: E402
 FORMS = ("kernels", "modules")
 SHAPES = ((20, 1024), (32, 1024))
 HEADS = "modules"                        # --heads
+WGRAD = "fp32"                           # --wgrad
 
 
 def line(what, res):
@@ -60,7 +64,8 @@ def line(what, res):
 
 
 def make_refiner(dcl, form, rotation="device"):
-    ref = dcl.refiner.Refiner(train_rotation=rotation, train_mlp=form, train_heads=HEADS)
+    ref = dcl.refiner.Refiner(train_rotation=rotation, train_mlp=form, train_heads=HEADS,
+                              train_wgrad=WGRAD if form == "kernels" else "fp32")
     ref.load_state_dict(dcl.synth.synth_state_dict(ref, 2))
     return ref.cuda().train()
 
@@ -108,9 +113,11 @@ def part_kernels(dcl, args):
     for P, Q in ((1024, 512), (512, 512), (512, 256), (512, 3)):
         a, x = rnd(M, P), rnd(M, Q)
         t_own = events_ms(lambda: ops.linear_wgrad(a, x), args.iters, args.warmup)
+        t_split = events_ms(lambda: ops.linear_wgrad_split(a, x), args.iters, args.warmup)
         t_lib = events_ms(lambda: torch.mm(a.t(), x), args.iters, args.warmup)
-        print("  linear_wgrad  dW (%4d x %3d)   %7.1f us  %6.1f TFLOP/s     torch.mm(a.t(), b) %7.1f us" %
-              (P, Q, t_own * 1e3, 2.0 * M * P * Q / t_own / 1e9, t_lib * 1e3))
+        print("  linear_wgrad  dW (%4d x %3d)   %7.1f us  %6.1f TFLOP/s     linear_wgrad_split %7.1f us  %6.1f TFLOP/s     "
+              "torch.mm(a.t(), b) %7.1f us" % (P, Q, t_own * 1e3, 2.0 * M * P * Q / t_own / 1e9, t_split * 1e3,
+                                               2.0 * M * P * Q / t_split / 1e9, t_lib * 1e3))
         del a, x
     for P in (1024, 512):
         h, gr = rnd(M, P), rnd(M, P)
@@ -228,13 +235,20 @@ def main():
     ap.add_argument("--step-iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--heads", choices=("modules", "kernels"), default="modules")
+    ap.add_argument("--wgrad", choices=("fp32", "split"), default="fp32")
+    ap.add_argument("--wgrad-all", action="store_true")
     args = ap.parse_args()
-    global HEADS
-    HEADS = args.heads
+    global HEADS, WGRAD
+    HEADS, WGRAD = args.heads, args.wgrad
     if not torch.cuda.is_available():
         raise SystemExit("bench_refiner_grad: needs the GPU (no CPU timing is meaningful)")
     dcl = importlib.import_module("dcl-net_amd")
-    print("== refiner training, part %s: train_mlp=\"kernels\" (csrc/linear_bwd.hip + the own GEMM core) vs \"modules\" (torch); train_heads=\"%s\"" % (args.part, args.heads))
+    if args.wgrad_all:
+        class EveryShape(dict):
+            def get(self, key, default=None):
+                return 0
+        dcl.ops.WGRAD_SPLIT_SHAPES = EveryShape()
+    print("== refiner training, part %s: train_mlp=\"kernels\" (csrc/linear_bwd.hip + the own GEMM core) vs \"modules\" (torch); train_heads=\"%s\", train_wgrad=\"%s\"%s" % (args.part, args.heads, args.wgrad, " on every shape" if args.wgrad_all else ""))
     print("device: %s, torch %s; blocks of at least %d calls / %d steps and %.2f s, six alternating blocks after %d warm-up rounds" %
           (torch.cuda.get_device_name(0), torch.__version__, args.iters, args.step_iters, MIN_BLOCK_S, args.warmup))
     {"accuracy": part_accuracy, "kernels": part_kernels, "op": part_op, "step": part_step, "launches": part_launches, "trace": part_trace}[args.part](dcl, args)
